@@ -7,15 +7,22 @@ BASELINE.json (20x20 TFIM, chi=32, ComplexF32, batched edge-colour apply on one 
 (iid complex-normal site tensors at bond dimension chi) and resident in HBM before the timed region.
 
 Prints ONE JSON line (rank 0).  Extra objects: "roofline" for the dominant kernel class (HIP-event timed inside the
-library on its own stream) and "cpu_baseline" (oracle/cpu_layer.py: the threaded CPU restatement of the same path, timed on the host
-cores on a bounded sample, next to the host's measured BLAS rates).  With --gpus N the lattice is sharded by vertex over N ranks and
-every exchange is an ncclAllGather the library enqueues on its own stream (RCCL inside the library, tnqs_set_sharding_rccl).
+library on its own stream).  With --full also "cpu_baseline" (oracle/cpu_port.cpp: the compiled CPU restatement of the same path, timed
+on the host cores on a bounded sample, next to the host's measured BLAS rates) and, for the headline configuration, the same command
+with the f32 matrix instructions and with the reference's sweep order, each in a child process; a plain run only sets up, warms up,
+times the steps and prints the line.  With --gpus N the lattice is sharded by vertex over N ranks and every exchange is an
+ncclAllGather the library enqueues on its own stream (RCCL inside the library, tnqs_set_sharding_rccl).
+
+--dump-outputs DIR (one GPU) writes what the last timed step returned -- the truncation errors, a fixed seeded sample of the site
+tensors and of the BP messages -- as DIR/<name>.npy (complex values as a trailing (real, imag) axis), so that two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "oracle")):
@@ -33,19 +40,75 @@ def tfim_layer(tn, g, groups, J=1.0, hx=2.5, dt=0.01):
     return layer
 
 
-def random_state_tensors(g, chi, d, seed, dtype, wanted=None):
+def random_state_tensors(g, chi, d, seed, dtype, wanted=None, threads=1):
     """iid complex-normal site tensors at bond dimension chi; one counter-based stream per vertex (seed, vertex position), so that a
-    rank of a sharded run only generates its own tensors.  Yields (v, tensor) for wanted vertices and (v, shape) for the others."""
-    for i, v in enumerate(g.vertices):
-        shp = (d,) + (chi,) * g.degree(v)
-        if wanted is not None and not wanted(v):
-            yield v, shp
-            continue
+    rank of a sharded run only generates its own tensors.  Yields (v, tensor) for wanted vertices and (v, shape) for the others, in
+    vertex order.  `threads` vertices are generated at a time (numpy's generators release the GIL); the values do not depend on it."""
+    def make(i, shp):
         n = int(np.prod(shp))
         rng = np.random.default_rng([seed, i])
         t = rng.standard_normal(2 * n, dtype=np.float32).view(np.complex64).reshape(shp)
         t *= np.float32(1.0 / np.sqrt(n))                       # unit Frobenius norm (f32-friendly scale)
-        yield v, t.astype(dtype, copy=False)
+        return t.astype(dtype, copy=False)
+
+    items = [(i, v, (d,) + (chi,) * g.degree(v)) for i, v in enumerate(g.vertices)]
+    chunk = 2 * max(1, threads)                                 # (bounds the host memory held at once)
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        for k in range(0, len(items), chunk):
+            part = items[k:k + chunk]
+            futs = [None if (wanted is not None and not wanted(v)) else pool.submit(make, i, shp) for i, v, shp in part]
+            for (i, v, shp), f in zip(part, futs):
+                yield v, (shp if f is None else f.result())
+
+
+def host_threads():
+    """CPUs this process may use for host-side set-up, at most 16 (more only contend with the rest of the host)"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
+
+
+DUMP_SEED = 20240601
+DUMP_MAX_VERTICES, DUMP_MAX_ELEMENTS, DUMP_MAX_EDGES = 32, 65536, 512
+
+
+def _real_view(a):
+    """complex -> trailing (real, imag) axis; float32 for single, float64 for double precision"""
+    a = np.asarray(a)
+    ft = np.float32 if a.dtype in (np.complex64, np.float32) else np.float64
+    if np.iscomplexobj(a):
+        return np.stack([a.real, a.imag], axis=-1).astype(ft, copy=False)
+    return a.astype(ft, copy=False)
+
+
+def dump_outputs(path, bpc, g, errs):
+    """what a caller of apply_gates received from the last timed step, on a fixed sample: the truncation errors of every gate, up to
+    DUMP_MAX_VERTICES site tensors (positions drawn with DUMP_SEED) with up to DUMP_MAX_ELEMENTS entries each (flat C-order positions
+    drawn from the stream (DUMP_SEED, vertex position)), and up to DUMP_MAX_EDGES BP messages (directed edges in the order of g.edges,
+    each edge followed by its reverse, drawn with DUMP_SEED).  The sample depends only on the lattice and the shapes."""
+    os.makedirs(path, exist_ok=True)
+    verts = list(g.vertices)
+    rng = np.random.default_rng(DUMP_SEED)
+    pos = np.arange(len(verts)) if len(verts) <= DUMP_MAX_VERTICES else np.sort(rng.choice(len(verts), DUMP_MAX_VERTICES, replace=False))
+    parts = []
+    for i in pos:
+        t = bpc.tensor(verts[i]).reshape(-1)
+        if t.size > DUMP_MAX_ELEMENTS:
+            t = t[np.sort(np.random.default_rng([DUMP_SEED, int(i)]).choice(t.size, DUMP_MAX_ELEMENTS, replace=False))]
+        parts.append(t)
+    directed = [e for (a, b) in g.edges for e in ((a, b), (b, a))]
+    epos = np.arange(len(directed)) if len(directed) <= DUMP_MAX_EDGES else np.sort(rng.choice(len(directed), DUMP_MAX_EDGES, replace=False))
+    msgs = [bpc.message(directed[k]).reshape(-1) for k in epos]
+    out = {"truncation_errors": np.asarray(errs, dtype=np.float64),
+           "site_tensor_sample": _real_view(np.concatenate(parts)),
+           "message_sample": _real_view(np.concatenate(msgs))}
+    total = sum(a.nbytes for a in out.values())
+    if total > 64e6:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 1e6:.1f} MB (limit 64 MB)")
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(chi, L, seed=1234):
@@ -163,7 +226,8 @@ def main_c1(args, tn, torch):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     prof_all = tn.profile_get(bpc)
-    z_dev = tn.expect_all(bpc, "Z").real
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bpc, g, errs)
     n2 = g.ne()
     sat = [t for t, c in zip(per_layer, chis) if c >= chi]
     out = {"metric": "two-site gates/sec at fixed chi (LxL TFIM Trotter layer)", "value": round(n2 * args.steps / elapsed, 2), "unit": "two-site gates/s", "n_gpus": 1,
@@ -179,9 +243,10 @@ def main_c1(args, tn, torch):
                                                     "measured is the dependent chain of ~330 launches per layer, see kernel_classes and DESIGN.md section 7",
                         "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None},
            "kernel_classes": {k: {"ms": round(v["ms"], 2), "launches": v["launches"]} for k, v in prof_all.items() if v["launches"]}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             import tnqs_oracle as o
+            z_dev = tn.expect_all(bpc, "Z").real
             og, olayer = o.named_grid((5, 5)), layer          # the same gate list (same vertex labels, same colour order) on both sides
             ob = o.update(o.BeliefPropagationCache(o.product_state(dtype, lambda v: "↑", og)))
             t0 = time.perf_counter(); osw = []
@@ -224,10 +289,16 @@ def main():
     ap.add_argument("--config", choices=["c1", "c2", "c4", "c5"], default="c2",
                     help="BASELINE.json configuration: c2 = configs[1] (L x L TFIM, chi 32; the headline metric), c4 = configs[3] (L^3 periodic cubic 3-D Ising "
                          "layer, chi 16; full size L = 10 needs 8 GPUs), c5 = configs[4] (L x L TFIM, chi 64; full size L = 32 needs 8 GPUs), c1 = configs[0] (5 x 5 TFIM, "
-                         "chi 10, ComplexF64, 50 layers from the product state: the reference's own CPU-runnable case, timed on the device AND on the host's CPU oracle)")
+                         "chi 10, ComplexF64, 50 layers from the product state: the reference's own CPU-runnable case, timed on the device; with --full also on the host's CPU oracle)")
     ap.add_argument("--L", type=int, default=0, help="lattice side (default: the BASELINE size of the configuration: 20 / 10 / 32)")
     ap.add_argument("--chi", type=int, default=0, help="bond dimension (default: 32 / 16 / 64)")
     ap.add_argument("--host-init", action="store_true", help="c4 / c5: generate the synthetic state with numpy on the host instead of on the device")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline number does not need: the CPU baseline and, for c2 on one GPU, the same command with the f32 matrix "
+                         "instructions and with the reference's sweep order (child processes); --no-cpu-baseline / --no-ab / --no-ref-order drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (truncation errors, a fixed seeded sample of the site tensors and BP "
+                         "messages) as DIR/<name>.npy, float32 / float64; one GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ref-order", action="store_true", help="skip the third leg: the same command with --bp-order reference (the reference's own default sweep order, what a Julia caller of the shim gets) in a child process")
     ap.add_argument("--no-ab", action="store_true", help="skip the second, untimed-by-the-driver leg: the same command with TNQS_NO_BF16X3=1 (the f32 matrix instructions) in a child process")
@@ -241,6 +312,10 @@ def main():
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 50 if args.config == "c1" else 3
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("bench.py: --dump-outputs needs the whole state on one rank: --gpus 1")
 
     import torch
     import torch.distributed as dist
@@ -327,7 +402,7 @@ def main():
         raise SystemExit(f"bench.py: {workload}: rank {rank} of {world} would hold {mem['site_tensor_GiB_this_rank']} GiB of site tensors (estimated peak "
                          f"{mem['estimated_peak_GiB']} GiB) but the device has {mem['free_GiB']} GiB free -- use more GPUs (--gpus) or a smaller --L")
     if cfg == "c2" or args.host_init:
-        for v, t in random_state_tensors(g, chi, d, 1234, dtype, wanted=(None if world == 1 else bpc.owns)):
+        for v, t in random_state_tensors(g, chi, d, 1234, dtype, wanted=(None if world == 1 else bpc.owns), threads=host_threads()):
             if isinstance(t, tuple):
                 bpc._declare_dims(v, t)
             else:
@@ -361,6 +436,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     prof_all = tn.profile_get(bpc)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bpc, g, errs)
     phase_prof = {k: v for k, v in prof_all.items() if k.startswith("phase_")}       # whole phases on the handle's stream (critical path)
     prof = {k: v for k, v in prof_all.items() if not k.startswith("phase_")}           # kernel classes
     # the library's pool keeps what it has allocated: device memory taken since the start of the run = the high-water mark of the layer
@@ -497,7 +574,7 @@ def main():
         out["evolved"] = {"state": f"{args.evolved} TFIM layers at dt = 0.1 (J = 1, hx = 2.5) from the product state, maxdim {chi}",
                           "max_bond_dim": int(b2.maxvirtualdim()), "ms_per_step": round(1e3 * el2 / max(1, args.steps), 3),
                           "value": round(n2 * args.steps / el2, 2), "bp_sweeps_per_step": sw2, "bp_updates_not_converged": nc2, "max_truncation_error": float(np.max(_e))}
-    if rank == 0 and world == 1 and cfg == "c2" and x3 and not args.no_ab and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and cfg == "c2" and x3 and not args.no_ab and not args.no_cpu_baseline:
         # A/B in the same run on the same box (not part of `value`): the chi = 32 plane kernels on v_mfma_f32_32x32x2_f32 instead of the bf16 matrix cores.  The
         # switches are read once per process, hence a child; it must never take the measured number down with it
         try:
@@ -511,7 +588,7 @@ def main():
                                                  "this_run_kernel_classes_ms": {k: v["ms"] for k, v in classes.items() if k in ("bp_pair", "bp_pairgram", "gate_modeprod")}}
         except Exception as e:
             out["ab_f32_matrix_instructions"] = {"value": None, "error": repr(e)}
-    if rank == 0 and world == 1 and cfg == "c2" and args.bp_order == "library" and not args.no_ref_order and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and cfg == "c2" and args.bp_order == "library" and not args.no_ref_order and not args.no_cpu_baseline:
         # the reference's own default sweep order (beliefpropagationcache.jl:28,41 forest_cover_edge_sequence; what the Julia shim passes by default) in the same run
         # on the same box, not part of `value` (round-5 verdict: the headline times the library's order; at the default tolerance both stop after one sweep per update
         # on different trajectories of the same fixed-point iteration)
@@ -528,7 +605,7 @@ def main():
         except Exception as e:
             out["reference_order"] = {"value": None, "error": repr(e)}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and cfg == "c2":      # (the CPU leg restates the 2-D chi = 32 path on a bounded sample; the 8-GPU shapes have none)
+        if args.full and world == 1 and not args.no_cpu_baseline and cfg == "c2":      # (the CPU leg restates the 2-D chi = 32 path on a bounded sample; the 8-GPU shapes have none)
             try:
                 out["cpu_baseline"] = cpu_baseline(chi, L)
             except Exception as e:      # the baseline must never take the measured number down with it; no compiler / no OpenBLAS on the host: the threaded numpy port

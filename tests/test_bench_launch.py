@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,6 +101,45 @@ def test_eight_ranks_over_gloo(cfg, L, chi):
     per_sweep = sum(1 for _ in _default_levels(g))
     assert abs(tr["allgathers_per_step"] - plan["exchanges_per_layer"]) <= 8 * per_sweep
     assert abs(tr["MB_gathered_per_step"] - plan["bytes_gathered_per_layer"] / 1e6) <= 0.25 * plan["bytes_gathered_per_layer"] / 1e6
+
+
+def test_bad_steps_and_sharded_dump_are_refused_before_any_work():
+    for extra in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "out"]):
+        r = subprocess.run([sys.executable, BENCH, "--warmup", "0"] + extra, env=clean_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and '"n_gpus"' not in r.stdout
+        assert ("--steps must be >= 1" if "--steps" in extra else "--gpus 1") in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    """a plain run (no --full): the line keeps the headline fields, `steps` timed steps, no CPU or A/B legs; --dump-outputs writes what the last
+    step returned as float32 arrays (ComplexF32 state) within 64 MB"""
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--L", "4", "--chi", "8", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                       env=clean_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 2 and len(out["config"]["bp_sweeps_per_step"]) == 2 and out["ms_per_step"] > 0
+    assert not {"cpu_baseline", "ab_f32_matrix_instructions", "reference_order"} & set(out)
+    arrays = {f.name: np.load(f) for f in d.iterdir()}
+    assert set(arrays) == {"truncation_errors.npy", "site_tensor_sample.npy", "message_sample.npy"}
+    assert arrays["truncation_errors.npy"].dtype == np.float64 and arrays["truncation_errors.npy"].size == 16 + 24       # Rx per vertex + Rzz per edge
+    for name in ("site_tensor_sample.npy", "message_sample.npy"):
+        a = arrays[name]
+        assert a.dtype == np.float32 and a.shape[-1] == 2 and np.all(np.isfinite(a)) and np.any(a != 0)
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_cpu_and_ab_legs():
+    r = subprocess.run([sys.executable, BENCH, "--L", "4", "--chi", "8", "--steps", "1", "--warmup", "1", "--full"],
+                       env=clean_env(), capture_output=True, text=True, timeout=1200)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["unit"] == out["unit"]
+    assert out["reference_order"]["ms_per_step"] > 0 and out["ab_f32_matrix_instructions"]["ms_per_step"] > 0
 
 
 def test_memory_estimate_refuses_what_cannot_fit():
