@@ -40,7 +40,37 @@ int tnqs_dbg_pair_gram2(int d, int z, const int* chi, int lx, int ly, const void
 /* timing only: average launch duration (ms, HIP events) of a chi = 32 plane kernel over `nsites` device-resident tensors [2][32]^4;
  * which = 0 pair product on legs (lx, ly), 1 both-messages pair-Gram */
 int tnqs_dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double* ms);
-/* c64 only, d = 2, chi_b = 32: out[s',b',rest] = sum in[s,b,rest] X[(s + 2 b) + 64 (s' + 2 b')]; *norm2 = |out|^2 */
+/* ---- entry points that reach exactly the kernels of ONE engine launch, with several items per launch set up as the engine sets them up.  ComplexF32
+ * only; the items' arrays are passed one after the other.  A shape the named kernel does not take is refused with TNQS_ERR_UNSUPPORTED (no fall-back);
+ * *route_out (may be NULL) says which kernel ran: */
+#define TNQS_DBG_ROUTE_X3 1            /* bf16 x 3 matrix-core kernel (kernels_x3.hip: x3_rowgemm64_kernel, x3_gram64_kernel) */
+#define TNQS_DBG_ROUTE_F32 2           /* f32 matrix-core kernel (mfma_rowgemm_kernel<KB, NB, D>, mfma_gram64_kernel) */
+#define TNQS_DBG_ROUTE_F64 3           /* mfma_gram128_f64_kernel<true, false> */
+#define TNQS_DBG_ROUTE_F64_SHARED 4    /* mfma_gram128_f64_kernel<true, true> (every item has D K = 128) */
+#define TNQS_DBG_ROUTE_HALF_LINES 5    /* mfma_pair16_kernel (planes that contain leg 0) */
+#define TNQS_DBG_ROUTE_WHOLE_LINES 6   /* mfma_pair16w_kernel */
+/* register-direct fiber GEMM (the chi = 32 gate epilogue: D = 2, K = 32; chi = 64 mode products / epilogue; chi = 32 mode products): item i is
+ * out_i[(s',n),(a,b)] = sum_{(s,k)} in_i[(s,k),(a,b)] X_i[(s,k),(s',n)] with in_i element (s,a,k,b) at s + D*(a + PA[i]*(k + K*b)), X_i (D K) x (D No[i]),
+ * out_i element (s',a,n,b) at s' + D*(a + PA[i]*(n + No[i]*b)); D in {1, 2}, K in {32, 64}, 1 <= No[i] <= K; PA[i] a multiple of 32, or a divisor of 32
+ * with PB[i] a multiple of 32 / PA[i].  norm2_out[i] = the sum of item i's norm partials (|out_i|^2); tpw <= 0: the engine's tiles per workgroup */
+int tnqs_dbg_rowgemm(int D, int K, int nitems, const int* PA, const int* PB, const int* No, const void* in, const void* X, void* out, double* norm2_out,
+                     int tpw, int* route_out);
+/* matrix-core Grams out_i[p + KK*q] = sum_{(a,b)} X_i[p,(a,b)] conj(Y_i[q,(a,b)]), p, q = (s,k), KK = D K, shape = (D, PA, K, PB) per item:
+ * 32 < max KK <= 64: f32 accumulation, out complex64 (the BP message Gram); 64 < max KK <= 128: f64 accumulation, out complex128, Y must be NULL
+ * (the gate-path Gram).  Y == NULL: Y_i = X_i.  nchunks <= 0: the engine's chunking, else at most nchunks chunks per item */
+int tnqs_dbg_gram_mfma(int nitems, const int* shape, const void* X, const void* Y, void* out, int nchunks, int* route_out);
+/* chi = 16 plane kernels on site tensors [d][chi_0]..[chi_{z[i]-1}] (chi: the items' dimensions one after the other), planes (lx[i], ly[i]) of two
+ * 16-dimensional legs; M: (Mx, My) per item, 2 x 256 complex64, M[i + 16 j].  pair16: out_i = in_i x_lx Mx x_ly My (items of one launch must be of one
+ * kind: route).  spw <= 0: the engine's slices per workgroup, else a multiple of 4 */
+int tnqs_dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const void* in, const void* M, void* out, int spw, int* route_out);
+/* out_y[i] (16 x 16, b + 16 b') = sum (X_i x_lx Mx)[.. b on ly ..] conj(Y_i[.. b' on ly ..]); both[i] != 0: also out_x[i] = sum (X_i x_ly My)[.. d on lx ..]
+ * conj(Y_i[.. d' on lx ..]); both[i] == 0: the single-message form (My = NULL, no partial_x; out_x[i] untouched) */
+int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const int* both, const void* X, const void* Y, const void* M,
+                           void* out_y, void* out_x, int spw);
+/* the tall route of the ComplexF32 theta SVD (Cholesky-QR preprocessing, Jacobi on R, A J, polishing sweeps where the pivot collapsed) on nitems matrices
+ * A_i (m[i] x n[i], 2 <= n <= 128, n <= m <= 256): A_i <- U Sigma (columns); chol_fail[i]: a Cholesky pivot was refused; polished[i]: the polishing sweeps
+ * ran on the item; sweeps[i]: sweeps of the Jacobi on R (each output array may be NULL) */
+int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps);
 /* the BP sweep order bp_update uses when no edge_sequence is given, as (src[i] -> dst[i]) vertex indices; *n_out = its length (2 ne) */
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out);
 /* the same order from the graph alone (nv vertices, ne undirected edges esrc[e] - edst[e]) together with the dependency level bp_update runs every message in

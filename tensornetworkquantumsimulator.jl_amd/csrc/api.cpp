@@ -196,7 +196,13 @@ namespace tnqs { void dbg_default_sequence(const State* s, std::vector<int>& src
                  void dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double* ms);
                  void dbg_pair_gram(int d, int z, const int* chi, int lx, int ly, const void* X, const void* Y, const void* M, void* out);
                  void dbg_fiber_gemm(int dtype, int D, int PA, int K, int PB, int Do, int No, const void* in, const void* X, void* out, double* norm2, int use_mfma);
-                 void dbg_gram(int dtype, int D, int PA, int K, int PB, const void* X, const void* Y, void* out, int acc64, int use_mfma); }
+                 void dbg_gram(int dtype, int D, int PA, int K, int PB, const void* X, const void* Y, void* out, int acc64, int use_mfma);
+                 void dbg_rowgemm(int D, int K, int nitems, const int* PA, const int* PB, const int* No, const void* in, const void* X, void* out, double* norm2, int tpw, int* route);
+                 void dbg_gram_mfma(int nitems, const int* shape, const void* X, const void* Y, void* out, int nchunks, int* route);
+                 void dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const void* in, const void* M, void* out, int spw, int* route);
+                 void dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const int* both, const void* X, const void* Y, const void* M,
+                                        void* out_y, void* out_x, int spw);
+                 void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
     return guard([&] { std::vector<int> a, b; dbg_default_sequence(S(h), a, b); *n_out = (int)a.size();
@@ -225,5 +231,21 @@ int tnqs_dbg_gram_fused(int PA, int K, int PB, const void* X, const void* Y, con
 int tnqs_dbg_gauge_gram(int z, const int* chi, int bleg, const void* X, const void* M, void* out) { return guard([&] { dbg_gauge_gram(z, chi, bleg, X, M, out); }); }
 int tnqs_dbg_gram(int dtype, int D, int PA, int K, int PB, const void* X, const void* Y, void* out, int acc64, int use_mfma) {
     return guard([&] { dbg_gram(dtype, D, PA, K, PB, X, Y, out, acc64, use_mfma); });
+}
+int tnqs_dbg_rowgemm(int D, int K, int nitems, const int* PA, const int* PB, const int* No, const void* in, const void* X, void* out, double* norm2_out, int tpw, int* route_out) {
+    return guard([&] { dbg_rowgemm(D, K, nitems, PA, PB, No, in, X, out, norm2_out, tpw, route_out); });
+}
+int tnqs_dbg_gram_mfma(int nitems, const int* shape, const void* X, const void* Y, void* out, int nchunks, int* route_out) {
+    return guard([&] { dbg_gram_mfma(nitems, shape, X, Y, out, nchunks, route_out); });
+}
+int tnqs_dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const void* in, const void* M, void* out, int spw, int* route_out) {
+    return guard([&] { dbg_pair16(d, nitems, z, chi, lx, ly, in, M, out, spw, route_out); });
+}
+int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const int* both, const void* X, const void* Y, const void* M,
+                           void* out_y, void* out_x, int spw) {
+    return guard([&] { dbg_pair_gram2x16(d, nitems, z, chi, lx, ly, both, X, Y, M, out_y, out_x, spw); });
+}
+int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps) {
+    return guard([&] { dbg_svd_tall(nitems, m, n, A, chol_fail, polished, sweeps); });
 }
 }

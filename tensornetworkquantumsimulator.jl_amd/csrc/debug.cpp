@@ -4,9 +4,11 @@
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
+#include <memory>
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "launch_util.hpp"
+#include "../../include/tnqs_debug.h"
 
 namespace tnqs {
 #define HIPCHK(x) hipchk((x), #x)
@@ -461,5 +463,212 @@ void dbg_gauge_gram(int z, const int* chi, int bleg, const void* X, const void* 
     launch_reduce<double, double>(nullptr, (const ReduceItem*)dR.p, 1, KK * KK);
     HIPCHK(hipDeviceSynchronize());
     dO.down(out, (size_t)KK * KK * 16);
+}
+
+// ---- entry points that reach exactly the kernels of one engine launch: several items per launch, set up as the engine sets them up
+// (engine_batch.cpp run_chains / run_grams / svd_batch, engine_gates.cpp plan_rowgemm, engine_bp.cpp), a shape the named kernel does not
+// take is refused (TNQS_ERR_UNSUPPORTED) and *route says which kernel ran (TNQS_DBG_ROUTE_*, include/tnqs_debug.h) ----
+namespace {
+template <class F> void cat_offsets(int n, std::vector<size_t>& off, F&& size_of) { off.assign(n + 1, 0); for (int i = 0; i < n; ++i) off[i + 1] = off[i] + size_of(i); }
+}
+void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail, int* d_polish_sweeps);
+
+// register-direct fiber GEMM (launch_mfma_rowgemm): items i with (PA[i], PB[i], No[i]), one D and K for the launch; in / X / out are the items'
+// arrays one after the other; norm2[i] = the sum of item i's norm partials; tpw <= 0: the engine's rule (D = 2: gate epilogue, D = 1: BP mode product)
+void dbg_rowgemm(int D, int K, int nitems, const int* PA, const int* PB, const int* No, const void* in, const void* X, void* out, double* norm2, int tpw, int* route) {
+    need_gpu();
+    if (nitems < 1 || !PA || !PB || !No) throw Err(TNQS_ERR_INVALID, "dbg_rowgemm: bad arguments");
+    std::vector<FiberItem> items(nitems);
+    double tiles = 0;
+    for (int i = 0; i < nitems; ++i) {
+        FiberItem& it = items[i]; it.D = D; it.PA = PA[i]; it.K = K; it.PB = PB[i]; it.Do = D; it.No = No[i];
+        if (PA[i] < 1 || PB[i] < 1 || !rowgemm_covers(it)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_rowgemm: item not covered by the register-direct kernels");
+        rowgemm_tiles(it); it.want_norm = 1; tiles += (double)it.nta * it.ntb;
+    }
+    std::vector<size_t> oi, ox, oo;
+    cat_offsets(nitems, oi, [&](int i) { return (size_t)D * PA[i] * K * PB[i]; });
+    cat_offsets(nitems, ox, [&](int i) { return (size_t)D * K * D * No[i]; });
+    cat_offsets(nitems, oo, [&](int i) { return (size_t)D * PA[i] * No[i] * PB[i]; });
+    if (tpw <= 0) { tpw = (int)std::max(4.0, std::min(D == 2 ? 32.0 : 64.0, tiles / 2048.0)); tpw &= ~3; }
+    DBuf dIn(oi[nitems] * 8), dX(ox[nitems] * 8), dOut(oo[nitems] * 8), dI(sizeof(FiberItem) * nitems);
+    dIn.up(in, oi[nitems] * 8); dX.up(X, ox[nitems] * 8);
+    HIPCHK(hipMemset(dOut.p, 0xff, oo[nitems] * 8));
+    int wgs = 0;
+    for (int i = 0; i < nitems; ++i) {
+        FiberItem& it = items[i];
+        it.in = (char*)dIn.p + oi[i] * 8; it.X = (char*)dX.p + ox[i] * 8; it.out = (char*)dOut.p + oo[i] * 8;
+        it.tpw = tpw; it.tile_begin = wgs; wgs += (it.nta * it.ntb + tpw - 1) / tpw;
+    }
+    DBuf dN((size_t)wgs * 8);
+    dI.up(items.data(), sizeof(FiberItem) * nitems);
+    launch_mfma_rowgemm(nullptr, (const FiberItem*)dI.p, nitems, wgs, D, K, (double*)dN.p);
+    HIPCHK(hipDeviceSynchronize());
+    dOut.down(out, oo[nitems] * 8);
+    std::vector<double> np(wgs); dN.down(np.data(), (size_t)wgs * 8);
+    for (int i = 0; i < nitems; ++i) {
+        const int end = i + 1 < nitems ? items[i + 1].tile_begin : wgs;
+        double t = 0; for (int w = items[i].tile_begin; w < end; ++w) t += np[w];
+        if (norm2) norm2[i] = t;
+    }
+    if (route) *route = (D * K == 64 && mfma_use_x3()) ? TNQS_DBG_ROUTE_X3 : TNQS_DBG_ROUTE_F32;
+}
+
+// matrix-core Grams of 32 < KK <= 64 (launch_mfma_gram64, f32 accumulation, complex64 out; the BP message Gram) and 64 < KK <= 128
+// (launch_mfma_gram128_f64, X == Y, complex128 out; the gate-path Gram at chi = 64).  shape: (D, PA, K, PB) per item; Y == NULL: X == Y;
+// nchunks <= 0: the engine's chunking (run_grams), else at most that many chunks per item; partials summed with launch_reduce
+void dbg_gram_mfma(int nitems, const int* shape, const void* X, const void* Y, void* out, int nchunks, int* route) {
+    need_gpu();
+    if (nitems < 1 || !shape) throw Err(TNQS_ERR_INVALID, "dbg_gram_mfma: bad arguments");
+    int KKmax = 0; bool all128 = true;
+    for (int i = 0; i < nitems; ++i) {
+        const int* q = shape + 4 * i;
+        if (q[0] < 1 || q[1] < 1 || q[2] < 1 || q[3] < 1) throw Err(TNQS_ERR_INVALID, "dbg_gram_mfma: bad shape");
+        KKmax = std::max(KKmax, q[0] * q[2]); all128 = all128 && q[0] * q[2] == 128;
+    }
+    const bool f64 = KKmax > 64;
+    if (KKmax <= 32 || KKmax > 128) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_gram_mfma: 32 < D K <= 128");
+    if (f64 && Y) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_gram_mfma: the 128 x 128 f64 Gram takes X == Y only");
+    const size_t asz = f64 ? 16 : 8;
+    std::vector<size_t> oi, oo;
+    cat_offsets(nitems, oi, [&](int i) { const int* q = shape + 4 * i; return (size_t)q[0] * q[1] * q[2] * q[3]; });
+    cat_offsets(nitems, oo, [&](int i) { const int* q = shape + 4 * i; return (size_t)q[0] * q[2] * q[0] * q[2]; });
+    DBuf dX(oi[nitems] * 8), dY(Y ? oi[nitems] * 8 : 1), dO(oo[nitems] * asz), dI(sizeof(GramItem) * nitems), dR(sizeof(ReduceItem) * nitems);
+    dX.up(X, oi[nitems] * 8); if (Y) dY.up(Y, oi[nitems] * 8);
+    const int per_item = std::max(1, (f64 ? 1024 : 2048) / nitems);      // run_grams: target workgroups per launch
+    std::vector<GramItem> items(nitems); std::vector<size_t> op(nitems + 1, 0); int chunks = 0;
+    for (int i = 0; i < nitems; ++i) {
+        const int* q = shape + 4 * i; GramItem& it = items[i];
+        it.X = (char*)dX.p + oi[i] * 8; it.Y = Y ? (const void*)((char*)dY.p + oi[i] * 8) : it.X;
+        it.D = q[0]; it.PA = q[1]; it.K = q[2]; it.PB = q[3];
+        tile_params(it.PA, it.PB, 64, it.TA, it.TB, it.nta, it.ntb);
+        const int ntiles = it.nta * it.ntb, nch = std::min(nchunks > 0 ? nchunks : per_item, ntiles);
+        it.tiles_per_chunk = (ntiles + nch - 1) / nch; it.nchunks = (ntiles + it.tiles_per_chunk - 1) / it.tiles_per_chunk;
+        it.chunk_begin = chunks; chunks += it.nchunks;
+        op[i + 1] = op[i] + (size_t)it.nchunks * (oo[i + 1] - oo[i]);         // one partial per chunk
+    }
+    DBuf dP(op[nitems] * asz);
+    std::vector<ReduceItem> ri(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        items[i].partial = (char*)dP.p + op[i] * asz;
+        ri[i] = ReduceItem{items[i].partial, (char*)dO.p + oo[i] * asz, (int)(oo[i + 1] - oo[i]), items[i].nchunks, 0, (int)oo[i]};
+    }
+    dI.up(items.data(), sizeof(GramItem) * nitems); dR.up(ri.data(), sizeof(ReduceItem) * nitems);
+    if (f64) {
+        launch_mfma_gram128_f64(nullptr, (const GramItem*)dI.p, nitems, chunks, KKmax, all128);
+        launch_reduce<double, double>(nullptr, (const ReduceItem*)dR.p, nitems, (int)oo[nitems]);
+    } else {
+        launch_mfma_gram64(nullptr, (const GramItem*)dI.p, nitems, chunks, KKmax);
+        launch_reduce<float, float>(nullptr, (const ReduceItem*)dR.p, nitems, (int)oo[nitems]);
+    }
+    HIPCHK(hipDeviceSynchronize());
+    dO.down(out, oo[nitems] * asz);
+    if (route) *route = f64 ? (all128 ? TNQS_DBG_ROUTE_F64_SHARED : TNQS_DBG_ROUTE_F64) : (mfma_use_x3() ? TNQS_DBG_ROUTE_X3 : TNQS_DBG_ROUTE_F32);
+}
+
+// chi = 16 planes: item i is a site tensor [d][chi_0]..[chi_{z[i]-1}] (chi: the items' dimensions one after the other) with the plane (lx[i], ly[i])
+static void plane_items(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, std::vector<PlaneGeom>& g, std::vector<size_t>& off) {
+    if (nitems < 1 || !z || !chi || !lx || !ly || d < 1) throw Err(TNQS_ERR_INVALID, "dbg plane kernels: bad arguments");
+    g.resize(nitems);
+    int c = 0;
+    cat_offsets(nitems, off, [&](int i) {
+        if (z[i] < 2 || z[i] > 8) throw Err(TNQS_ERR_INVALID, "dbg plane kernels: 2 <= z <= 8");
+        size_t n = d; for (int k = 0; k < z[i]; ++k) n *= chi[c + k];
+        if (!plane_geometry(d, z[i], chi + c, lx[i], ly[i], 16, g[i]) || (size_t)g[i].nslices() * 16 * 256 != n)
+            throw Err(TNQS_ERR_UNSUPPORTED, "dbg plane kernels: plane not covered by the chi = 16 kernels");
+        c += z[i];
+        return n;
+    });
+}
+// pair of mode products on two 16-dimensional legs (launch_mfma_pair16): out = in x_lx Mx x_ly My per item, M = (Mx, My) per item (2 x 256);
+// the items of one launch are of one kind (pair16_whole_lines); spw <= 0: the engine's rule (run_chains)
+void dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const void* in, const void* M, void* out, int spw, int* route) {
+    need_gpu();
+    std::vector<PlaneGeom> g; std::vector<size_t> off;
+    plane_items(d, nitems, z, chi, lx, ly, g, off);
+    const bool wl = pair16_whole_lines(g[0]);
+    double slices = 0;
+    for (int i = 0; i < nitems; ++i) { if (pair16_whole_lines(g[i]) != wl) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_pair16: one launch holds items of one kind"); slices += g[i].nslices(); }
+    if (spw <= 0) { spw = 4; while (spw < 64 && slices / (2 * spw) >= 2048.0) spw *= 2; }
+    if (spw % 4) throw Err(TNQS_ERR_INVALID, "dbg_pair16: spw must be a multiple of 4");
+    const size_t n = off[nitems];
+    DBuf dIn(n * 8), dOut(n * 8), dM((size_t)nitems * 512 * 8), dI(sizeof(Pair16Item) * nitems);
+    dIn.up(in, n * 8); dM.up(M, (size_t)nitems * 512 * 8);
+    HIPCHK(hipMemset(dOut.p, 0xff, n * 8));
+    std::vector<Pair16Item> items(nitems); int wgs = 0;
+    for (int i = 0; i < nitems; ++i) {
+        Pair16Item& it = items[i]; it.g = g[i]; it.in = (char*)dIn.p + off[i] * 8; it.out = (char*)dOut.p + off[i] * 8;
+        it.Mx = (char*)dM.p + (size_t)i * 512 * 8; it.My = (char*)it.Mx + 256 * 8;
+        it.spw = spw; it.wg_begin = wgs; wgs += (g[i].nslices() + spw - 1) / spw;
+    }
+    dI.up(items.data(), sizeof(Pair16Item) * nitems);
+    launch_mfma_pair16(nullptr, (const Pair16Item*)dI.p, nitems, wgs, wl);
+    HIPCHK(hipDeviceSynchronize());
+    dOut.down(out, n * 8);
+    if (route) *route = wl ? TNQS_DBG_ROUTE_WHOLE_LINES : TNQS_DBG_ROUTE_HALF_LINES;
+}
+// both messages of a 16 x 16 plane from one pass (launch_mfma_pair_gram2x16): per item out_y[i] (256 complex64) = sum (X x_lx Mx)[.. b on ly ..]
+// conj(Y[.. b' on ly ..]), and when both[i] != 0 out_x[i] = sum (X x_ly My)[.. d on lx ..] conj(Y[.. d' on lx ..]); both[i] == 0 is the single-message
+// form of the BP update (My = partial_x = null; out_x[i] is not written).  Partials of a message summed with launch_reduce; spw <= 0: the engine's rule
+void dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const int* both, const void* X, const void* Y, const void* M,
+                       void* out_y, void* out_x, int spw) {
+    need_gpu();
+    std::vector<PlaneGeom> g; std::vector<size_t> off;
+    plane_items(d, nitems, z, chi, lx, ly, g, off);
+    if (!both) throw Err(TNQS_ERR_INVALID, "dbg_pair_gram2x16: bad arguments");
+    double slices = 0; for (int i = 0; i < nitems; ++i) slices += g[i].nslices();
+    const int at = pair_gram2x16_slices_at_a_time();
+    if (spw <= 0) { spw = at; while (spw < 128 && slices / (2 * spw) >= 2048.0) spw *= 2; }
+    if (spw % at) throw Err(TNQS_ERR_INVALID, "dbg_pair_gram2x16: spw must be a multiple of the slices a workgroup walks at a time");
+    const size_t n = off[nitems];
+    std::vector<PairGram2x16Item> items(nitems); int wgs = 0;
+    for (int i = 0; i < nitems; ++i) { items[i].g = g[i]; items[i].spw = spw; items[i].wg_begin = wgs; wgs += (g[i].nslices() + spw - 1) / spw; }
+    DBuf dX(n * 8), dY(n * 8), dM((size_t)nitems * 512 * 8), dI(sizeof(PairGram2x16Item) * nitems), dP((size_t)2 * wgs * 256 * 8), dO((size_t)2 * nitems * 256 * 8),
+         dR(sizeof(ReduceItem) * 2 * nitems);
+    dX.up(X, n * 8); dY.up(Y, n * 8); dM.up(M, (size_t)nitems * 512 * 8);
+    HIPCHK(hipMemset(dO.p, 0, (size_t)2 * nitems * 256 * 8));
+    std::vector<ReduceItem> ri;
+    for (int i = 0; i < nitems; ++i) {
+        PairGram2x16Item& it = items[i];
+        const int nwg = (i + 1 < nitems ? items[i + 1].wg_begin : wgs) - it.wg_begin;
+        it.X = (char*)dX.p + off[i] * 8; it.Y = (char*)dY.p + off[i] * 8;
+        it.Mx = (char*)dM.p + (size_t)i * 512 * 8; it.My = both[i] ? (const void*)((char*)it.Mx + 256 * 8) : nullptr;
+        it.partial_y = (char*)dP.p + (size_t)it.wg_begin * 256 * 8;
+        it.partial_x = both[i] ? (void*)((char*)dP.p + ((size_t)wgs + it.wg_begin) * 256 * 8) : nullptr;
+        ri.push_back(ReduceItem{it.partial_y, (char*)dO.p + (size_t)i * 256 * 8, 256, nwg, 0, (int)ri.size() * 256});
+        if (both[i]) ri.push_back(ReduceItem{it.partial_x, (char*)dO.p + ((size_t)nitems + i) * 256 * 8, 256, nwg, 0, (int)ri.size() * 256});
+    }
+    dI.up(items.data(), sizeof(PairGram2x16Item) * nitems); dR.up(ri.data(), sizeof(ReduceItem) * ri.size());
+    launch_mfma_pair_gram2x16(nullptr, (const PairGram2x16Item*)dI.p, nitems, wgs);
+    launch_reduce<float, float>(nullptr, (const ReduceItem*)dR.p, (int)ri.size(), (int)ri.size() * 256);
+    HIPCHK(hipDeviceSynchronize());
+    dO.down(out_y, (size_t)nitems * 256 * 8);
+    if (out_x) for (int i = 0; i < nitems; ++i) if (both[i]) HIPCHK(hipMemcpy((char*)out_x + (size_t)i * 256 * 8, (char*)dO.p + ((size_t)nitems + i) * 256 * 8, 256 * 8, hipMemcpyDeviceToHost));
+}
+
+// svd_batch's tall route (svd_tall: Cholesky-QR, Jacobi on R, A J, polish where the pivot collapsed) on nitems ComplexF32 matrices A_i (m[i] x n[i],
+// one after the other): A_i <- U Sigma; chol_fail[i]: the packed Cholesky refused a pivot; polished[i]: the polishing sweeps ran on the item;
+// sweeps[i]: the sweeps of the Jacobi on R
+void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps) {
+    need_gpu();
+    if (nitems < 1 || !m || !n || !A) throw Err(TNQS_ERR_INVALID, "dbg_svd_tall: bad arguments");
+    for (int i = 0; i < nitems; ++i)
+        if (n[i] < 2 || n[i] > 128 || m[i] < n[i] || m[i] > 256) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_svd_tall: 2 <= n <= 128, n <= m <= 256");
+    std::vector<size_t> off; cat_offsets(nitems, off, [&](int i) { return (size_t)m[i] * n[i]; });
+    int dev = 0; HIPCHK(hipGetDevice(&dev));
+    std::unique_ptr<State> s(state_create(1, 0, nullptr, nullptr, nullptr, TNQS_C64, dev));
+    {
+        DBuf dA(off[nitems] * 8), dF(sizeof(int) * nitems), dS(sizeof(int) * nitems), dW(sizeof(int) * nitems);
+        dA.up(A, off[nitems] * 8);
+        HIPCHK(hipMemset(dS.p, 0, sizeof(int) * nitems)); HIPCHK(hipMemset(dW.p, 0xff, sizeof(int) * nitems));      // polish sweeps: -1 = not run
+        std::vector<JacobiItem> tall(nitems);
+        for (int i = 0; i < nitems; ++i) { JacobiItem j{}; j.A = (char*)dA.p + off[i] * 8; j.m = m[i]; j.n = n[i]; j.sweeps_out = (int*)dS.p + i; tall[i] = j; }
+        svd_tall(s.get(), tall, (int*)dF.p, (int*)dW.p);
+        HIPCHK(hipStreamSynchronize(s->stream));
+        dA.down(A, off[nitems] * 8);
+        std::vector<int> f(nitems), w(nitems);
+        dF.down(f.data(), sizeof(int) * nitems); dW.down(w.data(), sizeof(int) * nitems);
+        if (sweeps) dS.down(sweeps, sizeof(int) * nitems);
+        for (int i = 0; i < nitems; ++i) { if (chol_fail) chol_fail[i] = f[i]; if (polished) polished[i] = w[i] >= 0; }
+    }
 }
 }  // namespace tnqs

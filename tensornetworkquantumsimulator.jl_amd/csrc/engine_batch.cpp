@@ -172,6 +172,57 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
     (void)done;
 }
 
+// the tall route of svd_batch (ComplexF32, no V): Cholesky-QR preprocessing, Jacobi on R, A <- A J, polishing sweeps where the pivot collapsed.
+// d_fail (nt ints, may be null): the per-item Cholesky failure flags; d_polish_sweeps (nt ints, may be null): the sweeps of the polishing pass
+// (written only by the items it ran on)
+void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail_out, int* d_polish_sweeps) {
+    const size_t esz = sizeof(float) * 2;
+    const size_t nt = tall.size();
+    size_t off = 0; std::vector<size_t> oG(nt), oL(nt), oW(nt), oR0(nt), oRr(nt), oJ(nt), oT(nt);
+    for (size_t i = 0; i < nt; ++i) {
+        const size_t nn = (size_t)tall[i].n * tall[i].n, mn = (size_t)tall[i].m * tall[i].n;
+        oG[i] = off; off += round256(nn * 16); oL[i] = off; off += round256(nn * 16); oW[i] = off; off += round256(nn * 16);
+        oR0[i] = off; off += round256(nn * 8); oRr[i] = off; off += round256(nn * 8); oJ[i] = off; off += round256(nn * 16); oT[i] = off; off += round256(mn * 8);
+    }
+    Buf arena = dalloc(s, off); s->keepalive.push_back(arena);
+    Buf fail_buf; if (!d_fail_out) { fail_buf = dalloc(s, nt * sizeof(int)); s->keepalive.push_back(fail_buf); }
+    int* const d_fail = d_fail_out ? d_fail_out : reinterpret_cast<int*>(fail_buf->p);
+    HIPCHK(hipMemsetAsync(d_fail, 0, nt * sizeof(int), s->stream));
+    char* ap = reinterpret_cast<char*>(arena->p);
+    std::vector<TallSvdItem> ti, wi; std::vector<CholItem> ci; std::vector<JacobiItem> rj; std::vector<SmallGemmItem> gi; std::vector<CopyItem> cp;
+    int nmax = 1, mmax = 1;
+    for (size_t i = 0; i < nt; ++i) {
+        const int m = tall[i].m, n = tall[i].n; nmax = std::max(nmax, n); mmax = std::max(mmax, m);
+        ti.push_back(TallSvdItem{tall[i].A, ap + oG[i], ap + oL[i], ap + oR0[i], ap + oRr[i], m, n});
+        // delta = 1e-14 of the largest diagonal entry: singular directions below 1e-7 sigma_max are f32 noise of the data anyway, and R keeps
+        // a condition number <= 1e7 whatever the rank of A (no failure branch: a rank-deficient theta is the normal case early in an evolution)
+        ci.push_back(CholItem{ap + oG[i], ap + oL[i], ap + oW[i], n, d_fail + i, 0.0, 1e-14});      // Winv = (L^-1)^dagger = R^-1
+        rj.push_back(JacobiItem{ap + oRr[i], nullptr, n, n, tall[i].sweeps_out});
+        wi.push_back(TallSvdItem{nullptr, d_fail + i, ap + oW[i], ap + oJ[i], ap + oRr[i], n, n});   // J = R^-1 (R J), f64; G slot: the item's Cholesky failure flag (J := I then)
+        gi.push_back(SmallGemmItem{tall[i].A, ap + oJ[i], ap + oT[i], m, n, n});
+        cp.push_back(CopyItem{ap + oT[i], tall[i].A, (size_t)m * n * 8 / 16});
+    }
+    const TallSvdItem* dt = upload(s, ti); const CholItem* dc = upload(s, ci); const JacobiItem* dj = upload(s, rj);
+    const TallSvdItem* dw = upload(s, wi); const SmallGemmItem* dg = upload(s, gi); const CopyItem* dcp = upload(s, cp);
+    launch_tall_gram(s->stream, dt, (int)nt, nmax);
+    launch_chol_packed(s->stream, dc, (int)nt, nmax);
+    launch_tall_rt(s->stream, dt, (int)nt);
+    size_t lds = 0; for (auto& j : rj) lds = std::max(lds, jacobi_lds_bytes(j.m, j.n, false, esz));
+    launch_jacobi<float>(s->stream, dj, (int)nt, 60, lds, nmax);
+    launch_tall_w(s->stream, dw, (int)nt, nmax);
+    launch_tall_mj(s->stream, dg, (int)nt);                        // A J in f64 (J is complex128): column-relative accuracy, no polishing needed
+    launch_copy_items(s->stream, dcp, (int)nt);
+    // Polishing sweeps on A J itself are only needed where the preprocessing gave nothing to build on: an item whose Cholesky pivot
+    // collapsed in spite of the shift (J := I above) is factorised from scratch here; every other item is skipped on the device
+    // (JacobiItem::only_if).  Round 2 polished every item (2.6 ms per chi = 64 colour batch): its A J was an f32 product with an f32 J,
+    // which leaves eps32 sigma_max of residue in every column -- the f64 product does not.
+    std::vector<JacobiItem> pol;
+    for (size_t i = 0; i < nt; ++i) { JacobiItem j{tall[i].A, nullptr, tall[i].m, tall[i].n, d_polish_sweeps ? d_polish_sweeps + i : nullptr}; j.only_if = d_fail + i; pol.push_back(j); }
+    const JacobiItem* dp = upload(s, pol);
+    launch_jacobi<float>(s->stream, dp, (int)nt, 60, 0, mmax);
+    s->stats.n_tall_svd += (int)nt;
+}
+
 // One-sided Jacobi SVD of a batch of matrices (A <- U Sigma in place; V accumulated only when the items carry one).  Three routes:
 //   * the matrix fits the LDS (jacobi_lds_kernel);
 //   * ComplexF32, no V wanted, too tall for the LDS but its n x n triangle fits (256 x 128 at chi = 64): Cholesky-QR preprocessing --
@@ -210,51 +261,7 @@ template <class T> void svd_batch(State* s, const std::vector<JacobiItem>& all, 
         const JacobiItem* d = upload(s, rest);
         launch_jacobi<T>(s->stream, d, (int)rest.size(), 60, 0, mmax_of(rest));
     }
-    if (!tall.empty()) {
-        const size_t nt = tall.size();
-        size_t off = 0; std::vector<size_t> oG(nt), oL(nt), oW(nt), oR0(nt), oRr(nt), oJ(nt), oT(nt);
-        for (size_t i = 0; i < nt; ++i) {
-            const size_t nn = (size_t)tall[i].n * tall[i].n, mn = (size_t)tall[i].m * tall[i].n;
-            oG[i] = off; off += round256(nn * 16); oL[i] = off; off += round256(nn * 16); oW[i] = off; off += round256(nn * 16);
-            oR0[i] = off; off += round256(nn * 8); oRr[i] = off; off += round256(nn * 8); oJ[i] = off; off += round256(nn * 16); oT[i] = off; off += round256(mn * 8);
-        }
-        Buf arena = dalloc(s, off); s->keepalive.push_back(arena);
-        Buf d_fail = dalloc(s, nt * sizeof(int)); s->keepalive.push_back(d_fail);
-        HIPCHK(hipMemsetAsync(d_fail->p, 0, nt * sizeof(int), s->stream));
-        char* ap = reinterpret_cast<char*>(arena->p);
-        std::vector<TallSvdItem> ti, wi; std::vector<CholItem> ci; std::vector<JacobiItem> rj; std::vector<SmallGemmItem> gi; std::vector<CopyItem> cp;
-        int nmax = 1, mmax = 1;
-        for (size_t i = 0; i < nt; ++i) {
-            const int m = tall[i].m, n = tall[i].n; nmax = std::max(nmax, n); mmax = std::max(mmax, m);
-            ti.push_back(TallSvdItem{tall[i].A, ap + oG[i], ap + oL[i], ap + oR0[i], ap + oRr[i], m, n});
-            // delta = 1e-14 of the largest diagonal entry: singular directions below 1e-7 sigma_max are f32 noise of the data anyway, and R keeps
-            // a condition number <= 1e7 whatever the rank of A (no failure branch: a rank-deficient theta is the normal case early in an evolution)
-            ci.push_back(CholItem{ap + oG[i], ap + oL[i], ap + oW[i], n, reinterpret_cast<int*>(d_fail->p) + i, 0.0, 1e-14});      // Winv = (L^-1)^dagger = R^-1
-            rj.push_back(JacobiItem{ap + oRr[i], nullptr, n, n, tall[i].sweeps_out});
-            wi.push_back(TallSvdItem{nullptr, reinterpret_cast<int*>(d_fail->p) + i, ap + oW[i], ap + oJ[i], ap + oRr[i], n, n});   // J = R^-1 (R J), f64; G slot: the item's Cholesky failure flag (J := I then)
-            gi.push_back(SmallGemmItem{tall[i].A, ap + oJ[i], ap + oT[i], m, n, n});
-            cp.push_back(CopyItem{ap + oT[i], tall[i].A, (size_t)m * n * 8 / 16});
-        }
-        const TallSvdItem* dt = upload(s, ti); const CholItem* dc = upload(s, ci); const JacobiItem* dj = upload(s, rj);
-        const TallSvdItem* dw = upload(s, wi); const SmallGemmItem* dg = upload(s, gi); const CopyItem* dcp = upload(s, cp);
-        launch_tall_gram(s->stream, dt, (int)nt, nmax);
-        launch_chol_packed(s->stream, dc, (int)nt, nmax);
-        launch_tall_rt(s->stream, dt, (int)nt);
-        size_t lds = 0; for (auto& j : rj) lds = std::max(lds, jacobi_lds_bytes(j.m, j.n, false, esz));
-        launch_jacobi<T>(s->stream, dj, (int)nt, 60, lds, nmax);
-        launch_tall_w(s->stream, dw, (int)nt, nmax);
-        launch_tall_mj(s->stream, dg, (int)nt);                        // A J in f64 (J is complex128): column-relative accuracy, no polishing needed
-        launch_copy_items(s->stream, dcp, (int)nt);
-        // Polishing sweeps on A J itself are only needed where the preprocessing gave nothing to build on: an item whose Cholesky pivot
-        // collapsed in spite of the shift (J := I above) is factorised from scratch here; every other item is skipped on the device
-        // (JacobiItem::only_if).  Round 2 polished every item (2.6 ms per chi = 64 colour batch): its A J was an f32 product with an f32 J,
-        // which leaves eps32 sigma_max of residue in every column -- the f64 product does not.
-        std::vector<JacobiItem> pol;
-        for (size_t i = 0; i < nt; ++i) { JacobiItem j{tall[i].A, nullptr, tall[i].m, tall[i].n, nullptr}; j.only_if = reinterpret_cast<const int*>(d_fail->p) + i; pol.push_back(j); }
-        const JacobiItem* dp = upload(s, pol);
-        launch_jacobi<T>(s->stream, dp, (int)nt, 60, 0, mmax);
-        s->stats.n_tall_svd += (int)nt;
-    }
+    if (!tall.empty()) svd_tall(s, tall);
 }
 
 template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& jobs, int cls) {

@@ -262,6 +262,7 @@ struct GramJob {      // out[i,j] = sum X[i,.] conj(Y[j,.]) over everything but 
 template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls, int cls_pair = -1);
 template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& jobs, int cls);
 template <class T> void svd_batch(State* s, const std::vector<JacobiItem>& all, bool with_v);
+void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail = nullptr, int* d_polish_sweeps = nullptr);     // svd_batch's Cholesky-QR route (ComplexF32, no V)
 // optimistic: (apply_gates, a tolerance given) return after ENQUEUING the first sweep with its verdict left as a Check (engine.hpp); iters_before: sweeps this
 // update has already run (the continuation after a verdict turned out negative)
 template <class T> void bp_update_t(State* s, const tnqs_bp_opts* o, int* niter_out, double* diff_out, bool optimistic = false, int iters_before = 0);

@@ -29,6 +29,18 @@ def test_library_exports_every_declared_symbol():
     assert lib.tnqs_version() >= 100
 
 
+def test_library_exports_every_declared_debug_symbol():
+    """the kernel-level entry points of include/tnqs_debug.h (tests/test_gpu_kernels.py reaches every kernel through them): each declaration has its export"""
+    import ctypes
+    import tnqs_amd as tn
+    lib = ctypes.CDLL(tn.LIB_PATH)
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tnqs_debug.h")).read(), flags=re.S)
+    decl = set(re.findall(r"\b(tnqs_dbg_[a-z0-9_]+)\s*\(", src))
+    assert {"tnqs_dbg_rowgemm", "tnqs_dbg_gram_mfma", "tnqs_dbg_pair16", "tnqs_dbg_pair_gram2x16", "tnqs_dbg_svd_tall", "tnqs_dbg_fiber_gemm"} <= decl
+    for name in sorted(decl):
+        assert hasattr(lib, name), f"{name} declared in include/tnqs_debug.h but not exported"
+
+
 def test_no_cpu_fallback():
     import torch
     import tnqs_amd as tn

@@ -73,7 +73,8 @@ def fiber_ref(x, X, D, PA, K, PB, Do, No):
                                              (1, 2, 3, 5, 1, 3), (1, 100, 10, 7, 1, 10), (1, 1, 7, 130, 1, 7), (2, 9, 5, 4, 2, 3),
                                              (2, 1, 1, 1, 2, 1), (2, 300, 1, 1, 2, 1), (1, 64, 32, 33, 1, 32), (2, 16, 16, 16, 2, 16),
                                              (3, 5, 4, 6, 3, 2), (2, 70, 8, 3, 2, 11),
-                                             # D K = 64 with fewer than 32 fibers below the leg (rows of a tile = several b-indices): the register-direct kernels' second addressing mode
+                                             # D K = 64 with fewer than 32 fibers below the leg: the shapes of the register-direct kernels' second addressing mode (rows_b),
+                                             # here on mfma_fiber_gemm_w_kernel -- the register-direct kernels themselves: test_rowgemm_on_the_fiber_gemm_shapes
                                              (2, 1, 32, 64, 2, 32), (2, 8, 32, 16, 2, 32), (1, 16, 64, 8, 1, 64), (1, 4, 64, 32, 1, 40), (2, 2, 32, 48, 2, 9)])
 def test_fiber_gemm(dtype, mfma, D, PA, K, PB, Do, No):
     rng = np.random.default_rng(D + PA + K + PB)
@@ -260,8 +261,25 @@ def test_double_pair_gram(chi, lx, ly):
 @pytest.mark.parametrize("D,PA,K,PB", [(2, 64, 32, 64), (1, 128, 64, 32), (2, 1, 32, 2048)])
 def test_bf16x3_fiber_gemm_and_gram_are_f32_accurate(D, PA, K, PB):
     """the other kernels of the bf16 x 3 route (csrc/kernels_x3.hip: x3_rowgemm64_kernel -- chi = 32 epilogue with the site index folded in, chi = 64 mode
-    product -- and x3_gram64_kernel) against f64 references, held to f32-class bounds: 1e-6 of the largest entry for the 64-term products, 3e-6 for the Gram's
-    sums of PA PB terms (the generic tests above allow EPS D K = 4e-5 resp. 3e-5)"""
+    product -- and x3_gram64_kernel, reached through tnqs_dbg_rowgemm / tnqs_dbg_gram_mfma, which report the kernel that ran) against f64 references, held to
+    f32-class bounds: 1e-6 of the largest entry for the 64-term products, 3e-6 for the Gram's sums of PA PB terms (the generic tests above allow EPS D K = 4e-5
+    resp. 3e-5)"""
+    if NO_X3:
+        pytest.skip("the bf16 x 3 kernels are switched off in this process")
+    res, route = rowgemm(D, K, [(PA, PB, K)], seed=PA + PB)
+    assert route == ROUTE_X3
+    (out, ref, _), = res
+    assert np.max(np.abs(out - ref)) < 1e-6 * np.max(np.abs(ref))
+    if D * K == 64 and PA * PB >= 64:
+        ((g, gref),), groute = gram_mfma([(D, PA, K, PB)], False)
+        assert groute == ROUTE_X3
+        assert np.max(np.abs(g - gref)) < 3e-6 * np.max(np.abs(gref))
+
+
+@pytest.mark.parametrize("D,PA,K,PB", [(2, 64, 32, 64), (1, 128, 64, 32), (2, 1, 32, 2048)])
+def test_mfma_fiber_gemm_and_vector_gram_are_f32_accurate(D, PA, K, PB):
+    """the same shapes through tnqs_dbg_fiber_gemm (mfma_fiber_gemm_w_kernel) and tnqs_dbg_gram (KK = 64 without f64 accumulation: the vector Gram of
+    kernels.hip), at the same bounds"""
     rng = np.random.default_rng(D + PA + K + PB)
     x = rnd(rng, D * PA * K * PB, np.complex64)
     X = rnd(rng, D * K * D * K, np.complex64)
@@ -275,10 +293,7 @@ def test_bf16x3_fiber_gemm_and_gram_are_f32_accurate(D, PA, K, PB):
         KK = D * K
         g = np.zeros(KK * KK, dtype=np.complex64)
         assert lib.tnqs_dbg_gram(0, D, PA, K, PB, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), 0, 1) == 0
-        tx = x.reshape(PB, K, PA, D).transpose(3, 1, 2, 0).reshape(D, K, -1).astype(np.complex128)
-        ty = y.reshape(PB, K, PA, D).transpose(3, 1, 2, 0).reshape(D, K, -1).astype(np.complex128)
-        mx = tx.transpose(1, 0, 2).reshape(KK, -1); my = ty.transpose(1, 0, 2).reshape(KK, -1)
-        gref = (mx @ my.conj().T).T.reshape(-1)
+        gref = gram_ref(x, y, D, PA, K, PB)
         assert np.max(np.abs(g - gref)) < 3e-6 * np.max(np.abs(gref))
 
 
@@ -543,3 +558,327 @@ def test_theta_svd_pre_kernel_on_harvested_factors():
     print("sweeps of the preconditioned kernel:", sweeps)
     assert len(sweeps) >= 6 and max(sweeps.values()) <= 8
 
+
+
+# ---- the kernels of single engine launches, reached through the multi-item entry points of include/tnqs_debug.h (items set up as the engine sets them
+# up; a shape the named kernel does not take is refused, and the entry point reports which kernel ran) ------------------------------------------------
+ROUTE_X3, ROUTE_F32, ROUTE_F64, ROUTE_F64_SHARED, ROUTE_HALF_LINES, ROUTE_WHOLE_LINES = 1, 2, 3, 4, 5, 6
+ERR_UNSUPPORTED = -2                                     # include/tnqs.h
+NO_X3 = os.environ.get("TNQS_NO_BF16X3") == "1"          # the library reads the switch once per process: the f32 leg runs in a child (test_f32_matrix_core_leg)
+
+
+def _ints(v):
+    return np.ascontiguousarray(np.asarray(v, dtype=np.int32))
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _measured(kernel, err):
+    print(f"MEASURED {kernel}: {err:.3e}")
+
+
+def rowgemm(D, K, items, scale=1.0, tpw=0, seed=0, zero=False):
+    """items: (PA, PB, No) -> per item (out, ref, norm2) and the route"""
+    rng = np.random.default_rng(seed + 31 * K + D)
+    xs, Xs, refs = [], [], []
+    for (PA, PB, No) in items:
+        x = rnd(rng, D * PA * K * PB, np.complex64) * np.float32(scale)
+        if zero:
+            x[:] = 0
+        X = rnd(rng, D * K * D * No, np.complex64)
+        xs.append(x); Xs.append(X); refs.append(fiber_ref(x, X, D, PA, K, PB, D, No))
+    out = np.zeros(sum(r.size for r in refs), dtype=np.complex64)
+    n2 = np.zeros(len(items)); route = C.c_int(0)
+    PA, PB, No = (_ints([it[q] for it in items]) for q in range(3))
+    rc = lib.tnqs_dbg_rowgemm(D, K, len(items), _p(PA), _p(PB), _p(No), _p(np.concatenate(xs)), _p(np.concatenate(Xs)), _p(out),
+                              n2.ctypes.data_as(C.c_void_p), tpw, C.byref(route))
+    assert rc == 0, lib.tnqs_last_error()
+    outs = np.split(out, np.cumsum([r.size for r in refs])[:-1])
+    return [(o, r, n) for o, r, n in zip(outs, refs, n2)], route.value
+
+
+def rowgemm_route(D, K):
+    return ROUTE_X3 if D * K == 64 and not NO_X3 else ROUTE_F32
+
+
+# bounds of the register-direct kernels, relative to the largest entry of the product (inputs are seeded: the measured maxima on the MI355X are deterministic).
+# bf16 x 3 (D K = 64): the documented f32-class bound 1e-6 (DESIGN.md 4.29; measured 5.9e-7), 1e-4 for data at 1e-36 (the flushed low pieces; measured 5.8e-5).
+# f32 matrix instructions, about five times the measured maximum (EPS D K of test_fiber_gemm would allow 6.4e-5 ... 2.6e-4): <1,1,1> 4.1e-7, <4,4,2> 8.7e-7,
+# and under TNQS_NO_BF16X3=1 <2,2,1> 6.0e-7, <2,2,2> 5.7e-7
+ROWGEMM_TOL = {(ROUTE_X3, 1, 64): 1e-6, (ROUTE_X3, 2, 32): 1e-6, (ROUTE_F32, 1, 32): 2e-6, (ROUTE_F32, 2, 64): 4.5e-6,
+               (ROUTE_F32, 1, 64): 3e-6, (ROUTE_F32, 2, 32): 3e-6}
+ROWGEMM_NORM_TOL = 1e-6             # the norm partials (f32 squares per lane and tile, f64 across): measured 1.4e-7 of sum |ref|^2
+
+
+def rowgemm_tol(D, K, tiny=False):
+    r = rowgemm_route(D, K)
+    return 1e-4 if (tiny and r == ROUTE_X3) else ROWGEMM_TOL[(r, D, K)]
+
+
+# rows of a tile = several b-indices (PA < 32: the kernels' second addressing mode, rows_b), 32 consecutive a-indices (PA = 32, 96); PB keeps PB % (32 / PA) == 0
+ROWGEMM_ITEMS = [(1, 64), (2, 48), (8, 12), (16, 6), (32, 7), (96, 3)]
+
+
+@pytest.mark.parametrize("K,D", [(32, 1), (32, 2), (64, 1), (64, 2)])
+@pytest.mark.parametrize("No", ["1", "5", "K-1", "K"])
+@pytest.mark.parametrize("tpw", [0, 1, 8])
+def test_rowgemm_multi_item_launch(K, D, No, tpw):
+    """launch_mfma_rowgemm as the engine launches it (the chi = 32 gate epilogue of the headline workload: D = 2, K = 32 on x3_rowgemm64_kernel; chi = 64 mode
+    product D = 1, K = 64; mfma_rowgemm_kernel<1,1,1> and <4,4,2>): six items of different PA / PB in ONE launch (binary search on tile_begin), every
+    addressing mode, tail columns No < K, the engine's tiles per workgroup and forced ones with ragged last groups (tpw = 1, 8), and each item's norm
+    partials against sum |ref|^2"""
+    no = {"1": 1, "5": 5, "K-1": K - 1, "K": K}[No]
+    res, route = rowgemm(D, K, [(PA, PB, no) for (PA, PB) in ROWGEMM_ITEMS], tpw=tpw, seed=no)
+    assert route == rowgemm_route(D, K)
+    err = max(np.max(np.abs(o - r)) / np.max(np.abs(r)) for o, r, _ in res)
+    nerr = max(abs(n - np.sum(np.abs(r) ** 2)) / np.sum(np.abs(r) ** 2) for _, r, n in res)
+    _measured(f"rowgemm route {route} D {D} K {K} No {no} tpw {tpw} (norm {nerr:.1e})", err)
+    assert all(np.all(np.isfinite(o)) for o, _, _ in res)          # every output element written
+    assert err < rowgemm_tol(D, K)
+    assert nerr < ROWGEMM_NORM_TOL
+
+
+@pytest.mark.parametrize("K,D", [(32, 1), (32, 2), (64, 1), (64, 2)])
+@pytest.mark.parametrize("scale", [0.0, 1e-36, 1e-12, 1e-3, 1e6])
+def test_rowgemm_scale_sweep(K, D, scale):
+    """the tensor operand at any scale (the bf16 split keeps the f32 exponent range: no scaling anywhere).  At 1e-36 the low bf16 piece of an operand is a
+    denormal that the matrix cores flush: the documented bound 1e-4 (test_bf16x3_plane_kernels_are_f32_accurate).  Scale 0: exact zeros and norm^2 0."""
+    items = [(2, 32, K), (32, 5, K - 1), (16, 4, 5)]
+    res, route = rowgemm(D, K, items, scale=scale or 1.0, zero=scale == 0.0, seed=7)
+    assert route == rowgemm_route(D, K)
+    if scale == 0.0:
+        for o, _, n in res:
+            assert np.all(o == 0) and n == 0.0
+        return
+    err = max(np.max(np.abs(o - r)) / np.max(np.abs(r)) for o, r, _ in res)
+    _measured(f"rowgemm route {route} D {D} K {K} scale {scale:g}", err)
+    assert err < rowgemm_tol(D, K, tiny=scale < 1e-30)
+    if scale > 1e-30:               # (|out|^2 of data at 1e-36 underflows in the f32 partial sums, on any route)
+        assert max(abs(n - np.sum(np.abs(r) ** 2)) / np.sum(np.abs(r) ** 2) for _, r, n in res) < ROWGEMM_NORM_TOL
+
+
+def test_rowgemm_refuses_what_it_does_not_cover():
+    x = np.zeros(2 * 3 * 32 * 5, dtype=np.complex64); X = np.zeros(64 * 64, dtype=np.complex64); out = np.zeros(x.size, dtype=np.complex64)
+    for (D, K, PA, PB, No) in [(2, 32, 3, 5, 32), (2, 32, 4, 5, 32), (2, 32, 32, 5, 33), (3, 32, 32, 1, 32), (2, 16, 32, 1, 16), (2, 32, 48, 1, 32)]:
+        assert lib.tnqs_dbg_rowgemm(D, K, 1, _p(_ints([PA])), _p(_ints([PB])), _p(_ints([No])), _p(x), _p(X), _p(out), None, 0, None) == ERR_UNSUPPORTED
+
+
+def gram_ref(x, y, D, PA, K, PB):
+    KK = D * K
+    tx = x.reshape(PB, K, PA, D).transpose(1, 3, 2, 0).reshape(KK, -1).astype(np.complex128)   # rows s + D k
+    ty = y.reshape(PB, K, PA, D).transpose(1, 3, 2, 0).reshape(KK, -1).astype(np.complex128)
+    return (tx @ ty.conj().T).T.reshape(-1)                                                       # out[i + KK j]
+
+
+def gram_mfma(items, same, nchunks=0, seed=0):
+    rng = np.random.default_rng(seed + len(items))
+    xs = [rnd(rng, int(np.prod(s)), np.complex64) for s in items]
+    ys = xs if same else [rnd(rng, int(np.prod(s)), np.complex64) for s in items]
+    refs = [gram_ref(x, y, *s) for x, y, s in zip(xs, ys, items)]
+    f64 = max(s[0] * s[2] for s in items) > 64
+    out = np.zeros(sum(r.size for r in refs), dtype=np.complex128 if f64 else np.complex64)
+    route = C.c_int(0)
+    rc = lib.tnqs_dbg_gram_mfma(len(items), _p(_ints(items).ravel()), _p(np.concatenate(xs)), None if same else _p(np.concatenate(ys)), _p(out), nchunks, C.byref(route))
+    assert rc == 0, lib.tnqs_last_error()
+    return list(zip(np.split(out, np.cumsum([r.size for r in refs])[:-1]), refs)), route.value
+
+
+# 32 < KK <= 64 (KK = 40, 48, 64), fiber counts PA PB that are not multiples of 64, every item in several chunks
+GRAM64_LAUNCHES = {"kk40": [(1, 7, 40, 30)], "kk48": [(2, 5, 24, 37)], "kk64": [(2, 64, 32, 3)],
+                   "mixed": [(1, 7, 40, 30), (2, 5, 24, 37), (2, 64, 32, 3), (1, 3, 64, 100), (2, 1, 32, 70)]}
+GRAM64_TOL = {ROUTE_X3: 1.5e-6, ROUTE_F32: 2e-6}      # relative to the largest entry; measured x3_gram64_kernel 2.8e-7, mfma_gram64_kernel 3.8e-7
+
+
+@pytest.mark.parametrize("launch", sorted(GRAM64_LAUNCHES))
+@pytest.mark.parametrize("same", [0, 1])
+@pytest.mark.parametrize("nchunks", [0, 3])
+def test_gram_mfma64(launch, same, nchunks):
+    """the BP message Gram for 32 < KK <= 64 (launch_mfma_gram64: x3_gram64_kernel, mfma_gram64_kernel under TNQS_NO_BF16X3=1), X != Y and X == Y, the engine's
+    chunking (one tile per chunk here) and three chunks of several tiles, several items of different KK in one launch (chunk_begin), partials reduced as the
+    engine reduces them"""
+    res, route = gram_mfma(GRAM64_LAUNCHES[launch], same, nchunks)
+    assert route == (ROUTE_F32 if NO_X3 else ROUTE_X3)
+    err = max(np.max(np.abs(o - r)) / np.max(np.abs(r)) for o, r in res)
+    _measured(f"gram64 route {route} {launch} same {same} nchunks {nchunks}", err)
+    assert err < GRAM64_TOL[route]
+
+
+GRAM128_LAUNCHES = {"kk72": ([(2, 5, 36, 41)], ROUTE_F64), "kk72b": ([(1, 3, 72, 50)], ROUTE_F64), "kk128": ([(2, 64, 64, 3), (1, 7, 128, 30)], ROUTE_F64_SHARED),
+                    "mixed96_128": ([(2, 5, 48, 29), (2, 3, 64, 50), (1, 2, 96, 33)], ROUTE_F64)}
+
+
+@pytest.mark.parametrize("launch", sorted(GRAM128_LAUNCHES))
+@pytest.mark.parametrize("nchunks", [0, 2])
+def test_gram_mfma128_f64(launch, nchunks):
+    """the gate-path Gram at chi = 64 (launch_mfma_gram128_f64): f32 operands, products exact in f64, f64 accumulation -- 1e-12 of the largest entry.  Both
+    instantiations: <true, true> when every item has D K = 128 (the engine's all_kk128), <true, false> otherwise (KK = 72, a 96 + 128 launch)"""
+    items, want = GRAM128_LAUNCHES[launch]
+    res, route = gram_mfma(items, True, nchunks)
+    assert route == want
+    err = max(np.max(np.abs(o - r)) / np.max(np.abs(r)) for o, r in res)
+    _measured(f"gram128 route {route} {launch} nchunks {nchunks}", err)
+    assert err < 5e-15             # (the f64 bound 1e-12 is 1000 times the measured 9.4e-16: held to five times that)
+
+
+def test_gram_mfma_refuses_what_it_does_not_cover():
+    x = np.zeros(2 * 64 * 64, dtype=np.complex64); out = np.zeros(128 * 128, dtype=np.complex128)
+    for items, y in [([(1, 2, 32, 3)], None), ([(2, 1, 65, 1)], None), ([(2, 2, 64, 2)], x)]:
+        assert lib.tnqs_dbg_gram_mfma(len(items), _p(_ints(items).ravel()), _p(x), _p(y), _p(out), 0, None) == ERR_UNSUPPORTED
+
+
+def _plane_launch(items, rng):
+    """items: (chi, lx, ly) -> flat tensors, numpy tensors, matrices (Mx, My) as numpy and flat"""
+    flats, ts, ms, mflat = [], [], [], []
+    for (chi, lx, ly) in items:
+        f, t = _site(rng, 2, chi); flats.append(f); ts.append(t)
+        m = rnd(rng, 512, np.complex64); mflat.append(m)
+        ms.append((m[:256].reshape(16, 16).T.astype(np.complex128), m[256:].reshape(16, 16).T.astype(np.complex128)))     # M[i, j] at i + 16 j
+    z = _ints([len(c) for c, _, _ in items]); chi = _ints([x for c, _, _ in items for x in c])
+    lx = _ints([it[1] for it in items]); ly = _ints([it[2] for it in items])
+    return flats, ts, ms, np.concatenate(mflat), (z, chi, lx, ly)
+
+
+def _absorb(t, M, leg):
+    return np.moveaxis(np.tensordot(t, M, axes=([1 + leg], [0])), -1, 1 + leg)
+
+
+# heavy-hex (degree 3), degree 4 with mixed legs, degree 5 and 6; planes that contain leg 0 (leg-0 branch of plane_geometry: mfma_pair16_kernel) and planes that
+# do not (16 contiguous companions: mfma_pair16w_kernel)
+PLANE16_HALF = [((16, 16, 16), 0, 2), ((16, 8, 16, 4), 0, 2), ((16, 4, 16, 8), 2, 0), ((16, 8, 16, 4, 16), 0, 4), ((16, 4, 16, 2, 16, 4), 4, 0)]
+PLANE16_WHOLE = [((16, 16, 16), 1, 2), ((8, 16, 16, 4), 1, 2), ((16, 8, 16, 4, 16), 2, 4), ((16, 4, 16, 2, 16, 4), 2, 4), ((16, 16, 16, 16), 3, 1)]
+
+
+@pytest.mark.parametrize("kind", ["half", "whole"])
+@pytest.mark.parametrize("spw", [0, 4, 12])
+def test_pair16_multi_item_launch(kind, spw):
+    """two 16-dimensional legs absorbed in one pass (launch_mfma_pair16), all geometries of one kind in ONE launch (wg_begin), the engine's slices per
+    workgroup and forced ones with ragged last groups"""
+    items = PLANE16_HALF if kind == "half" else PLANE16_WHOLE
+    rng = np.random.default_rng(len(items) + spw)
+    flats, ts, ms, m, (z, chi, lx, ly) = _plane_launch(items, rng)
+    x = np.concatenate(flats); out = np.zeros_like(x); route = C.c_int(0)
+    rc = lib.tnqs_dbg_pair16(2, len(items), _p(z), _p(chi), _p(lx), _p(ly), _p(x), _p(m), _p(out), spw, C.byref(route))
+    assert rc == 0, lib.tnqs_last_error()
+    assert route.value == (ROUTE_HALF_LINES if kind == "half" else ROUTE_WHOLE_LINES)
+    err = 0.0
+    for o, t, (Mx, My), (c, a, b) in zip(np.split(out, np.cumsum([f.size for f in flats])[:-1]), ts, ms, items):
+        ref = _absorb(_absorb(t, Mx, a), My, b)
+        err = max(err, np.max(np.abs(o.reshape((2,) + c, order="F") - ref)) / np.max(np.abs(ref)))
+    _measured(f"pair16 {kind} spw {spw}", err)
+    assert err < 2e-6              # two chained 16-term f32 products; measured 3.8e-7 (half lines), 3.1e-7 (whole lines)
+
+
+def test_pair16_refuses_mixed_kinds_and_uncovered_planes():
+    items = [PLANE16_HALF[0], PLANE16_WHOLE[0]]
+    rng = np.random.default_rng(0)
+    flats, _, _, m, (z, chi, lx, ly) = _plane_launch(items, rng)
+    x = np.concatenate(flats); out = np.zeros_like(x)
+    assert lib.tnqs_dbg_pair16(2, 2, _p(z), _p(chi), _p(lx), _p(ly), _p(x), _p(m), _p(out), 0, None) == ERR_UNSUPPORTED
+    z1, chi1 = _ints([4]), _ints([4, 16, 8, 16])        # leg 1 above 8 elements: no companion geometry
+    assert lib.tnqs_dbg_pair16(2, 1, _p(z1), _p(chi1), _p(_ints([1])), _p(_ints([3])), _p(x), _p(m), _p(out), 0, None) == ERR_UNSUPPORTED
+
+
+@pytest.mark.parametrize("spw", [0, 8])
+def test_pair_gram2x16_both_and_single_message_items(spw):
+    """both messages of a 16 x 16 plane from one pass over (X, Y) (launch_mfma_pair_gram2x16) and the single-message form of the BP update (My = null,
+    no partial_x), items of both forms and both geometries in ONE launch, partials summed per message"""
+    items = [PLANE16_HALF[1], PLANE16_WHOLE[2], PLANE16_HALF[0], PLANE16_WHOLE[3], PLANE16_HALF[4], PLANE16_WHOLE[1]]
+    both = _ints([1, 1, 0, 0, 1, 0])
+    rng = np.random.default_rng(3 + spw)
+    fx, tx, ms, m, (z, chi, lx, ly) = _plane_launch(items, rng)
+    fy, ty = zip(*[_site(rng, 2, c) for c, _, _ in items])
+    oy = np.zeros(256 * len(items), dtype=np.complex64); ox = np.full(256 * len(items), 7, dtype=np.complex64)
+    rc = lib.tnqs_dbg_pair_gram2x16(2, len(items), _p(z), _p(chi), _p(lx), _p(ly), _p(both), _p(np.concatenate(fx)), _p(np.concatenate(fy)), _p(m), _p(oy), _p(ox), spw)
+    assert rc == 0, lib.tnqs_last_error()
+    err = 0.0
+    for i, ((c, a, b), X, Y, (Mx, My)) in enumerate(zip(items, tx, ty, ms)):
+        zz = len(c)
+        for (absorbed, kept, M, got) in ((a, b, Mx, oy), (b, a, My, ox)):
+            g = got[256 * i: 256 * (i + 1)]
+            if M is My and not both[i]:
+                assert np.all(g == 7)                       # single-message item: no second message written
+                continue
+            axes = [q for q in range(zz + 1) if q != 1 + kept]
+            ref = np.tensordot(_absorb(X, M, absorbed), Y.conj(), axes=(axes, axes))
+            err = max(err, np.max(np.abs(g.reshape(16, 16).T - ref)) / np.max(np.abs(ref)))
+    _measured(f"pair_gram2x16 spw {spw}", err)
+    assert err < 3e-6              # measured 5.6e-7
+
+
+def tall_svd(mats):
+    ms = _ints([a.shape[0] for a in mats]); ns = _ints([a.shape[1] for a in mats])
+    A = np.concatenate([np.asfortranarray(a.astype(np.complex64)).ravel(order="F") for a in mats])
+    fail, pol, sw = (np.zeros(len(mats), dtype=np.int32) for _ in range(3))
+    rc = lib.tnqs_dbg_svd_tall(len(mats), _p(ms), _p(ns), _p(A), _p(fail), _p(pol), _p(sw))
+    assert rc == 0, lib.tnqs_last_error()
+    outs = np.split(A, np.cumsum([a.size for a in mats])[:-1])
+    return [o.reshape(a.shape, order="F").astype(np.complex128) for o, a in zip(outs, mats)], fail, pol, sw
+
+
+def check_tall(a, A):
+    """what test_theta_svd_kernel asserts, with the reconstruction in the form the V-less route allows: A_out = A J with J unitary <=> A_out A_out^H = A A^H"""
+    b = a.astype(np.complex64).astype(np.complex128)
+    s_ref = np.linalg.svd(b, compute_uv=False)
+    nrm = np.linalg.norm(A, axis=0)
+    if s_ref[0] == 0:
+        assert np.all(A == 0)
+        return 0.0
+    e_s = np.max(np.abs(np.sort(nrm)[::-1][:len(s_ref)] - s_ref)) / s_ref[0]
+    big = nrm > 1e-4 * s_ref[0]
+    U = A[:, big] / nrm[big]
+    e_o = np.max(np.abs(U.conj().T @ U - np.eye(U.shape[1])))
+    e_r = np.max(np.abs(A @ A.conj().T - b @ b.conj().T)) / s_ref[0] ** 2
+    _measured("svd_tall singular values", e_s); _measured("svd_tall orthogonality", e_o); _measured("svd_tall reconstruction", e_r)
+    assert e_s < 1e-5 and e_o < 1.25e-6 and e_r < 4.5e-6, (e_s, e_o, e_r)          # measured 2.9e-6, 2.5e-7, 8.6e-7
+    return max(e_s, e_o, e_r)
+
+
+@pytest.mark.parametrize("scale", [1e-9, 1.0, 1e6])
+def test_svd_tall_route(scale):
+    """svd_batch's tall route (tall_gram -> chol_packed -> tall_rt -> Jacobi on R -> tall_w -> tall_mj -> copy_items, polish where the pivot collapsed) at the
+    shapes the engine sends it (m <= 256, 2 <= n <= 128): full rank, rank deficient, spectra over 3.5 decades, badly scaled -- all in one launch with an all-zero
+    item (every pivot refused: tau = 0 and a shift of 1e-14 * 0; J := I, the polishing sweeps factorise it) and an item with exact zero columns next to nonzero
+    ones (the shift keeps its pivots: no failure, no polish)"""
+    rng = np.random.default_rng(int(np.log10(scale)) + 20)
+    mats = []
+    for (m, n, rank) in [(256, 128, 128), (256, 128, 40), (200, 100, 100), (130, 70, 7), (256, 2, 2)]:
+        dec = np.exp(-np.arange(rank) * (8.0 / max(rank, 1)))
+        q1, _ = np.linalg.qr(rnd(rng, (m, rank), np.complex128)); q2, _ = np.linalg.qr(rnd(rng, (n, rank), np.complex128))
+        mats.append((q1 * dec) @ q2.conj().T * scale)
+    zc = rnd(rng, (256, 96), np.complex128) * scale; zc[:, [0, 17, 50, 95]] = 0
+    mats += [np.zeros((256, 128)), zc]
+    outs, fail, pol, sw = tall_svd(mats)
+    assert list(fail) == [0, 0, 0, 0, 0, 1, 0]
+    assert list(pol) == [0, 0, 0, 0, 0, 1, 0]
+    assert np.all(sw >= 0) and np.all(sw < 60)
+    for a, A in zip(mats, outs):
+        check_tall(a, A)
+
+
+def test_f32_matrix_core_leg():
+    """the f32 matrix-instruction variants that only run under TNQS_NO_BF16X3=1 (mfma_rowgemm_kernel<2,2,1>, <2,2,2>, mfma_gram64_kernel): the library reads
+    the switch once per process, so the rowgemm and Gram tests above run again in a child process with the switch set, asserting that route"""
+    if NO_X3:
+        pytest.skip("this is the child")
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", os.path.abspath(__file__), "-k", "rowgemm or gram_mfma64", "-p", "no:cacheprovider"],
+                       env=dict(os.environ, TNQS_NO_BF16X3="1", PYTHONPATH=os.pathsep.join(sys.path)), capture_output=True, text=True, timeout=600)
+    print("\n".join(l[l.index("MEASURED"):] for l in r.stdout.splitlines() if "MEASURED" in l))
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    assert " passed" in r.stdout and " failed" not in r.stdout
+
+
+@pytest.mark.parametrize("D,PA,K,PB,No", [(2, 1, 32, 64, 32), (2, 8, 32, 16, 32), (1, 16, 64, 8, 64), (1, 4, 64, 32, 40), (2, 2, 32, 48, 9),
+                                          (2, 64, 64, 8, 64), (1, 128, 64, 16, 64), (1, 64, 32, 64, 32), (2, 32, 32, 32, 32), (2, 128, 32, 4, 17)])
+def test_rowgemm_on_the_fiber_gemm_shapes(D, PA, K, PB, No):
+    """the register-direct kernels on the shapes test_fiber_gemm gives mfma_fiber_gemm_w_kernel that they cover, the rows_b ones (PA < 32) first"""
+    res, route = rowgemm(D, K, [(PA, PB, No)], seed=PA + PB)
+    assert route == rowgemm_route(D, K)
+    (out, ref, n2), = res
+    err = np.max(np.abs(out - ref)) / np.max(np.abs(ref))
+    _measured(f"rowgemm route {route} fiber-gemm shape {(D, PA, K, PB, No)}", err)
+    assert err < rowgemm_tol(D, K)
+    assert abs(n2 - np.sum(np.abs(ref) ** 2)) < ROWGEMM_NORM_TOL * np.sum(np.abs(ref) ** 2)
