@@ -127,15 +127,6 @@ void dbg_chol(int n, const void* G, void* Lout, void* Wout, int* fail, double ta
     dL.down(Lout, b); dW.down(Wout, b); dF.down(fail, 4);
 }
 
-static void tile_params(size_t PA, size_t PB, int TR, int& TA, int& TB, int& nta, int& ntb) {
-    TA = (int)std::min<size_t>(PA, TR); TB = std::max(1, TR / TA); TB = (int)std::min<size_t>(TB, PB);
-    nta = (int)((PA + TA - 1) / TA); ntb = (int)((PB + TB - 1) / TB);
-}
-static int pick_TR(size_t KK, size_t esz, int copies) {
-    for (int tr : {64, 32, 16, 8, 4}) if (KK * tr * esz * copies <= 64 * 1024) return tr;
-    throw Err(TNQS_ERR_UNSUPPORTED, "too large");
-}
-
 void dbg_fiber_gemm(int dtype, int D, int PA, int K, int PB, int Do, int No, const void* in, const void* X, void* out, double* norm2, int use_mfma) {
     need_gpu();
     size_t esz = dtype == TNQS_C64 ? 8 : 16;
@@ -147,11 +138,9 @@ void dbg_fiber_gemm(int dtype, int D, int PA, int K, int PB, int Do, int No, con
     int TR = pick_TR((size_t)D * K, esz, 1);
     bool mf = use_mfma && dtype == TNQS_C64 && mfma_fiber_tile_rows(D * K, Do * No) > 0;
     if (mf) TR = mfma_fiber_tile_rows(D * K, Do * No);
-    tile_params(PA, PB, TR, it.TA, it.TB, it.nta, it.ntb);
-    it.tile_begin = 0; it.want_norm = 1; it.tpw = mf ? 5 : 1;
+    it.want_norm = 1;
     const bool mf64 = use_mfma && dtype == TNQS_C128 && fiber_gemm_f64_covers(it);       // kernels_f64.hip (general form: D, Do, norm partial)
-    if (mf64) { fiber_gemm_f64_tiles(it); it.tpw = 12; }
-    int tiles = (it.nta * it.ntb + it.tpw - 1) / it.tpw;
+    const int tiles = mf64 ? plan_fiber_gemm_f64(&it, 1, nullptr, 12) : plan_fiber_gemm(&it, 1, TR, mf ? 5 : 1);
     DBuf dN((size_t)tiles * 8);
     dI.up(&it, sizeof(it));
     if (mf64) launch_mfma_fiber_gemm_f64(nullptr, (const FiberItem*)dI.p, 1, tiles, D * K, Do * No, (double*)dN.p, true);
@@ -171,26 +160,22 @@ void dbg_gram(int dtype, int D, int PA, int K, int PB, const void* X, const void
     DBuf dX(nin * esz), dY(same ? 1 : nin * esz), dI(sizeof(GramItem)), dR(sizeof(ReduceItem));
     dX.up(X, nin * esz); if (!same) dY.up(Y, nin * esz);
     GramItem it{}; it.X = dX.p; it.Y = same ? dX.p : dY.p; it.D = D; it.PA = PA; it.K = K; it.PB = PB;
-    int TR = pick_TR((size_t)KK + 1, esz, 2);
-    bool mf = use_mfma && dtype == TNQS_C64 && !acc64 && KK <= 32;
-    bool mf64 = use_mfma && dtype == TNQS_C64 && acc64 && same && KK <= 64 && KK >= 16;
-    if (mf || mf64) TR = 64;
+    const bool mf = use_mfma && dtype == TNQS_C64 && !acc64 && KK <= 32;
+    const bool mf64 = use_mfma && dtype == TNQS_C64 && acc64 && same && KK <= 64 && KK >= 16;
     const bool mfz = use_mfma && dtype == TNQS_C128 && gram_f64in_covers(D, K);           // kernels_f64.hip
-    if (mfz) TR = 32;
+    const GramRoute r = mfz ? GramRoute::F64In : mf64 ? GramRoute::F64x64 : mf ? GramRoute::Mfma32 : GramRoute::Generic;
+    const int TR = gram_tile_rows(r, KK, esz);
     tile_params(PA, PB, TR, it.TA, it.TB, it.nta, it.ntb);
-    int ntiles = it.nta * it.ntb; int nch = std::min(7, ntiles);
-    if (const char* e = std::getenv("TNQS_DBG_GRAM_CHUNKS")) nch = std::min(ntiles, std::max(1, std::atoi(e)));
-    it.tiles_per_chunk = (ntiles + nch - 1) / nch; it.nchunks = (ntiles + it.tiles_per_chunk - 1) / it.tiles_per_chunk; it.chunk_begin = 0;
+    const char* e = std::getenv("TNQS_DBG_GRAM_CHUNKS");
+    int npart = 0; plan_gram(&it, 1, r, false, e ? std::max(1, std::atoi(e)) : 7, &npart);
     bool a64 = acc64 || dtype == TNQS_C128;
     size_t asz = a64 ? 16 : 8;
-    int npart = mf ? 4 * it.nchunks : (mf64 ? 2 * it.nchunks : it.nchunks);
     DBuf dP((size_t)npart * KK * KK * asz), dO((size_t)KK * KK * asz);
     it.partial = dP.p; dI.up(&it, sizeof(it));
-    if (mfz) launch_mfma_gram_f64in(nullptr, (const GramItem*)dI.p, 1, it.nchunks);
-    else if (mf64) launch_mfma_gram64_f64(nullptr, (const GramItem*)dI.p, 1, it.nchunks, KK, KK == 64);
-    else if (mf) launch_mfma_gram32(nullptr, (const GramItem*)dI.p, 1, it.nchunks, KK);
-    else if (dtype == TNQS_C64) { if (a64) launch_gram<float, double>(nullptr, (const GramItem*)dI.p, 1, it.nchunks, TR, KK); else launch_gram<float, float>(nullptr, (const GramItem*)dI.p, 1, it.nchunks, TR, KK); }
-    else launch_gram<double, double>(nullptr, (const GramItem*)dI.p, 1, it.nchunks, TR, KK);
+    const GramItem* d = (const GramItem*)dI.p;
+    if (dtype == TNQS_C128) launch_gram_route<double, double>(nullptr, r, d, 1, it.nchunks, TR, KK, KK == 64);
+    else if (a64) launch_gram_route<float, double>(nullptr, r, d, 1, it.nchunks, TR, KK, KK == 64);
+    else launch_gram_route<float, float>(nullptr, r, d, 1, it.nchunks, TR, KK);
     ReduceItem ri{dP.p, dO.p, KK * KK, npart, 0, 0}; dR.up(&ri, sizeof(ri));
     if (a64) launch_reduce<double, double>(nullptr, (const ReduceItem*)dR.p, 1, KK * KK); else launch_reduce<float, float>(nullptr, (const ReduceItem*)dR.p, 1, KK * KK);
     HIPCHK(hipDeviceSynchronize());
@@ -203,12 +188,12 @@ void dbg_pair(int C0, int NMID, int NHI, const void* in, const void* Mx, const v
     DBuf dIn(n * 8), dOut(n * 8), dX(32 * 32 * 8), dY(32 * 32 * 8), dI(sizeof(PairItem));
     dIn.up(in, n * 8); dX.up(Mx, 32 * 32 * 8); dY.up(My, 32 * 32 * 8);
     HIPCHK(hipMemset(dOut.p, 0xff, n * 8));
-    PairItem it{}; it.in = dIn.p; it.out = dOut.p; it.Mx = dX.p; it.My = dY.p; it.slice_begin = 0; it.spw = 3;
+    PairItem it{}; it.in = dIn.p; it.out = dOut.p; it.Mx = dX.p; it.My = dY.p;
     it.g.cstr = 2; it.g.sx = C0; it.g.sy = (long long)C0 * 32 * NMID; it.g.n0 = C0 / 16; it.g.t0 = 16; it.g.n1 = NMID; it.g.t1 = (long long)C0 * 32;
     it.g.n2 = NHI; it.g.t2 = (long long)C0 * 32 * NMID * 32;
-    int nslices = (C0 / 16) * NMID * NHI;
+    const int wgs = plan_pair(&it, 1, 3);
     dI.up(&it, sizeof(it));
-    launch_mfma_pair(nullptr, (const PairItem*)dI.p, 1, pair_wgs(nslices, it.spw));
+    launch_mfma_pair(nullptr, (const PairItem*)dI.p, 1, wgs);
     HIPCHK(hipDeviceSynchronize());
     dOut.down(out, n * 8);
 }
@@ -221,11 +206,11 @@ void dbg_pair_legs(int d, int z, const int* chi, int lx, int ly, const void* in,
     DBuf dIn(n * 8), dOut(n * 8), dX(32 * 32 * 8), dY(32 * 32 * 8), dI(sizeof(PairItem));
     dIn.up(in, n * 8); dX.up(Mx, 32 * 32 * 8); dY.up(My, 32 * 32 * 8);
     HIPCHK(hipMemset(dOut.p, 0xff, n * 8));
-    it.in = dIn.p; it.out = dOut.p; it.Mx = dX.p; it.My = dY.p; it.slice_begin = 0; it.spw = 3;
-    int nslices = it.g.n0 * it.g.n1 * it.g.n2;
-    if ((size_t)nslices * 16 * 1024 != n) throw Err(TNQS_ERR_INVALID, "dbg_pair_legs: slice count");
+    it.in = dIn.p; it.out = dOut.p; it.Mx = dX.p; it.My = dY.p;
+    if ((size_t)it.g.n0 * it.g.n1 * it.g.n2 * 16 * 1024 != n) throw Err(TNQS_ERR_INVALID, "dbg_pair_legs: slice count");
+    const int wgs = plan_pair(&it, 1, 3);
     dI.up(&it, sizeof(it));
-    launch_mfma_pair(nullptr, (const PairItem*)dI.p, 1, pair_wgs(nslices, it.spw));
+    launch_mfma_pair(nullptr, (const PairItem*)dI.p, 1, wgs);
     HIPCHK(hipDeviceSynchronize());
     dOut.down(out, n * 8);
 }
@@ -235,15 +220,14 @@ void dbg_pair_gram(int d, int z, const int* chi, int lx, int ly, const void* X, 
     PairGramItem it{};
     if (!pair_geometry(d, z, chi, lx, ly, it.g)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_pair_gram: shape not covered by the pair kernel");
     size_t n = d; for (int i = 0; i < z; ++i) n *= chi[i];
-    int nslices = it.g.n0 * it.g.n1 * it.g.n2;
-    it.spw = 3; it.wg_begin = 0;
-    const bool x3 = mfma_use_x3();       // the engine's route: the bf16 kernel in its one-message form (half-slice workgroups in groups of 16)
-    int nwg = x3 ? 16 * (((nslices + it.spw - 1) / it.spw + 7) / 8) : (nslices + it.spw - 1) / it.spw, npart = nwg;
+    const bool x3 = mfma_use_x3();       // the engine's route: the bf16 kernel in its one-message form
+    PairGram2Item one{}; one.g = it.g;
+    const int nwg = x3 ? plan_x3_pair_gram1(&one, 1, nullptr, 3) : plan_pair_gram(&it, 1, nullptr, 3), npart = nwg;
     DBuf dX(n * 8), dY(n * 8), dM(32 * 32 * 8), dI(sizeof(PairGram2Item)), dR(sizeof(ReduceItem)), dP((size_t)npart * 1024 * 8), dO(1024 * 8);
     dX.up(X, n * 8); dY.up(Y, n * 8); dM.up(M, 32 * 32 * 8);
     it.X = dX.p; it.Y = dY.p; it.M = dM.p; it.partial = dP.p;
     if (x3) {
-        PairGram2Item one{}; one.X = it.X; one.Y = it.Y; one.Mx = it.M; one.My = nullptr; one.partial_y = it.partial; one.partial_x = nullptr; one.g = it.g; one.wg_begin = 0; one.spw = it.spw;
+        one.X = it.X; one.Y = it.Y; one.Mx = it.M; one.partial_y = it.partial;
         dI.up(&one, sizeof(one));
         launch_x3_pair_gram1(nullptr, (const PairGram2Item*)dI.p, 1, nwg);
     } else {
@@ -262,9 +246,7 @@ void dbg_pair_gram2(int d, int z, const int* chi, int lx, int ly, const void* X,
     PairGram2Item it{};
     if (!pair_geometry(d, z, chi, lx, ly, it.g)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_pair_gram2: shape not covered");
     size_t n = d; for (int i = 0; i < z; ++i) n *= chi[i];
-    int nslices = it.g.n0 * it.g.n1 * it.g.n2;
-    it.spw = 3; it.wg_begin = 0;
-    int npairs = (nslices + it.spw - 1) / it.spw, nwg = pair_gram2_group() * ((npairs + 7) / 8), npart = nwg;
+    const int nwg = plan_pair_gram2(&it, 1, nullptr, 3), npart = nwg;
     DBuf dX(n * 8), dY(n * 8), dMx(1024 * 8), dMy(1024 * 8), dI(sizeof(PairGram2Item)), dR(2 * sizeof(ReduceItem)), dP1((size_t)npart * 1024 * 8), dP2((size_t)npart * 1024 * 8), dO(2 * 1024 * 8);
     dX.up(X, n * 8); dY.up(Y, n * 8); dMx.up(Mx, 1024 * 8); dMy.up(My, 1024 * 8);
     it.X = dX.p; it.Y = dY.p; it.Mx = dMx.p; it.My = dMy.p; it.partial_y = dP1.p; it.partial_x = dP2.p;
@@ -303,15 +285,14 @@ static void dbg_bench_plane16(int which, int nsites, int lx, int ly, int reps, d
     fill_random(dA.p, (size_t)nsites * n * 2, 1); fill_random(dB.p, (size_t)nsites * n * 2, 2); fill_random(dM.p, 2 * 256 * 2, 3);
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     float t = 0.f;
-    const double tot = (double)nsites * g.nslices();
     if (which == 2) {
         std::vector<Pair16Item> items(nsites);
-        int spw = 4; while (spw < 64 && tot / (2 * spw) >= 2048.0) spw *= 2;
-        int wgs = 0;
         for (int i = 0; i < nsites; ++i) {
             Pair16Item& it = items[i]; it.g = g; it.in = (char*)dA.p + (size_t)i * n * 8; it.out = (char*)dB.p + (size_t)i * n * 8;
-            it.Mx = dM.p; it.My = (char*)dM.p + 256 * 8; it.wg_begin = wgs; it.spw = spw; wgs += (g.nslices() + spw - 1) / spw;
+            it.Mx = dM.p; it.My = (char*)dM.p + 256 * 8;
         }
+        int w[2]; plan_pair16(items.data(), nsites, w);
+        const int wgs = w[pair16_whole_lines(g) ? 1 : 0];
         DBuf dI(items.size() * sizeof(Pair16Item)); dI.up(items.data(), items.size() * sizeof(Pair16Item));
         launch_mfma_pair16(nullptr, (const Pair16Item*)dI.p, nsites, wgs, pair16_whole_lines(g));
         HIPCHK(hipEventRecord(e0, nullptr));
@@ -319,14 +300,13 @@ static void dbg_bench_plane16(int which, int nsites, int lx, int ly, int reps, d
         HIPCHK(hipEventRecord(e1, nullptr)); HIPCHK(hipEventSynchronize(e1)); HIPCHK(hipEventElapsedTime(&t, e0, e1));
     } else {
         std::vector<PairGram2x16Item> items(nsites);
-        int spw = pair_gram2x16_slices_at_a_time(); while (spw < 128 && tot / (2 * spw) >= 2048.0) spw *= 2;
-        int wgs = 0; const int nwg = (g.nslices() + spw - 1) / spw;
+        for (auto& it : items) it.g = g;
+        const int wgs = plan_pair_gram2x16(items.data(), nsites), nwg = wgs / nsites;      // (identical items)
         DBuf dP((size_t)2 * nsites * nwg * 256 * 8);
         for (int i = 0; i < nsites; ++i) {
-            PairGram2x16Item& it = items[i]; it.g = g; it.X = (char*)dA.p + (size_t)i * n * 8; it.Y = (char*)dB.p + (size_t)i * n * 8;
-            it.Mx = dM.p; it.My = (char*)dM.p + 256 * 8; it.wg_begin = wgs; it.spw = spw;
+            PairGram2x16Item& it = items[i]; it.X = (char*)dA.p + (size_t)i * n * 8; it.Y = (char*)dB.p + (size_t)i * n * 8;
+            it.Mx = dM.p; it.My = (char*)dM.p + 256 * 8;
             it.partial_y = (char*)dP.p + (size_t)(2 * i) * nwg * 256 * 8; it.partial_x = (char*)dP.p + (size_t)(2 * i + 1) * nwg * 256 * 8;
-            wgs += nwg;
         }
         DBuf dI(items.size() * sizeof(PairGram2x16Item)); dI.up(items.data(), items.size() * sizeof(PairGram2x16Item));
         launch_mfma_pair_gram2x16(nullptr, (const PairGram2x16Item*)dI.p, nsites, wgs);
@@ -344,7 +324,7 @@ void dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double* ms
     const int chi[4] = {32, 32, 32, 32};
     PairGeom g{};
     if (!pair_geometry(2, 4, chi, lx, ly, g)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_bench_plane: legs not covered");
-    const size_t n = (size_t)2 * 32 * 32 * 32 * 32, nslices = (size_t)g.n0 * g.n1 * g.n2;
+    const size_t n = (size_t)2 * 32 * 32 * 32 * 32;
     DBuf dA((size_t)nsites * n * 8), dB((size_t)nsites * n * 8), dM(2 * 1024 * 8);
     fill_random(dA.p, (size_t)nsites * n * 2, 1); fill_random(dB.p, (size_t)nsites * n * 2, 2); fill_random(dM.p, 2 * 1024 * 2, 3);
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
@@ -356,19 +336,22 @@ void dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double* ms
         const char* e = std::getenv("TNQS_DBG_GROUP"); int G = e ? std::atoi(e) : 0; if (G <= 0 || G > nsites) G = nsites;
         int ox = -1, oy = -1; for (int q = 0; q < 4; ++q) if (q != lx && q != ly) { if (ox < 0) ox = q; else oy = q; }
         PairGeom g2{}; if (!pair_geometry(2, 4, chi, ox, oy, g2)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_bench_plane: other legs not covered");
-        const size_t ns2 = (size_t)g2.n0 * g2.n1 * g2.n2;
         const int ngroups = (nsites + G - 1) / G;
-        int spw_p = pair_spw((double)G * nslices);
-        int spw_g = 16; while (spw_g > 1 && (long)G * pair_gram2_group() * (((ns2 + spw_g - 1) / spw_g + 7) / 8) < 1024) spw_g >>= 1;
-        const int npairs = (int)((ns2 + spw_g - 1) / spw_g), nwg_g = pair_gram2_group() * ((npairs + 7) / 8);
-        DBuf dT((size_t)G * n * 8), dP((size_t)2 * nsites * nwg_g * 1024 * 8);
         std::vector<PairItem> pit(nsites); std::vector<PairGram2Item> git(nsites);
-        std::vector<int> pw(ngroups, 0), gwg(ngroups, 0);
+        for (int i = 0; i < nsites; ++i) { pit[i].g = g; git[i].g = g2; }
+        // the engine's layout of a group of G sites; the last group keeps the first one's spw
+        std::vector<int> pw(ngroups), gwg(ngroups), nwg(nsites);
+        for (int gr = 0; gr < ngroups; ++gr) {
+            const int cnt = std::min(G, nsites - gr * G);
+            pw[gr] = plan_pair(&pit[(size_t)gr * G], cnt, gr ? pit[0].spw : 0);
+            gwg[gr] = plan_pair_gram2(&git[(size_t)gr * G], cnt, &nwg[(size_t)gr * G], gr ? git[0].spw : 0);
+        }
+        const int spw_p = pit[0].spw, spw_g = git[0].spw, nwg_g = nwg[0];
+        DBuf dT((size_t)G * n * 8), dP((size_t)2 * nsites * nwg_g * 1024 * 8);
         for (int i = 0; i < nsites; ++i) {
-            const int gr = i / G, k = i % G;
-            PairItem& a = pit[i]; a.g = g; a.in = (char*)dA.p + (size_t)i * n * 8; a.out = (char*)dT.p + (size_t)k * n * 8; a.Mx = dM.p; a.My = (char*)dM.p + 1024 * 8;
-            a.slice_begin = pw[gr]; a.spw = spw_p; pw[gr] += pair_wgs((int)nslices, spw_p);
-            PairGram2Item& b = git[i]; b.g = g2; b.X = a.out; b.Y = a.in; b.Mx = dM.p; b.My = (char*)dM.p + 1024 * 8; b.wg_begin = gwg[gr]; b.spw = spw_g; gwg[gr] += nwg_g;
+            const int k = i % G;
+            PairItem& a = pit[i]; a.in = (char*)dA.p + (size_t)i * n * 8; a.out = (char*)dT.p + (size_t)k * n * 8; a.Mx = dM.p; a.My = (char*)dM.p + 1024 * 8;
+            PairGram2Item& b = git[i]; b.X = a.out; b.Y = a.in; b.Mx = dM.p; b.My = (char*)dM.p + 1024 * 8;
             b.partial_y = (char*)dP.p + (size_t)(2 * i) * nwg_g * 1024 * 8; b.partial_x = (char*)dP.p + (size_t)(2 * i + 1) * nwg_g * 1024 * 8;
         }
         DBuf dPI(pit.size() * sizeof(PairItem)), dGI(git.size() * sizeof(PairGram2Item));
@@ -387,11 +370,11 @@ void dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double* ms
         std::fprintf(stderr, "level bench: group %d, pair spw %d, gram spw %d\n", G, spw_p, spw_g);
     } else if (which == 0) {
         std::vector<PairItem> items(nsites);
-        const int spw = pair_spw((double)nsites * nslices); int wgs = 0;
         for (int i = 0; i < nsites; ++i) {
             PairItem& it = items[i]; it.g = g; it.in = (char*)dA.p + (size_t)i * n * 8; it.out = (char*)dB.p + (size_t)i * n * 8;
-            it.Mx = dM.p; it.My = (char*)dM.p + 1024 * 8; it.slice_begin = wgs; it.spw = spw; wgs += pair_wgs((int)nslices, spw);
+            it.Mx = dM.p; it.My = (char*)dM.p + 1024 * 8;
         }
+        const int wgs = plan_pair(items.data(), nsites);
         DBuf dI(items.size() * sizeof(PairItem)); dI.up(items.data(), items.size() * sizeof(PairItem));
         launch_mfma_pair(nullptr, (const PairItem*)dI.p, nsites, wgs);
         HIPCHK(hipEventRecord(e0, nullptr));
@@ -399,14 +382,13 @@ void dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double* ms
         HIPCHK(hipEventRecord(e1, nullptr)); HIPCHK(hipEventSynchronize(e1)); HIPCHK(hipEventElapsedTime(&t, e0, e1));
     } else {
         std::vector<PairGram2Item> items(nsites);
-        const int spw = 16; int wgs = 0;
-        const int npairs = (int)((nslices + spw - 1) / spw), nwg = pair_gram2_group() * ((npairs + 7) / 8);
+        for (auto& it : items) it.g = g;
+        const int wgs = plan_pair_gram2(items.data(), nsites, nullptr, 16), nwg = wgs / nsites;      // (identical items)
         DBuf dP((size_t)2 * nsites * nwg * 1024 * 8);
         for (int i = 0; i < nsites; ++i) {
-            PairGram2Item& it = items[i]; it.g = g; it.X = (char*)dA.p + (size_t)i * n * 8; it.Y = (char*)dB.p + (size_t)i * n * 8;
-            it.Mx = dM.p; it.My = (char*)dM.p + 1024 * 8; it.wg_begin = wgs; it.spw = spw;
+            PairGram2Item& it = items[i]; it.X = (char*)dA.p + (size_t)i * n * 8; it.Y = (char*)dB.p + (size_t)i * n * 8;
+            it.Mx = dM.p; it.My = (char*)dM.p + 1024 * 8;
             it.partial_y = (char*)dP.p + (size_t)(2 * i) * nwg * 1024 * 8; it.partial_x = (char*)dP.p + (size_t)(2 * i + 1) * nwg * 1024 * 8;
-            wgs += nwg;
         }
         DBuf dI(items.size() * sizeof(PairGram2Item)); dI.up(items.data(), items.size() * sizeof(PairGram2Item));
         launch_mfma_pair_gram2(nullptr, (const PairGram2Item*)dI.p, nsites, wgs);
@@ -426,12 +408,10 @@ void dbg_gram_fused(int PA, int K, int PB, const void* X, const void* Y, const v
     GramItem it{}; it.X = dX.p; it.Y = dY.p; it.M = dM.p; it.D = 1; it.PA = PA; it.K = K; it.PB = PB;
     tile_params(PA, PB, 64, it.TA, it.TB, it.nta, it.ntb);
     if (it.TA * it.TB != 64) throw Err(TNQS_ERR_INVALID, "dbg_gram_fused: tiles must hold 64 fibers");
-    int ntiles = it.nta * it.ntb; int nch = std::min(3, ntiles);
-    it.tiles_per_chunk = (ntiles + nch - 1) / nch; it.nchunks = (ntiles + it.tiles_per_chunk - 1) / it.tiles_per_chunk; it.chunk_begin = 0;
-    int npart = 4 * it.nchunks;
+    int npart = 0; plan_gram(&it, 1, GramRoute::Fused32, false, 3, &npart);
     DBuf dP((size_t)npart * K * K * 8), dO((size_t)K * K * 8);
     it.partial = dP.p; dI.up(&it, sizeof(it));
-    launch_mfma_gram32_fused(nullptr, (const GramItem*)dI.p, 1, it.nchunks);
+    launch_gram_route<float, float>(nullptr, GramRoute::Fused32, (const GramItem*)dI.p, 1, it.nchunks, 64, K);
     ReduceItem ri{dP.p, dO.p, K * K, npart, 0, 0}; dR.up(&ri, sizeof(ri));
     launch_reduce<float, float>(nullptr, (const ReduceItem*)dR.p, 1, K * K);
     HIPCHK(hipDeviceSynchronize());
@@ -452,13 +432,12 @@ void dbg_gauge_gram(int z, const int* chi, int bleg, const void* X, const void* 
     GramItem it{}; it.X = dX.p; it.Y = dX.p; it.M = dM.p; it.D = 2; it.PA = (int)PA; it.K = K; it.PB = (int)PB;
     tile_params(PA, PB, 64, it.TA, it.TB, it.nta, it.ntb);
     if (k16) { it.nta = gauge_gram32_units(z, chi, bleg); it.ntb = 1; }
-    const int ntiles = it.nta * it.ntb, nch = std::min(5, ntiles);
-    it.tiles_per_chunk = (ntiles + nch - 1) / nch; it.nchunks = (ntiles + it.tiles_per_chunk - 1) / it.tiles_per_chunk; it.chunk_begin = 0;
-    const int npart = k16 ? it.nchunks : 2 * it.nchunks;
+    const GramRoute r = k16 ? GramRoute::Gauge32 : GramRoute::Gauge64;
+    int npart = 0; plan_gram(&it, 1, r, true, 5, &npart);
     DBuf dP((size_t)npart * KK * KK * 16), dO((size_t)KK * KK * 16);
     HIPCHK(hipMemset(dP.p, 0, (size_t)npart * KK * KK * 16));
     it.partial = dP.p; dI.up(&it, sizeof(it));
-    if (k16) launch_mfma_gauge_gram32(nullptr, (const GramItem*)dI.p, 1, it.nchunks); else launch_mfma_gauge_gram64(nullptr, (const GramItem*)dI.p, 1, it.nchunks);
+    launch_gram_route<float, double>(nullptr, r, (const GramItem*)dI.p, 1, it.nchunks, 64, KK);
     ReduceItem ri{dP.p, dO.p, KK * KK, npart, 0, 0}; dR.up(&ri, sizeof(ri));
     launch_reduce<double, double>(nullptr, (const ReduceItem*)dR.p, 1, KK * KK);
     HIPCHK(hipDeviceSynchronize());
@@ -479,26 +458,23 @@ void dbg_rowgemm(int D, int K, int nitems, const int* PA, const int* PB, const i
     need_gpu();
     if (nitems < 1 || !PA || !PB || !No) throw Err(TNQS_ERR_INVALID, "dbg_rowgemm: bad arguments");
     std::vector<FiberItem> items(nitems);
-    double tiles = 0;
     for (int i = 0; i < nitems; ++i) {
         FiberItem& it = items[i]; it.D = D; it.PA = PA[i]; it.K = K; it.PB = PB[i]; it.Do = D; it.No = No[i];
         if (PA[i] < 1 || PB[i] < 1 || !rowgemm_covers(it)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_rowgemm: item not covered by the register-direct kernels");
-        rowgemm_tiles(it); it.want_norm = 1; tiles += (double)it.nta * it.ntb;
+        rowgemm_tiles(it); it.want_norm = 1;
     }
     std::vector<size_t> oi, ox, oo;
     cat_offsets(nitems, oi, [&](int i) { return (size_t)D * PA[i] * K * PB[i]; });
     cat_offsets(nitems, ox, [&](int i) { return (size_t)D * K * D * No[i]; });
     cat_offsets(nitems, oo, [&](int i) { return (size_t)D * PA[i] * No[i] * PB[i]; });
-    if (tpw <= 0) { tpw = (int)std::max(4.0, std::min(D == 2 ? 32.0 : 64.0, tiles / 2048.0)); tpw &= ~3; }
     DBuf dIn(oi[nitems] * 8), dX(ox[nitems] * 8), dOut(oo[nitems] * 8), dI(sizeof(FiberItem) * nitems);
     dIn.up(in, oi[nitems] * 8); dX.up(X, ox[nitems] * 8);
     HIPCHK(hipMemset(dOut.p, 0xff, oo[nitems] * 8));
-    int wgs = 0;
     for (int i = 0; i < nitems; ++i) {
         FiberItem& it = items[i];
         it.in = (char*)dIn.p + oi[i] * 8; it.X = (char*)dX.p + ox[i] * 8; it.out = (char*)dOut.p + oo[i] * 8;
-        it.tpw = tpw; it.tile_begin = wgs; wgs += (it.nta * it.ntb + tpw - 1) / tpw;
     }
+    const int wgs = plan_rowgemm(items.data(), nitems, D == 2 ? 32 : 64, nullptr, tpw);
     DBuf dN((size_t)wgs * 8);
     dI.up(items.data(), sizeof(FiberItem) * nitems);
     launch_mfma_rowgemm(nullptr, (const FiberItem*)dI.p, nitems, wgs, D, K, (double*)dN.p);
@@ -534,30 +510,28 @@ void dbg_gram_mfma(int nitems, const int* shape, const void* X, const void* Y, v
     cat_offsets(nitems, oo, [&](int i) { const int* q = shape + 4 * i; return (size_t)q[0] * q[2] * q[0] * q[2]; });
     DBuf dX(oi[nitems] * 8), dY(Y ? oi[nitems] * 8 : 1), dO(oo[nitems] * asz), dI(sizeof(GramItem) * nitems), dR(sizeof(ReduceItem) * nitems);
     dX.up(X, oi[nitems] * 8); if (Y) dY.up(Y, oi[nitems] * 8);
-    const int per_item = std::max(1, (f64 ? 1024 : 2048) / nitems);      // run_grams: target workgroups per launch
-    std::vector<GramItem> items(nitems); std::vector<size_t> op(nitems + 1, 0); int chunks = 0;
+    const GramRoute r = f64 ? GramRoute::F64x128 : GramRoute::Mfma64;
+    std::vector<GramItem> items(nitems); std::vector<size_t> op(nitems + 1, 0); std::vector<int> npart(nitems);
     for (int i = 0; i < nitems; ++i) {
         const int* q = shape + 4 * i; GramItem& it = items[i];
         it.X = (char*)dX.p + oi[i] * 8; it.Y = Y ? (const void*)((char*)dY.p + oi[i] * 8) : it.X;
         it.D = q[0]; it.PA = q[1]; it.K = q[2]; it.PB = q[3];
         tile_params(it.PA, it.PB, 64, it.TA, it.TB, it.nta, it.ntb);
-        const int ntiles = it.nta * it.ntb, nch = std::min(nchunks > 0 ? nchunks : per_item, ntiles);
-        it.tiles_per_chunk = (ntiles + nch - 1) / nch; it.nchunks = (ntiles + it.tiles_per_chunk - 1) / it.tiles_per_chunk;
-        it.chunk_begin = chunks; chunks += it.nchunks;
-        op[i + 1] = op[i] + (size_t)it.nchunks * (oo[i + 1] - oo[i]);         // one partial per chunk
     }
+    const int chunks = plan_gram(items.data(), nitems, r, f64, nchunks, npart.data());
+    for (int i = 0; i < nitems; ++i) op[i + 1] = op[i] + (size_t)npart[i] * (oo[i + 1] - oo[i]);
     DBuf dP(op[nitems] * asz);
     std::vector<ReduceItem> ri(nitems);
     for (int i = 0; i < nitems; ++i) {
         items[i].partial = (char*)dP.p + op[i] * asz;
-        ri[i] = ReduceItem{items[i].partial, (char*)dO.p + oo[i] * asz, (int)(oo[i + 1] - oo[i]), items[i].nchunks, 0, (int)oo[i]};
+        ri[i] = ReduceItem{items[i].partial, (char*)dO.p + oo[i] * asz, (int)(oo[i + 1] - oo[i]), npart[i], 0, (int)oo[i]};
     }
     dI.up(items.data(), sizeof(GramItem) * nitems); dR.up(ri.data(), sizeof(ReduceItem) * nitems);
     if (f64) {
-        launch_mfma_gram128_f64(nullptr, (const GramItem*)dI.p, nitems, chunks, KKmax, all128);
+        launch_gram_route<float, double>(nullptr, r, (const GramItem*)dI.p, nitems, chunks, 64, KKmax, all128);
         launch_reduce<double, double>(nullptr, (const ReduceItem*)dR.p, nitems, (int)oo[nitems]);
     } else {
-        launch_mfma_gram64(nullptr, (const GramItem*)dI.p, nitems, chunks, KKmax);
+        launch_gram_route<float, float>(nullptr, r, (const GramItem*)dI.p, nitems, chunks, 64, KKmax);
         launch_reduce<float, float>(nullptr, (const ReduceItem*)dR.p, nitems, (int)oo[nitems]);
     }
     HIPCHK(hipDeviceSynchronize());
@@ -586,22 +560,20 @@ void dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* lx, 
     std::vector<PlaneGeom> g; std::vector<size_t> off;
     plane_items(d, nitems, z, chi, lx, ly, g, off);
     const bool wl = pair16_whole_lines(g[0]);
-    double slices = 0;
-    for (int i = 0; i < nitems; ++i) { if (pair16_whole_lines(g[i]) != wl) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_pair16: one launch holds items of one kind"); slices += g[i].nslices(); }
-    if (spw <= 0) { spw = 4; while (spw < 64 && slices / (2 * spw) >= 2048.0) spw *= 2; }
-    if (spw % 4) throw Err(TNQS_ERR_INVALID, "dbg_pair16: spw must be a multiple of 4");
+    for (int i = 0; i < nitems; ++i) if (pair16_whole_lines(g[i]) != wl) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_pair16: one launch holds items of one kind");
+    if (spw > 0 && spw % 4) throw Err(TNQS_ERR_INVALID, "dbg_pair16: spw must be a multiple of 4");
     const size_t n = off[nitems];
     DBuf dIn(n * 8), dOut(n * 8), dM((size_t)nitems * 512 * 8), dI(sizeof(Pair16Item) * nitems);
     dIn.up(in, n * 8); dM.up(M, (size_t)nitems * 512 * 8);
     HIPCHK(hipMemset(dOut.p, 0xff, n * 8));
-    std::vector<Pair16Item> items(nitems); int wgs = 0;
+    std::vector<Pair16Item> items(nitems);
     for (int i = 0; i < nitems; ++i) {
         Pair16Item& it = items[i]; it.g = g[i]; it.in = (char*)dIn.p + off[i] * 8; it.out = (char*)dOut.p + off[i] * 8;
         it.Mx = (char*)dM.p + (size_t)i * 512 * 8; it.My = (char*)it.Mx + 256 * 8;
-        it.spw = spw; it.wg_begin = wgs; wgs += (g[i].nslices() + spw - 1) / spw;
     }
+    int wgs[2]; plan_pair16(items.data(), nitems, wgs, spw);
     dI.up(items.data(), sizeof(Pair16Item) * nitems);
-    launch_mfma_pair16(nullptr, (const Pair16Item*)dI.p, nitems, wgs, wl);
+    launch_mfma_pair16(nullptr, (const Pair16Item*)dI.p, nitems, wgs[wl ? 1 : 0], wl);
     HIPCHK(hipDeviceSynchronize());
     dOut.down(out, n * 8);
     if (route) *route = wl ? TNQS_DBG_ROUTE_WHOLE_LINES : TNQS_DBG_ROUTE_HALF_LINES;
@@ -615,13 +587,10 @@ void dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const in
     std::vector<PlaneGeom> g; std::vector<size_t> off;
     plane_items(d, nitems, z, chi, lx, ly, g, off);
     if (!both) throw Err(TNQS_ERR_INVALID, "dbg_pair_gram2x16: bad arguments");
-    double slices = 0; for (int i = 0; i < nitems; ++i) slices += g[i].nslices();
-    const int at = pair_gram2x16_slices_at_a_time();
-    if (spw <= 0) { spw = at; while (spw < 128 && slices / (2 * spw) >= 2048.0) spw *= 2; }
-    if (spw % at) throw Err(TNQS_ERR_INVALID, "dbg_pair_gram2x16: spw must be a multiple of the slices a workgroup walks at a time");
+    if (spw > 0 && spw % pair_gram2x16_slices_at_a_time()) throw Err(TNQS_ERR_INVALID, "dbg_pair_gram2x16: spw must be a multiple of the slices a workgroup walks at a time");
     const size_t n = off[nitems];
-    std::vector<PairGram2x16Item> items(nitems); int wgs = 0;
-    for (int i = 0; i < nitems; ++i) { items[i].g = g[i]; items[i].spw = spw; items[i].wg_begin = wgs; wgs += (g[i].nslices() + spw - 1) / spw; }
+    std::vector<PairGram2x16Item> items(nitems); std::vector<int> nwg(nitems); for (int i = 0; i < nitems; ++i) items[i].g = g[i];
+    const int wgs = plan_pair_gram2x16(items.data(), nitems, nwg.data(), spw);
     DBuf dX(n * 8), dY(n * 8), dM((size_t)nitems * 512 * 8), dI(sizeof(PairGram2x16Item) * nitems), dP((size_t)2 * wgs * 256 * 8), dO((size_t)2 * nitems * 256 * 8),
          dR(sizeof(ReduceItem) * 2 * nitems);
     dX.up(X, n * 8); dY.up(Y, n * 8); dM.up(M, (size_t)nitems * 512 * 8);
@@ -629,13 +598,12 @@ void dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const in
     std::vector<ReduceItem> ri;
     for (int i = 0; i < nitems; ++i) {
         PairGram2x16Item& it = items[i];
-        const int nwg = (i + 1 < nitems ? items[i + 1].wg_begin : wgs) - it.wg_begin;
         it.X = (char*)dX.p + off[i] * 8; it.Y = (char*)dY.p + off[i] * 8;
         it.Mx = (char*)dM.p + (size_t)i * 512 * 8; it.My = both[i] ? (const void*)((char*)it.Mx + 256 * 8) : nullptr;
         it.partial_y = (char*)dP.p + (size_t)it.wg_begin * 256 * 8;
         it.partial_x = both[i] ? (void*)((char*)dP.p + ((size_t)wgs + it.wg_begin) * 256 * 8) : nullptr;
-        ri.push_back(ReduceItem{it.partial_y, (char*)dO.p + (size_t)i * 256 * 8, 256, nwg, 0, (int)ri.size() * 256});
-        if (both[i]) ri.push_back(ReduceItem{it.partial_x, (char*)dO.p + ((size_t)nitems + i) * 256 * 8, 256, nwg, 0, (int)ri.size() * 256});
+        ri.push_back(ReduceItem{it.partial_y, (char*)dO.p + (size_t)i * 256 * 8, 256, nwg[i], 0, (int)ri.size() * 256});
+        if (both[i]) ri.push_back(ReduceItem{it.partial_x, (char*)dO.p + ((size_t)nitems + i) * 256 * 8, 256, nwg[i], 0, (int)ri.size() * 256});
     }
     dI.up(items.data(), sizeof(PairGram2x16Item) * nitems); dR.up(ri.data(), sizeof(ReduceItem) * ri.size());
     launch_mfma_pair_gram2x16(nullptr, (const PairGram2x16Item*)dI.p, nitems, wgs);

@@ -16,8 +16,7 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
     // ---- stage 0: two legs per pass over the tensor -- 32-dimensional legs: mfma_pair_kernel (once), 16-dimensional legs:
     // mfma_pair16_kernel, repeated while a chain still has two of them (a degree-6 site absorbs its legs in 3 passes instead of 5) ---
     if (std::is_same<T, float>::value && use_mfma() && use_pair()) {
-        std::vector<PairItem> items; int wgs = 0; double bytes = 0, flops = 0;
-        double tot_slices = 0;
+        std::vector<PairItem> items; double bytes = 0, flops = 0;
         std::vector<std::pair<size_t, std::pair<int, int>>> sel;     // chain index, (position of x, position of y) in c.steps
         for (size_t ci = 0; ci < chains.size(); ++ci) {
             Chain& c = chains[ci];
@@ -32,10 +31,8 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
             }
             if (px < 0) continue;
             sel.push_back({ci, {px, py}});
-            tot_slices += (double)c.sd.n / (16.0 * 1024.0);
         }
         if (!sel.empty()) {
-            const int spw = pair_spw(tot_slices);
             for (auto& se : sel) {
                 Chain& c = chains[se.first];
                 int x = c.steps[se.second.first].first, y = c.steps[se.second.second].first;
@@ -44,20 +41,19 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
                 if (!dst) dst = dalloc(s, c.sd.n * esz);
                 it.in = c.result; it.out = dst->p; it.Mx = c.steps[se.second.first].second; it.My = c.steps[se.second.second].second;
                 if (!pair_geometry(c.sd.d, c.sd.z, c.sd.chi.data(), x, y, it.g)) throw Err(TNQS_ERR_HIP, "internal: pair geometry");
-                int nslices = it.g.n0 * it.g.n1 * it.g.n2;
-                it.spw = spw; it.slice_begin = wgs; wgs += pair_wgs(nslices, spw);
                 items.push_back(it);
                 c.result = dst->p; nt[se.first]++; c.trail.push_back({x, y});
                 // drop the two consumed steps
                 c.steps.erase(c.steps.begin() + se.second.second); c.steps.erase(c.steps.begin() + se.second.first);
                 bytes += 2.0 * c.sd.n * esz; flops += 2 * 8.0 * c.sd.n * 32;
             }
+            const int wgs = plan_pair(items.data(), (int)items.size());
             const PairItem* d = upload(s, items);
             ProfScope ps(s, cls_pair, bytes, flops);
             launch_mfma_pair(s->stream, d, (int)items.size(), wgs);
         }
         for (;;) {                                                  // 16-dimensional legs, two per round
-            std::vector<Pair16Item> it16; std::vector<std::pair<size_t, std::pair<int, int>>> sel16; double slices16 = 0, by16 = 0, fl16 = 0;
+            std::vector<Pair16Item> it16; std::vector<std::pair<size_t, std::pair<int, int>>> sel16; double by16 = 0, fl16 = 0;
             for (size_t ci = 0; ci < chains.size(); ++ci) {
                 Chain& c = chains[ci];
                 if (c.steps.size() < 2 || c.sd.n < (size_t)(1u << 14)) continue;     // small tensors stay on the single-leg kernel (launch bound)
@@ -66,7 +62,7 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
                     Pair16Item it{};
                     if (plane_geometry(c.sd.d, c.sd.z, c.sd.chi.data(), c.steps[0].first, c.steps[1].first, 16, it.g)) {
                         it.Mx = c.steps[0].second; it.My = c.steps[1].second;
-                        it16.push_back(it); sel16.push_back({ci, {0, 1}}); slices16 += (double)it.g.nslices(); found = true;
+                        it16.push_back(it); sel16.push_back({ci, {0, 1}}); found = true;
                     }
                 }
                 // the LOWEST remaining leg with the HIGHEST one (round 5): a plane that contains leg 0 streams at 4.4 - 4.55 TB/s, every other one at 3.7 - 3.9 and
@@ -77,20 +73,18 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
                         Pair16Item it{};
                         if (!plane_geometry(c.sd.d, c.sd.z, c.sd.chi.data(), c.steps[qx].first, c.steps[qy].first, 16, it.g)) continue;
                         it.Mx = c.steps[qx].second; it.My = c.steps[qy].second;
-                        it16.push_back(it); sel16.push_back({ci, {qx, qy}}); slices16 += (double)it.g.nslices(); found = true;
+                        it16.push_back(it); sel16.push_back({ci, {qx, qy}}); found = true;
                     }
             }
             if (it16.empty()) break;
-            // slices per workgroup: a multiple of 4 (4 slices at a time, as 8 waves x half slices or 4 waves x whole slices), at least ~8 workgroups per CU overall
-            int spw = 4; while (spw < 64 && slices16 / (2 * spw) >= 2048.0) spw *= 2;
-            std::vector<Pair16Item> kind[2]; int wgs16[2] = {0, 0};           // [1]: whole 128-byte lines per wave (pair16_whole_lines)
+            std::vector<Pair16Item> kind[2]; int wgs16[2];           // [1]: whole 128-byte lines per wave (pair16_whole_lines)
+            plan_pair16(it16.data(), (int)it16.size(), wgs16);
             for (size_t q = 0; q < it16.size(); ++q) {
                 Chain& c = chains[sel16[q].first]; Pair16Item& it = it16[q];
-                const int wl = pair16_whole_lines(it.g) ? 1 : 0;
                 Buf& dst = c.tmp[nt[sel16[q].first] & 1];
                 if (!dst) dst = dalloc(s, c.sd.n * esz);
-                it.in = c.result; it.out = dst->p; it.spw = spw; it.wg_begin = wgs16[wl]; wgs16[wl] += (it.g.nslices() + spw - 1) / spw;
-                kind[wl].push_back(it);
+                it.in = c.result; it.out = dst->p;
+                kind[pair16_whole_lines(it.g) ? 1 : 0].push_back(it);
                 c.result = dst->p; nt[sel16[q].first]++;
                 c.trail.push_back({c.steps[sel16[q].second.first].first, c.steps[sel16[q].second.second].first});
                 c.steps.erase(c.steps.begin() + sel16[q].second.second); c.steps.erase(c.steps.begin() + sel16[q].second.first);
@@ -107,14 +101,14 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
     size_t maxsteps = 0;
     for (auto& c : chains) maxsteps = std::max(maxsteps, c.steps.size());
     for (size_t o = 0; o < maxsteps; ++o) {
-        std::vector<FiberItem> items; int tiles = 0; size_t KKmax = 1; double bytes = 0, flops = 0;
+        std::vector<FiberItem> items; size_t KKmax = 1; double bytes = 0, flops = 0;
         for (auto& c : chains) if (c.steps.size() > o) KKmax = std::max<size_t>(KKmax, c.sd.chi[c.steps[o].first]);
         int TR = pick_TR(KKmax, esz, 1);
         bool mf = false;
         if (std::is_same<T, float>::value && use_mfma() && KKmax >= 8) { int t = mfma_fiber_tile_rows((int)KKmax, (int)KKmax); if (t > 0) { TR = t; mf = true; } }
         int tpw = 1;
         if (mf) { double tot = 0; for (auto& c : chains) if (c.steps.size() > o) tot += (double)c.sd.n / c.sd.chi[c.steps[o].first] / TR; tpw = (int)std::max(1.0, std::min(TR == 32 ? 32.0 : 8.0, tot / 4096.0)); if (TR == 32 && tpw >= 4) tpw &= ~3; }
-        std::vector<FiberItem> rg_items, rg32_items; double rg_tiles = 0, rg32_tiles = 0, rg_bytes = 0, rg_flops = 0;      // chi = 64 (32) legs: register-direct MFMA kernel
+        std::vector<FiberItem> rg_items, rg32_items; double rg_bytes = 0, rg_flops = 0;      // chi = 64 (32) legs: register-direct MFMA kernel
         for (size_t ci = 0; ci < chains.size(); ++ci) {
             Chain& c = chains[ci];
             if (c.steps.size() <= o) continue;
@@ -127,14 +121,12 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
             it.D = 1; it.PA = (int)c.sd.pre(j); it.K = c.sd.chi[j]; it.PB = (int)c.sd.post(j); it.Do = 1; it.No = it.K;
             if (std::is_same<T, float>::value && use_mfma() && rowgemm_covers(it) && (it.K != 64 || use_chi64())) {
                 rowgemm_tiles(it); it.want_norm = 0;
-                (it.K == 64 ? rg_items : rg32_items).push_back(it); (it.K == 64 ? rg_tiles : rg32_tiles) += (double)it.nta * it.ntb;
+                (it.K == 64 ? rg_items : rg32_items).push_back(it);
                 c.result = dst->p; nt[ci]++;
                 rg_bytes += 2.0 * c.sd.n * esz; rg_flops += 8.0 * c.sd.n * it.K;
                 continue;
             }
-            tile_params(it.PA, it.PB, TR, it.TA, it.TB, it.nta, it.ntb);
-            it.tpw = mf ? tpw : 1;
-            it.tile_begin = tiles; tiles += (it.nta * it.ntb + it.tpw - 1) / it.tpw; it.want_norm = 0;
+            it.want_norm = 0;
             items.push_back(it);
             c.result = dst->p; nt[ci]++;
             bytes += 2.0 * c.sd.n * esz; flops += 8.0 * c.sd.n * it.K;
@@ -143,9 +135,7 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
         for (int pass = 0; pass < 2; ++pass) {
             std::vector<FiberItem>& ri = pass ? rg32_items : rg_items;
             if (ri.empty()) continue;
-            const double nt = pass ? rg32_tiles : rg_tiles;
-            int tpw = (int)std::max(4.0, std::min(64.0, nt / 2048.0)); tpw &= ~3; int wgs = 0;
-            for (auto& it : ri) { it.tpw = tpw; it.tile_begin = wgs; wgs += (it.nta * it.ntb + tpw - 1) / tpw; }
+            const int wgs = plan_rowgemm(ri.data(), (int)ri.size(), 64);
             const FiberItem* d = upload(s, ri);
             ProfScope ps(s, cls, booked ? 0.0 : rg_bytes, booked ? 0.0 : rg_flops); booked = true;      // bytes / flops of both groups are booked on the first scope
             launch_mfma_rowgemm(s->stream, d, (int)ri.size(), wgs, 1, pass ? 32 : 64, nullptr);
@@ -155,15 +145,13 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
         bool f64mf = std::is_same<T, double>::value && use_mfma();
         for (auto& it : items) f64mf = f64mf && fiber_gemm_f64_covers(it);
         if (f64mf) {
-            double tot = 0; for (auto& it : items) { fiber_gemm_f64_tiles(it); tot += (double)it.nta * it.ntb; }
-            int tpw = (int)std::max(8.0, std::min(64.0, tot / 4096.0)); tpw &= ~3;
-            int wgs = 0;
-            for (auto& it : items) { it.tpw = tpw; it.tile_begin = wgs; wgs += (it.nta * it.ntb + tpw - 1) / tpw; }
+            const int wgs = plan_fiber_gemm_f64(items.data(), (int)items.size());
             const FiberItem* d = upload(s, items);
             ProfScope ps(s, cls, bytes, flops);
             launch_mfma_fiber_gemm_f64(s->stream, d, (int)items.size(), wgs, (int)KKmax, (int)KKmax, nullptr, false);
             continue;
         }
+        const int tiles = plan_fiber_gemm(items.data(), (int)items.size(), TR, mf ? tpw : 1);
         const FiberItem* d = upload(s, items);
         ProfScope ps(s, cls, bytes, flops);
         if (mf) launch_mfma_fiber_gemm(s->stream, d, (int)items.size(), tiles, (int)KKmax, (int)KKmax, nullptr);
@@ -269,27 +257,20 @@ template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& job
     const size_t esz = s->esz();
     size_t KKmax = 1;
     for (auto& j : jobs) { j.KK = (j.keep_site ? j.sd.d : 1) * (j.leg >= 0 ? j.sd.chi[j.leg] : 1); KKmax = std::max<size_t>(KKmax, j.KK); }
-    int TR = pick_TR(KKmax + 1, esz, 2);
+    constexpr bool f32 = std::is_same<T, float>::value, f32_acc64 = f32 && std::is_same<Acc, double>::value, acc32 = std::is_same<Acc, float>::value;
+    bool same = true, f64in = std::is_same<T, double>::value && use_mfma();
+    for (auto& j : jobs) { same = same && j.X == j.Y; f64in = f64in && j.M == nullptr && gram_f64in_covers(j.keep_site ? j.sd.d : 1, j.leg >= 0 ? j.sd.chi[j.leg] : 1); }
     // M set: the BP Gram absorbs the first row leg (f32 accumulation, mfma_gram32_fused_kernel); the gate-path Gram (f64 accumulation)
-    // absorbs the last gauge leg (mfma_gauge_gram64_kernel) -- a batch is one or the other
-    const bool gauge_fused = jobs[0].M != nullptr && std::is_same<T, float>::value && std::is_same<Acc, double>::value;
-    const bool fused = jobs[0].M != nullptr && !gauge_fused;
-    const bool mf = fused || (std::is_same<T, float>::value && std::is_same<Acc, float>::value && use_mfma() && KKmax <= (use_chi64() ? 64 : 32) && KKmax >= 8);
-    bool mf64 = std::is_same<T, float>::value && std::is_same<Acc, double>::value && use_mfma() && KKmax <= 64 && KKmax >= 16;
-    bool mf128 = std::is_same<T, float>::value && std::is_same<Acc, double>::value && use_mfma() && use_chi64() && KKmax <= 128 && KKmax > 64;
-    for (auto& j : jobs) { mf64 = mf64 && (j.X == j.Y); mf128 = mf128 && (j.X == j.Y); }
-    if (gauge_fused) { mf64 = true; mf128 = false; }
-    const bool gauge16 = gauge_fused && KKmax == 32;      // 16-dimensional legs: the wave-private kernel (units of one fiber of r, one partial per chunk)
-    if (mf || mf64 || mf128) TR = 64;
-    // ComplexF64 operands: tiles of 32 fibers through LDS, f64 matrix cores (kernels_f64.hip)
-    bool mf64in = std::is_same<T, double>::value && use_mfma() && jobs[0].M == nullptr;
-    for (auto& j : jobs) mf64in = mf64in && j.M == nullptr && gram_f64in_covers(j.keep_site ? j.sd.d : 1, j.leg >= 0 ? j.sd.chi[j.leg] : 1);
-    if (mf64in) TR = 32;
-    // workgroups per launch.  The f64 Grams of the gate path write one 64 KiB partial per (site, chunk, tile parity) which reduce_kernel reads back: 2048 chunks were
-    // 268 MB and 85-90 us per colour batch WHATEVER its size; 1024 (four workgroups per CU) halves that and costs the Gram pass nothing measurable
-    const int target = (std::is_same<T, float>::value && std::is_same<Acc, double>::value) ? 1024 : 2048;
-    int per_item = std::max(1, target / (int)jobs.size());
-    std::vector<GramItem> items; int chunks = 0; double bytes = 0, flops = 0;
+    // absorbs the last gauge leg (mfma_gauge_gram64_kernel; 16-dimensional legs: the wave-private mfma_gauge_gram32_kernel) -- a batch is one or the other
+    GramRoute r = GramRoute::Generic;
+    if (jobs[0].M) r = f32_acc64 ? (KKmax == 32 ? GramRoute::Gauge32 : GramRoute::Gauge64) : GramRoute::Fused32;
+    else if (f32_acc64 && use_mfma() && same && KKmax <= 64 && KKmax >= 16) r = GramRoute::F64x64;
+    else if (f32_acc64 && use_mfma() && use_chi64() && same && KKmax <= 128 && KKmax > 64) r = GramRoute::F64x128;
+    else if (f64in) r = GramRoute::F64In;          // ComplexF64 operands: tiles of 32 fibers through LDS, f64 matrix cores (kernels_f64.hip)
+    else if (f32 && acc32 && use_mfma() && KKmax <= (use_chi64() ? 64 : 32) && KKmax >= 8) r = KKmax <= 32 ? GramRoute::Mfma32 : GramRoute::Mfma64;
+    const bool gauge = r == GramRoute::Gauge32 || r == GramRoute::Gauge64;
+    const int TR = gram_tile_rows(r, KKmax, esz);
+    std::vector<GramItem> items; double bytes = 0, flops = 0; bool all_full = true;
     for (auto& j : jobs) {
         GramItem it{};
         it.X = j.X; it.Y = j.Y; it.M = j.M;
@@ -299,28 +280,22 @@ template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& job
             it.K = j.sd.chi[j.leg]; it.PB = (int)j.sd.post(j.leg);
         } else { it.D = j.sd.d; it.PA = (int)(j.sd.n / j.sd.d); it.K = 1; it.PB = 1; }
         tile_params(it.PA, it.PB, TR, it.TA, it.TB, it.nta, it.ntb);
-        if (gauge16) { it.nta = gauge_gram32_units(j.sd.z, j.sd.chi.data(), j.leg); it.ntb = 1; }
-        int ntiles = it.nta * it.ntb;
-        int nch = std::min(per_item, ntiles);
-        it.tiles_per_chunk = (ntiles + nch - 1) / nch;
-        it.nchunks = (ntiles + it.tiles_per_chunk - 1) / it.tiles_per_chunk;
-        // 32 x 32 f32 MFMA kernels: one partial per wave; f64 64 x 64 MFMA kernel: one per tile parity; the chi = 64 kernels: one per chunk
-        j.nchunks = (mf && (fused || KKmax <= 32)) ? 4 * it.nchunks : ((mf64 && !gauge16) ? 2 * it.nchunks : it.nchunks);
-        j.partial = dalloc(s, (size_t)j.nchunks * j.KK * j.KK * 2 * sizeof(Acc));
-        it.partial = j.partial->p; it.chunk_begin = chunks; chunks += it.nchunks;
+        if (r == GramRoute::Gauge32) { it.nta = gauge_gram32_units(j.sd.z, j.sd.chi.data(), j.leg); it.ntb = 1; }      // units of one fiber of r
         items.push_back(it);
-        bytes += (j.X == j.Y ? 1.0 : 2.0) * j.sd.n * esz; flops += gauge_fused ? 8.0 * j.sd.n * (j.KK + (gauge16 ? 16.0 : 32.0)) : 8.0 * j.sd.n * j.KK * (j.M ? 2.0 : 1.0);
+        all_full = all_full && j.KK == (r == GramRoute::F64x128 ? 128 : 64);
+        bytes += (j.X == j.Y ? 1.0 : 2.0) * j.sd.n * esz; flops += gauge ? 8.0 * j.sd.n * (j.KK + (r == GramRoute::Gauge32 ? 16.0 : 32.0)) : 8.0 * j.sd.n * j.KK * (j.M ? 2.0 : 1.0);
+    }
+    std::vector<int> npart(jobs.size());
+    const int chunks = plan_gram(items.data(), (int)items.size(), r, f32_acc64, 0, npart.data());
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        GramJob& j = jobs[q];
+        j.nchunks = npart[q];
+        j.partial = dalloc(s, (size_t)j.nchunks * j.KK * j.KK * 2 * sizeof(Acc));
+        items[q].partial = j.partial->p;
     }
     const GramItem* d = upload(s, items);
     ProfScope ps(s, cls, bytes, flops);
-    if (gauge16) launch_mfma_gauge_gram32(s->stream, d, (int)items.size(), chunks);
-    else if (gauge_fused) launch_mfma_gauge_gram64(s->stream, d, (int)items.size(), chunks);
-    else if (fused) launch_mfma_gram32_fused(s->stream, d, (int)items.size(), chunks);
-    else if (mf64) { bool all64 = true; for (auto& j : jobs) all64 = all64 && j.KK == 64; launch_mfma_gram64_f64(s->stream, d, (int)items.size(), chunks, (int)KKmax, all64); }
-    else if (mf128) { bool all128 = true; for (auto& j : jobs) all128 = all128 && j.KK == 128; launch_mfma_gram128_f64(s->stream, d, (int)items.size(), chunks, (int)KKmax, all128); }
-    else if (mf64in) launch_mfma_gram_f64in(s->stream, d, (int)items.size(), chunks);
-    else if (mf) { if (KKmax <= 32) launch_mfma_gram32(s->stream, d, (int)items.size(), chunks, (int)KKmax); else launch_mfma_gram64(s->stream, d, (int)items.size(), chunks, (int)KKmax); }
-    else launch_gram<T, Acc>(s->stream, d, (int)items.size(), chunks, TR, (int)KKmax);
+    launch_gram_route<T, Acc>(s->stream, r, d, (int)items.size(), chunks, TR, (int)KKmax, all_full);
 }
 
 template void run_chains<float>(State*, std::vector<Chain>&, int, int);

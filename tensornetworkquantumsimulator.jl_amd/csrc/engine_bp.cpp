@@ -719,8 +719,7 @@ template <class T> void bp_update_t(State* s, const tnqs_bp_opts* o, int* niter_
                 struct SplitGuard { State* s; hipStream_t m; bool on; ~SplitGuard() { s->stream = m; if (on) s->pool->set_defer(false); } } split_guard{s, main_stream, split_level};
                 auto on_side = [&](bool side) { if (split_level) { s->stream = side ? side_stream : main_stream; s->prof->chain = false; } };
                 if (!sh_pair.empty()) {
-                    const int spw = pair_spw(sh_pair_slices); int wgs = 0;
-                    for (auto& it : sh_pair) { it.spw = spw; it.slice_begin = wgs; wgs += pair_wgs(it.g.n0 * it.g.n1 * it.g.n2, spw); }
+                    const int wgs = plan_pair(sh_pair.data(), (int)sh_pair.size());
                     const PairItem* d = upload(s, sh_pair);
                     ProfScope ps(s, TNQS_PROF_BP_PAIR, 2.0 * sh_pair_slices * 16384.0 * esz, 2 * 8.0 * sh_pair_slices * 16384.0 * 32);
                     launch_mfma_pair(s->stream, d, (int)sh_pair.size(), wgs);
@@ -770,20 +769,10 @@ template <class T> void bp_update_t(State* s, const tnqs_bp_opts* o, int* niter_
                     on_side(false);
                 }
                 if (!sh_dbl.empty()) {
-                    // full slices per workgroup pair: the largest power of two that still gives >= 4 workgroups per CU; an item gets groups
-                    // of 16 workgroups (8 pairs), so powers of two avoid idle workgroups for the usual 2^k slices per site
-                    int spw = 16, wgs = 0;
-                    for (; spw > 1; spw >>= 1) {
-                        long tot = 0;
-                        for (auto& it : sh_dbl) { int np = (it.g.n0 * it.g.n1 * it.g.n2 + spw - 1) / spw; tot += 16 * ((np + 7) / 8); }      // (counted in half-slice workgroups for both kernels)
-                        if (tot >= 1024) break;
-                    }
+                    std::vector<int> nwg(sh_dbl.size()); const int wgs = plan_pair_gram2(sh_dbl.data(), (int)sh_dbl.size(), nwg.data());
                     for (size_t q = 0; q < sh_dbl.size(); ++q) {
                         PairGram2Item& it = sh_dbl[q]; GramJob& jy = jobs[sh_dbl_chain[q].first]; GramJob& jx = jobs[sh_dbl_chain[q].second];
-                        const int npairs = (it.g.n0 * it.g.n1 * it.g.n2 + spw - 1) / spw;     // workgroup pairs (one per half), in groups of 8 pairs
-                        const int nwg = pair_gram2_group() * ((npairs + 7) / 8);
-                        it.spw = spw; it.wg_begin = wgs; wgs += nwg;
-                        jy.nchunks = jx.nchunks = nwg; jy.KK = jx.KK = 32;             // one partial per workgroup
+                        jy.nchunks = jx.nchunks = nwg[q]; jy.KK = jx.KK = 32;
                         jy.partial = dalloc(s, (size_t)jy.nchunks * 1024 * esz); jx.partial = dalloc(s, (size_t)jx.nchunks * 1024 * esz);
                         it.partial_y = jy.partial->p; it.partial_x = jx.partial->p;
                     }
@@ -793,13 +782,9 @@ template <class T> void bp_update_t(State* s, const tnqs_bp_opts* o, int* niter_
                 }
                 for (int q : g16_single) { g16[q].X = chains[g16_chain[q].first].result; is_shared[g16_chain[q].first] = 1; }
                 if (!g16.empty()) {
-                    double tot = 0; for (auto& it : g16) tot += it.g.nslices();
-                    int spw = pair_gram2x16_slices_at_a_time(); while (spw < 128 && tot / (2 * spw) >= 2048.0) spw *= 2;       // a multiple of the slices a workgroup walks at a time (waves / 2: half slices)
-                    int wgs = 0; double by = 0, fl = 0;
+                    std::vector<int> nwgs(g16.size()); const int wgs = plan_pair_gram2x16(g16.data(), (int)g16.size(), nwgs.data()); double by = 0, fl = 0;
                     for (size_t q = 0; q < g16.size(); ++q) {
-                        PairGram2x16Item& it = g16[q]; GramJob& jy = jobs[g16_chain[q].first];
-                        const int nwg = (it.g.nslices() + spw - 1) / spw;
-                        it.spw = spw; it.wg_begin = wgs; wgs += nwg;
+                        PairGram2x16Item& it = g16[q]; GramJob& jy = jobs[g16_chain[q].first]; const int nwg = nwgs[q];
                         jy.nchunks = nwg; jy.KK = 16; jy.partial = dalloc(s, (size_t)nwg * 256 * esz); it.partial_y = jy.partial->p;
                         if (g16_chain[q].second >= 0) {
                             GramJob& jx = jobs[g16_chain[q].second];
@@ -819,27 +804,23 @@ template <class T> void bp_update_t(State* s, const tnqs_bp_opts* o, int* niter_
                 if (!sh_gram.empty() && mfma_use_x3()) {
                     // the bf16 kernel in its one-message form (round 5): half-slice workgroups in groups of 16, one partial per workgroup.  These launches are what a
                     // sweep in the reference's forest-cover order consists of (a handful of messages per dependency level)
-                    double tot = 0; for (auto& it : sh_gram) tot += (double)(it.g.n0 * it.g.n1 * it.g.n2);
-                    int spw = 16; while (spw > 1 && 2.0 * tot / spw < 1024.0) spw >>= 1;
-                    std::vector<PairGram2Item> one(sh_gram.size()); int wgs = 0;
+                    std::vector<PairGram2Item> one(sh_gram.size()); std::vector<int> nwg(sh_gram.size());
+                    for (size_t q = 0; q < sh_gram.size(); ++q) { const PairGramItem& a = sh_gram[q]; one[q].X = a.X; one[q].Y = a.Y; one[q].Mx = a.M; one[q].g = a.g; }
+                    const int wgs = plan_x3_pair_gram1(one.data(), (int)one.size(), nwg.data());
                     for (size_t q = 0; q < sh_gram.size(); ++q) {
-                        const PairGramItem& a = sh_gram[q]; PairGram2Item& it = one[q]; GramJob& j = jobs[sh_chain[q]];
-                        const int np = (a.g.n0 * a.g.n1 * a.g.n2 + spw - 1) / spw, nwg = 16 * ((np + 7) / 8);
-                        it.X = a.X; it.Y = a.Y; it.Mx = a.M; it.My = nullptr; it.g = a.g; it.spw = spw; it.wg_begin = wgs; wgs += nwg;
-                        j.nchunks = nwg; j.KK = 32; j.partial = dalloc(s, (size_t)j.nchunks * 1024 * esz);
-                        it.partial_y = j.partial->p; it.partial_x = nullptr;
+                        GramJob& j = jobs[sh_chain[q]];
+                        j.nchunks = nwg[q]; j.KK = 32; j.partial = dalloc(s, (size_t)j.nchunks * 1024 * esz);
+                        one[q].partial_y = j.partial->p;
                     }
                     const PairGram2Item* d = upload(s, one);
                     ProfScope ps(s, TNQS_PROF_BP_PAIRGRAM, 2.0 * sh_gram_slices * 16384.0 * esz, 2 * 8.0 * sh_gram_slices * 16384.0 * 32);
                     launch_x3_pair_gram1(s->stream, d, (int)one.size(), wgs);
                 } else if (!sh_gram.empty()) {
-                    int spw = (int)std::max(4.0, std::min(16.0, sh_gram_slices / 2048.0)); int wgs = 0;
+                    std::vector<int> nwg(sh_gram.size()); const int wgs = plan_pair_gram(sh_gram.data(), (int)sh_gram.size(), nwg.data());
                     for (size_t q = 0; q < sh_gram.size(); ++q) {
-                        PairGramItem& it = sh_gram[q]; GramJob& j = jobs[sh_chain[q]];
-                        int nwg = (it.g.n0 * it.g.n1 * it.g.n2 + spw - 1) / spw;
-                        it.spw = spw; it.wg_begin = wgs; wgs += nwg;
-                        j.nchunks = nwg; j.KK = 32; j.partial = dalloc(s, (size_t)j.nchunks * 1024 * esz);
-                        it.partial = j.partial->p;
+                        GramJob& j = jobs[sh_chain[q]];
+                        j.nchunks = nwg[q]; j.KK = 32; j.partial = dalloc(s, (size_t)j.nchunks * 1024 * esz);
+                        sh_gram[q].partial = j.partial->p;
                     }
                     const PairGramItem* d = upload(s, sh_gram);
                     ProfScope ps(s, TNQS_PROF_BP_PAIRGRAM, 2.0 * sh_gram_slices * 16384.0 * esz, 2 * 8.0 * sh_gram_slices * 16384.0 * 32);

@@ -10,6 +10,7 @@ static struct HostTimerReport { ~HostTimerReport() { if (envflag("TNQS_HOST_TIMI
 void hipchk(hipError_t e, const char* what) {
     if (e != hipSuccess) throw Err(TNQS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+void throw_unsupported(const char* what) { throw Err(TNQS_ERR_UNSUPPORTED, what); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // pool

@@ -146,7 +146,7 @@ template <class T> static void apply_one_site_batch(State* s, const std::vector<
         }
     }
     std::vector<FiberItem> items; std::vector<int> verts, tb, nt; std::vector<Buf> outs; std::vector<size_t> ne;
-    int tiles = 0; size_t KKmax = 1; double bytes = 0, flops = 0;
+    size_t KKmax = 1; double bytes = 0, flops = 0;
     for (auto& g1 : gates) KKmax = std::max<size_t>(KKmax, s->d[g1.v]);
     const int TR = pick_TR(KKmax, esz, 1);
     std::vector<T> hx;       // X[kk + d*nn] = G[nn, kk]  (out[s'] = sum_s G[s', s] psi[s], simple_update.jl:27)
@@ -167,15 +167,15 @@ template <class T> static void apply_one_site_batch(State* s, const std::vector<
         SD sd = site_dims(s, g1.v);
         FiberItem it{}; Buf out = dalloc(s, sd.n * esz);
         it.in = s->site[g1.v]->p; it.out = out->p; it.X = dxp + xoff[gi] * sizeof(T);
-        it.D = sd.d; it.PA = (int)(sd.n / sd.d); it.K = 1; it.PB = 1; it.Do = sd.d; it.No = 1;
-        tile_params(it.PA, it.PB, TR, it.TA, it.TB, it.nta, it.ntb);
-        it.tpw = 1; it.tile_begin = tiles; it.want_norm = normalize ? 1 : 0;
-        verts.push_back(g1.v); outs.push_back(out); ne.push_back(sd.n); tb.push_back(tiles); nt.push_back(it.nta * it.ntb);
-        tiles += it.nta * it.ntb; items.push_back(it);
+        it.D = sd.d; it.PA = (int)(sd.n / sd.d); it.K = 1; it.PB = 1; it.Do = sd.d; it.No = 1; it.want_norm = normalize ? 1 : 0;
+        verts.push_back(g1.v); outs.push_back(out); ne.push_back(sd.n); items.push_back(it);
         bytes += 2.0 * sd.n * esz; flops += 8.0 * sd.n * sd.d;
         ++gi;
     }
     if (items.empty()) return;
+    nt.resize(items.size());
+    const int tiles = plan_fiber_gemm(items.data(), (int)items.size(), TR, 1, nt.data());
+    for (auto& it : items) tb.push_back(it.tile_begin);
     Buf np = dalloc(s, std::max(1, tiles) * sizeof(double));
     const FiberItem* d = upload(s, items);
     { ProfScope ps(s, TNQS_PROF_GATE_APPLY, bytes, flops);
@@ -615,11 +615,12 @@ template <class T> static void apply_two_site_batch(State* s, const std::vector<
                 P.rby += (double)(j.sd.n + nout) * esz; P.rfl += 8.0 * j.sd.n * j.sd.d * chin; P.via[q] = 1; if (skip) (*skip)[q] = 1;
             }
         for (int kk : {64, 32}) {
-            RgGroup G; G.kk = kk; double st = 0;
-            for (size_t q = 0; q < rg.size(); ++q) if (rg[q].K == kk) { G.sub.push_back(rg[q]); G.sv.push_back(rverts[q]); G.so.push_back(routs[q]); G.sn.push_back(rne[q]); st += (double)rg[q].nta * rg[q].ntb; }
+            RgGroup G; G.kk = kk;
+            for (size_t q = 0; q < rg.size(); ++q) if (rg[q].K == kk) { G.sub.push_back(rg[q]); G.sv.push_back(rverts[q]); G.so.push_back(routs[q]); G.sn.push_back(rne[q]); }
             if (G.sub.empty()) continue;
-            int tpw = (int)std::max(4.0, std::min(32.0, st / 2048.0)); tpw &= ~3;
-            for (auto& it : G.sub) { const int nwg = (it.nta * it.ntb + tpw - 1) / tpw; it.tpw = tpw; it.tile_begin = G.wgs; G.stb.push_back(G.wgs); G.snt.push_back(nwg); G.wgs += nwg; }
+            G.snt.resize(G.sub.size());
+            G.wgs = tnqs::plan_rowgemm(G.sub.data(), (int)G.sub.size(), 32, G.snt.data());
+            for (auto& it : G.sub) G.stb.push_back(it.tile_begin);
             G.npr = dalloc(s, (size_t)G.wgs * sizeof(double));
             G.d = upload(s, G.sub);
             P.groups.push_back(std::move(G));
@@ -827,7 +828,7 @@ template <class T> static void apply_two_site_batch(State* s, const std::vector<
                 if (sharded || !rs.empty()) {
                     const size_t m = rs.size();
                     std::vector<Buf> X1(m), Q1(m), G2(m), V2(m), GVn(m), GWn(m); Buf d_rk = dalloc(s, std::max<size_t>(1, m) * sizeof(int));
-                    std::vector<Qr2RinvItem> ri; std::vector<FiberItem> fi; std::vector<GramJob> gj; std::vector<size_t> own_k; size_t KKmax = 1; int tiles = 0;
+                    std::vector<Qr2RinvItem> ri; std::vector<FiberItem> fi; std::vector<GramJob> gj; std::vector<size_t> own_k; size_t KKmax = 1;
                     for (size_t k = 0; k < m; ++k) {
                         const size_t i = rs[k]; const int q = rq[k]; const bool second = (i & 1) != 0; const int n = nof(i); const size_t nn = (size_t)n * n;
                         X1[k] = dalloc(s, nn * 16); V2[k] = dalloc(s, nn * 16); GVn[k] = dalloc(s, nn * 16); GWn[k] = dalloc(s, nn * 16);
@@ -839,12 +840,12 @@ template <class T> static void apply_two_site_batch(State* s, const std::vector<
                         const size_t i = rs[k]; const SiteJob& j = sj[i]; const int chi = j.sd.chi[j.bleg];
                         FiberItem it{}; it.in = gauged_of[i]; it.out = Q1[k]->p; it.X = X1[k]->p;
                         it.D = j.sd.d; it.PA = (int)(j.sd.pre(j.bleg) / j.sd.d); it.K = chi; it.PB = (int)j.sd.post(j.bleg); it.Do = j.sd.d; it.No = chi;
-                        tile_params(it.PA, it.PB, TR, it.TA, it.TB, it.nta, it.ntb); it.tpw = 1; it.tile_begin = tiles; it.want_norm = 0;
-                        tiles += it.nta * it.ntb; fi.push_back(it);
+                        fi.push_back(it);
                         GramJob g2{}; g2.X = Q1[k]->p; g2.Y = Q1[k]->p; g2.sd = j.sd; g2.leg = j.bleg; g2.keep_site = true; gj.push_back(g2);
                     }
                     if (m) { const Qr2RinvItem* d = upload(s, ri); ProfScope ps(s, TNQS_PROF_SMALL, 0, 0); launch_qr2_rinv(s->stream, d, (int)m); }
                     if (!fi.empty()) {
+                        const int tiles = plan_fiber_gemm(fi.data(), (int)fi.size(), TR, 1);
                         Buf np = dalloc(s, std::max(1, tiles) * sizeof(double)); const FiberItem* d = upload(s, fi);
                         { ProfScope ps(s, TNQS_PROF_GATE_APPLY, 0, 0); launch_fiber_gemm<T>(s->stream, d, (int)fi.size(), tiles, TR, (int)KKmax, reinterpret_cast<double*>(np->p)); }
                         s->keepalive.push_back(np);
@@ -977,7 +978,7 @@ template <class T> static void apply_two_site_batch(State* s, const std::vector<
     run_chains<T>(s, pch, TNQS_PROF_GATE_MODEPROD);
     if (!own_idx.empty()) {
         std::vector<FiberItem> items; std::vector<int> verts, tb, nt; std::vector<Buf> outs; std::vector<size_t> ne;
-        int tiles = 0; size_t KKmax = 1, NNmax = 1; double bytes = 0, flops = 0;
+        size_t KKmax = 1, NNmax = 1; double bytes = 0, flops = 0;
         for (size_t q = 0; q < own_idx.size(); ++q) {
             size_t i = own_idx[q];
             KKmax = std::max<size_t>(KKmax, (size_t)sj[i].sd.d * sj[i].sd.chi[sj[i].bleg]);
@@ -1015,15 +1016,15 @@ template <class T> static void apply_two_site_batch(State* s, const std::vector<
             FiberItem it{}; Buf out = dalloc(s, nout * esz);
             it.in = pch[q].result; it.out = out->p; it.X = (i & 1) ? ws[gi].X2->p : ws[gi].X1->p;
             it.D = j.sd.d; it.PA = (int)(pre / j.sd.d); it.K = chi; it.PB = (int)post; it.Do = j.sd.d; it.No = chin;
-            tile_params(it.PA, it.PB, TR, it.TA, it.TB, it.nta, it.ntb);
-            it.tpw = mf ? (TR == 32 ? 16 : 4) : 1;
-            if (f64mf) { fiber_gemm_f64_tiles(it); it.tpw = 32; }      // ComplexF64 epilogue on the f64 matrix cores: tiles of 16 fibers, 32 per workgroup
-            const int nwg = (it.nta * it.ntb + it.tpw - 1) / it.tpw;
-            it.tile_begin = tiles; it.want_norm = ao.normalize_tensors ? 1 : 0;
-            verts.push_back(j.v); outs.push_back(out); ne.push_back(nout); tb.push_back(tiles); nt.push_back(nwg);
-            tiles += nwg; items.push_back(it);
+            it.want_norm = ao.normalize_tensors ? 1 : 0;
+            verts.push_back(j.v); outs.push_back(out); ne.push_back(nout); items.push_back(it);
             bytes += (double)(j.sd.n + nout) * esz; flops += 8.0 * j.sd.n * j.sd.d * chin;
         }
+        // ComplexF64 on the f64 matrix cores: tiles of 16 fibers, 32 per workgroup
+        nt.resize(items.size());
+        const int tiles = f64mf ? plan_fiber_gemm_f64(items.data(), (int)items.size(), nt.data(), 32)
+                                : plan_fiber_gemm(items.data(), (int)items.size(), TR, mf ? (TR == 32 ? 16 : 4) : 1, nt.data());
+        for (auto& it : items) tb.push_back(it.tile_begin);
         Buf np = dalloc(s, std::max(1, tiles) * sizeof(double));
         const FiberItem* d = upload(s, items);
         if (!items.empty())

@@ -231,14 +231,6 @@ inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 void exchange(State* s, size_t bytes_per_rank);                       // sharding.cpp
 void check_exchange(const State* s, size_t bytes_per_rank);           // call BEFORE enqueuing anything that writes into s->exch
 
-inline int pick_TR(size_t KK, size_t esz, int copies) {
-    for (int tr : {64, 32, 16, 8, 4}) if (KK * tr * esz * copies <= 64 * 1024) return tr;
-    throw Err(TNQS_ERR_UNSUPPORTED, "bond dimension too large for the fiber-tile kernels (d*chi*16*elemsize must fit 64 KiB of LDS)");
-}
-inline void tile_params(size_t PA, size_t PB, int TR, int& TA, int& TB, int& nta, int& ntb) {
-    TA = (int)std::min<size_t>(PA, TR); TB = std::max(1, TR / TA); TB = (int)std::min<size_t>(TB, PB);
-    nta = (int)((PA + TA - 1) / TA); ntb = (int)((PB + TB - 1) / TB);
-}
 
 
 // a chain = one site tensor pushed through several mode products (leg j with matrix X_j, chi_j x chi_j)

@@ -188,11 +188,10 @@ template <class T> static void region_contract(State* s, int nr, const int32_t* 
                     FiberItem it{}; it.in = ket; it.out = opbuf->p; it.X = dx;
                     it.D = d; it.PA = (int)(sd.n / d); it.K = 1; it.PB = 1; it.Do = d; it.No = 1;
                     const int TR = pick_TR(d, esz, 1);
-                    tile_params(it.PA, it.PB, TR, it.TA, it.TB, it.nta, it.ntb);
-                    it.tpw = 1; it.tile_begin = 0; it.want_norm = 0;
                     std::vector<FiberItem> items{it};
+                    const int tiles = plan_fiber_gemm(items.data(), 1, TR, 1);
                     const FiberItem* dI = upload(s, items);
-                    launch_fiber_gemm<T>(s->stream, dI, 1, it.nta * it.ntb, TR, d, nullptr);
+                    launch_fiber_gemm<T>(s->stream, dI, 1, tiles, TR, d, nullptr);
                     ket = opbuf->p;
                 }
             }

@@ -228,6 +228,37 @@ template void launch_gram<float, float>(hipStream_t, const GramItem*, int, int, 
 template void launch_gram<float, double>(hipStream_t, const GramItem*, int, int, int, int);
 template void launch_gram<double, double>(hipStream_t, const GramItem*, int, int, int, int);
 
+int gram_tile_rows(GramRoute r, size_t KKmax, size_t esz) {
+    const int tr = pick_TR(KKmax + 1, esz, 2);          // the generic kernel: two operand blocks in LDS
+    return r == GramRoute::Generic ? tr : r == GramRoute::F64In ? 32 : 64;
+}
+// The f64 Grams of f32 data write one 64 KiB partial per (site, chunk, tile parity) which reduce_kernel reads back: 2048 chunks per launch were 268 MB and
+// 85-90 us per colour batch of the gate path WHATEVER its size; 1024 (four workgroups per CU) halves that and costs the Gram pass nothing measurable.
+// Partials per chunk: one per wave on the 32 x 32 f32 matrix-core kernels, one per tile parity on the f64 64 x 64 one, one otherwise.
+int plan_gram(GramItem* it, int n, GramRoute r, bool f32_acc64, int max_chunks, int* npart) {
+    if (max_chunks <= 0) max_chunks = std::max(1, (f32_acc64 ? 1024 : 2048) / n);
+    const int per_chunk = (r == GramRoute::Mfma32 || r == GramRoute::Fused32) ? 4 : (r == GramRoute::F64x64 || r == GramRoute::Gauge64) ? 2 : 1;
+    const int chunks = lay_out(it, n, &GramItem::chunk_begin, npart, [&](GramItem& g) {
+        const int ntiles = g.nta * g.ntb, nch = std::min(max_chunks, ntiles);
+        g.tiles_per_chunk = (ntiles + nch - 1) / nch; g.nchunks = (ntiles + g.tiles_per_chunk - 1) / g.tiles_per_chunk;
+        return g.nchunks; });
+    if (npart) for (int i = 0; i < n; ++i) npart[i] *= per_chunk;
+    return chunks;
+}
+template <class T, class Acc>
+void launch_gram_route(hipStream_t s, GramRoute r, const GramItem* d, int n, int chunks, int TR, int KKmax, bool all_full) {
+    switch (r) {
+    case GramRoute::Gauge32: launch_mfma_gauge_gram32(s, d, n, chunks); break; case GramRoute::Gauge64: launch_mfma_gauge_gram64(s, d, n, chunks); break;
+    case GramRoute::F64x64: launch_mfma_gram64_f64(s, d, n, chunks, KKmax, all_full); break; case GramRoute::F64x128: launch_mfma_gram128_f64(s, d, n, chunks, KKmax, all_full); break;
+    case GramRoute::Mfma32: launch_mfma_gram32(s, d, n, chunks, KKmax); break; case GramRoute::Mfma64: launch_mfma_gram64(s, d, n, chunks, KKmax); break;
+    case GramRoute::Fused32: launch_mfma_gram32_fused(s, d, n, chunks); break; case GramRoute::F64In: launch_mfma_gram_f64in(s, d, n, chunks); break;
+    case GramRoute::Generic: launch_gram<T, Acc>(s, d, n, chunks, TR, KKmax); break;
+    }
+}
+template void launch_gram_route<float, float>(hipStream_t, GramRoute, const GramItem*, int, int, int, int, bool);
+template void launch_gram_route<float, double>(hipStream_t, GramRoute, const GramItem*, int, int, int, int, bool);
+template void launch_gram_route<double, double>(hipStream_t, GramRoute, const GramItem*, int, int, int, int, bool);
+
 // ------------------------------------------------------------------------------------------------------------
 // reduce partials
 // ------------------------------------------------------------------------------------------------------------

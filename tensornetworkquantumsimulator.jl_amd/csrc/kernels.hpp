@@ -4,6 +4,7 @@
 // contracted / kept, (s) the site index when it takes part (D = d) or folded into a (D = 1), and (a, b) the
 // remaining indices before / after leg k.  No explicit transposes are ever materialised.
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 #include <cstddef>
@@ -186,11 +187,43 @@ void launch_record_pack(hipStream_t s, const RecordPackItem* d_items, int nitems
 void launch_header_gather(hipStream_t s, const void* const* d_srcs, int n, double* d_out);
 struct PermItem { const void* in; void* out; int ndim; int dims_out[8]; long long stride_in[8]; size_t n; };
 
+// ---- workgroup layout of a batch (host): the plan_* function next to a launcher sets spw / tpw and the *_begin offsets of items whose geometry
+// is set, writes item i's workgroups to nwg[i] (may be null; for the Gram-type kernels also its partials, per message) and returns the launch's
+// total.  spw / tpw > 0 forces that value (debug entry points); otherwise the kernel's rule for the batch applies.
+template <class Item, class Count> int lay_out(Item* it, int n, int Item::*begin, int* nwg, Count count) {
+    int w = 0; for (int i = 0; i < n; ++i) { const int c = count(it[i]); it[i].*begin = w; w += c; if (nwg) nwg[i] = c; } return w;
+}
+[[noreturn]] void throw_unsupported(const char* what);      // engine_core.cpp: the engine's TNQS_ERR_UNSUPPORTED error
+// fiber tiles of the generic kernels: TR fibers per tile, the most that keeps `copies` operand blocks of KK x TR within 64 KiB of LDS
+inline int pick_TR(size_t KK, size_t esz, int copies) {
+    for (int tr : {64, 32, 16, 8, 4}) if (KK * tr * esz * copies <= 64 * 1024) return tr;
+    throw_unsupported("bond dimension too large for the fiber-tile kernels (d*chi*16*elemsize must fit 64 KiB of LDS)");
+}
+inline void tile_params(size_t PA, size_t PB, int TR, int& TA, int& TB, int& nta, int& ntb) {
+    TA = (int)std::min<size_t>(PA, TR); TB = std::max(1, TR / TA); TB = (int)std::min<size_t>(TB, PB);
+    nta = (int)((PA + TA - 1) / TA); ntb = (int)((PB + TB - 1) / TB);
+}
+
 // ---- launchers (T = float or double; data are complex<T>) ------------------------------------------------------
 template <class T> void launch_fiber_gemm(hipStream_t s, const FiberItem* d_items, int nitems, int total_tiles,
                                           int TR, int KKmax, double* d_norm_partials);
+// tile grid (tile_params) and layout of a batch of the generic or the f32-MFMA fiber GEMM: tpw tiles per workgroup (1 on the generic kernel)
+inline int plan_fiber_gemm(FiberItem* it, int n, int TR, int tpw, int* nwg = nullptr) {
+    for (int i = 0; i < n; ++i) tile_params(it[i].PA, it[i].PB, TR, it[i].TA, it[i].TB, it[i].nta, it[i].ntb);
+    return lay_out(it, n, &FiberItem::tile_begin, nwg, [&](FiberItem& f) { f.tpw = tpw; return (f.nta * f.ntb + tpw - 1) / tpw; });
+}
 template <class T, class Acc> void launch_gram(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks,
                                                int TR, int KKmax);
+// the Gram kernel of a batch, decided once by the caller: generic tiled; f32 matrix cores up to 32 x 32 / 64 x 64; message fused on the first
+// row leg (32 x 32); f64 accumulation on the f64 matrix cores, 64 x 64 / 128 x 128; ComplexF64 operands; gauge leg fused, 32- / 16-dimensional legs
+enum class GramRoute { Generic, Mfma32, Mfma64, Fused32, F64x64, F64x128, F64In, Gauge64, Gauge32 };
+int gram_tile_rows(GramRoute r, size_t KKmax, size_t esz);       // TR: fibers per tile of the route
+// chunks of a batch whose tiles are set: min(max_chunks, tiles) per item (max_chunks <= 0: the engine's target of workgroups per launch; f32_acc64:
+// f32 data accumulated in f64); npart[i]: the partials item i leaves; returns the launch's chunks
+int plan_gram(GramItem* it, int n, GramRoute r, bool f32_acc64, int max_chunks, int* npart);
+// all_full: every item has D K = 64 (F64x64) / 128 (F64x128)
+template <class T, class Acc> void launch_gram_route(hipStream_t s, GramRoute r, const GramItem* d_items, int nitems, int total_chunks, int TR, int KKmax,
+                                                     bool all_full = false);
 template <class Acc, class Out> void launch_reduce(hipStream_t s, const ReduceItem* d_items, int nitems, int total_elems);
 template <class T> void launch_msg_finalize(hipStream_t s, const MsgFinalItem* d_items, int nitems);
 struct RecoverItem { const void* A0; const void* A; void* V; int m; int n; int nu; const int* dyn; int dm, dn; int pre; /* JacobiItem::pre of the same gate: skip when theta_pre_takes */ };   // dyn: as in JacobiItem   // V (n x nu) = A0^dagger (U Sigma) Sigma^-2; A0: m x n, U Sigma: m x nu
@@ -220,9 +253,11 @@ struct CholItem { const void* G; void* L; void* Winv; int n; int* fail; double t
 struct TallSvdItem { const void* A; void* G; const void* L; void* R0; void* Rrot; int m, n; };
 struct SmallGemmItem { const void* A; const void* B; void* C; int m, n, k; };           // C (m x n) = A (m x k) B (k x n), ComplexF32
 struct CopyItem { const void* src; void* dst; size_t n16; };                             // n16 16-byte words
-// register-direct MFMA fiber GEMM for chi = 64 sites (kernels_chi64.hip): rowgemm_tiles() sets the tile grid of an item
+// register-direct MFMA fiber GEMM for chi = 64 sites (kernels_chi64.hip): rowgemm_tiles() sets the tile grid of an item, plan_rowgemm() the layout
+// of a batch (tpw rule capped at `cap`)
 bool rowgemm_covers(const FiberItem& it);
 void rowgemm_tiles(FiberItem& it);
+int plan_rowgemm(FiberItem* it, int n, int cap, int* nwg = nullptr, int tpw = 0);
 void launch_mfma_rowgemm(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, int D, int K, double* d_norm_partials);   // all items: the same K and D
 bool launch_x3_gram64(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks, int KKmax);                               // kernels_x3.hip: mfma_gram64_kernel on the bf16 matrix cores
 void launch_x3_rowgemm64(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, int D, double* d_norm_partials);              // kernels_x3.hip: D K = 64 on the bf16 matrix cores
@@ -257,34 +292,6 @@ void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int n
 //  * leg 0 involved (only the site index below it): the 2 site components are the contiguous pair and the 8 pairs step
 //    along another leg a (cstr = pre(a)); then consecutive plane rows ix of leg 0 are contiguous (8 x 16 B = 128-byte runs)
 struct PairGeom { long long cstr, sx, sy, t0, t1, t2; int n0, n1, n2; };
-// geometry for the legs (lx -> plane index ix, ly -> plane index iy) of a site tensor [d][chi_0]..[chi_{z-1}];
-// false when the pair kernels do not cover the shape (both legs must have dimension 32)
-inline bool pair_geometry(int d, int z, const int* chi, int lx, int ly, PairGeom& g) {
-    if (lx == ly || lx < 0 || ly < 0 || lx >= z || ly >= z || chi[lx] != 32 || chi[ly] != 32) return false;
-    auto pre = [&](int j) { long long p = d; for (int i = 0; i < j; ++i) p *= chi[i]; return p; };
-    const int p = lx < ly ? lx : ly, q = lx < ly ? ly : lx;
-    g.sx = pre(lx); g.sy = pre(ly);
-    if (pre(p) % 16 == 0) {            // 16 contiguous companions below the lower leg
-        g.cstr = 2; g.n0 = (int)(pre(p) / 16); g.t0 = 16;
-        g.n1 = (int)(pre(q) / (pre(p) * 32)); g.t1 = pre(p) * 32;
-        long long post = 1; for (int i = q + 1; i < z; ++i) post *= chi[i];
-        g.n2 = (int)post; g.t2 = pre(q) * 32;
-        return true;
-    }
-    if (pre(p) != 2) return false;     // leg 0 above a 2-dimensional site index: companions = (s) x 8 values of another leg
-    int a = -1;
-    for (int i = 0; i < z; ++i) if (i != p && i != q && chi[i] % 8 == 0) { a = i; break; }
-    if (a < 0) return false;
-    g.cstr = pre(a); g.n0 = chi[a] / 8; g.t0 = 8 * pre(a);
-    g.n1 = 1; g.t1 = 0; g.n2 = 1; g.t2 = 0;
-    int k = 0;
-    for (int i = 0; i < z; ++i) {
-        if (i == p || i == q || i == a) continue;
-        if (k == 0) { g.n1 = chi[i]; g.t1 = pre(i); } else if (k == 1) { g.n2 = chi[i]; g.t2 = pre(i); } else return false;
-        ++k;
-    }
-    return true;
-}
 struct PairItem {         // out = in x_x Mx x_y My for two 32-dimensional legs
     const void* in; void* out; const void* Mx; const void* My;
     PairGeom g;
@@ -292,7 +299,7 @@ struct PairItem {         // out = in x_x Mx x_y My for two 32-dimensional legs
     int spw;              // slices (16 companions x 32 x 32) walked by one PAIR of workgroups (each takes 8 of the 16 companions)
 };
 struct PairGramItem {     // partial[b,b'] = sum_{rest, jx} (sum_ix X[.. ix .. b ..] M[ix, jx]) conj(Y[.. jx .. b' ..]);  x = absorbed leg, y = kept leg
-    const void* X; const void* Y; const void* M; void* partial;   // 8 partials (one per wave) per workgroup, 32*32 complex each
+    const void* X; const void* Y; const void* M; void* partial;   // one partial per workgroup, 32*32 complex each
     PairGeom g;
     int wg_begin;         // first workgroup id of this item
     int spw;              // slices per workgroup
@@ -330,6 +337,14 @@ inline bool plane_geometry(int d, int z, const int* chi, int lx, int ly, int DIM
     }
     return true;
 }
+// PairGeom for the legs (lx -> plane index ix, ly -> plane index iy) of a site tensor [d][chi_0]..[chi_{z-1}]: plane_geometry with at most two
+// slice counters (no third leg besides the plane and the companions: t3 == 0); false when the pair kernels do not cover the shape
+inline bool pair_geometry(int d, int z, const int* chi, int lx, int ly, PairGeom& g) {
+    PlaneGeom p;
+    if (!plane_geometry(d, z, chi, lx, ly, 32, p) || p.t3 != 0) return false;
+    g = PairGeom{p.cstr, p.sx, p.sy, p.t0, p.t1, p.t2, p.n0, p.n1, p.n2};
+    return true;
+}
 struct Pair16Item {       // out = in x_x Mx x_y My for two 16-dimensional legs
     const void* in; void* out; const void* Mx; const void* My;
     PlaneGeom g;
@@ -343,8 +358,11 @@ struct PairGram2x16Item { const void* X; const void* Y; const void* Mx; const vo
 // two kernels: a wave pair sharing every 128-byte line (planes that contain leg 0: a wave's lanes read 256 contiguous bytes anyway) and one
 // wave owning whole lines (the 16 companions are 16 consecutive elements); a launch holds items of one kind
 bool pair16_whole_lines(const PlaneGeom& g);
+// spw for the whole batch, offsets counted per kind: wgs[k] = the workgroups of the launch of kind k (1: whole lines)
+void plan_pair16(Pair16Item* it, int n, int wgs[2], int spw = 0);
 void launch_mfma_pair16(hipStream_t s, const Pair16Item* d_items, int nitems, int total_wgs, bool whole_lines);
 int pair_gram2x16_slices_at_a_time();
+int plan_pair_gram2x16(PairGram2x16Item* it, int n, int* nwg = nullptr, int spw = 0);
 void launch_mfma_pair_gram2x16(hipStream_t s, const PairGram2x16Item* d_items, int nitems, int total_wgs);
 
 // ---- MFMA fast paths (ComplexF32 only; kernels_mfma.hip) -----------------------------------------------------------
@@ -361,7 +379,7 @@ bool launch_mfma_gram64_f64(hipStream_t s, const GramItem* d_items, int nitems, 
 // tiles and partial layout as launch_mfma_gram64_f64 (2 partials per chunk)
 // ComplexF64 mode products on the f64 matrix cores (kernels_f64.hip): one wave per tile of 16 fibers, FiberItem::tpw tiles per wave-quartet
 bool fiber_gemm_f64_covers(const FiberItem& it);
-void fiber_gemm_f64_tiles(FiberItem& it);
+int plan_fiber_gemm_f64(FiberItem* it, int n, int* nwg = nullptr, int tpw = 0);     // sets the tile grid too
 void launch_mfma_fiber_gemm_f64(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, int Kmax, int Nmax, double* d_norm_partials, bool general);
 bool gram_f64in_covers(int D, int K);          // ComplexF64 Gram over tiles of 32 fibers (one partial per chunk)
 void launch_mfma_gram_f64in(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks);
@@ -373,27 +391,20 @@ void launch_mfma_gauge_gram64(hipStream_t s, const GramItem* d_items, int nitems
 // the same for 64 < D*K <= 128 (chi = 64 sites; kernels_chi64.hip); writes ONE partial per chunk
 bool launch_mfma_gram128_f64(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks, int KKmax, bool all_kk128 = false);   // all_kk128: every item has D * K = 128
 // fused pair of mode products on two slow 32-dim legs (16 companions = 128-byte runs per workgroup)
+int plan_pair(PairItem* it, int n, int spw = 0);
 void launch_mfma_pair(hipStream_t s, const PairItem* d_items, int nitems, int total_wgs);
 void launch_x3_pair(hipStream_t s, const PairItem* d_items, int nitems, int total_wgs);                  // kernels_x3.hip: the same pass on the bf16 matrix cores
-// workgroups of one PairItem: ceil(nslices / spw) slice ranges in groups of 8, two workgroups (one per 8-companion half) per range
-inline int pair_wgs(int nslices, int spw) { const int np = (nslices + spw - 1) / spw; return 16 * ((np + 7) / 8); }
-// slices per workgroup for a batch of `total_slices`: the largest power of two <= 16 that still gives >= 1024 workgroups
-inline int pair_spw(double total_slices) {
-#ifdef TNQS_EXPERIMENTS
-    static const int forced = [] { const char* e = std::getenv("TNQS_PAIR_SPW"); return e ? std::atoi(e) : 0; }();
-    if (forced > 0) return forced;
-#endif
-    int spw = 16; while (spw > 1 && 2.0 * total_slices / spw < 1024.0) spw >>= 1; return spw;
-}
 // both messages a site sends into one linear forest in ONE pass over (X, Y): legs (lx, ly) span the plane;
 //   partial_y[b,b'] = sum (X x_lx Mx)[.. b on ly ..] conj(Y[.. b' on ly ..])      (message leaving through ly: lx absorbed with Mx)
 //   partial_x[d,d'] = sum (X x_ly My)[.. d on lx ..] conj(Y[.. d' on lx ..])      (message leaving through lx: ly absorbed with My)
 struct PairGram2Item { const void* X; const void* Y; const void* Mx; const void* My; void* partial_y; void* partial_x; PairGeom g; int wg_begin; int spw; };
+int plan_pair_gram2(PairGram2Item* it, int n, int* nwg = nullptr, int spw = 0);
 void launch_mfma_pair_gram2(hipStream_t s, const PairGram2Item* d_items, int nitems, int total_wgs);
 void launch_x3_pair_gram2(hipStream_t s, const PairGram2Item* d_items, int nitems, int total_wgs);      // kernels_x3.hip: the same pass on the bf16 matrix cores
+int plan_x3_pair_gram1(PairGram2Item* it, int n, int* nwg = nullptr, int spw = 0);
 void launch_x3_pair_gram1(hipStream_t s, const PairGram2Item* d_items, int nitems, int total_wgs);     // kernels_x3.hip: ONE message per item (My = partial_x = null)
-int pair_gram2_group();      // workgroups of one group of 8 slice ranges: 32 (a workgroup walks one quarter of each slice)
 // last absorption + Gram on two arbitrary 32-dim legs (absorbed leg x, kept leg y), reading a (cached) pair product X and psi = Y
+int plan_pair_gram(PairGramItem* it, int n, int* nwg = nullptr, int spw = 0);
 void launch_mfma_pair_gram(hipStream_t s, const PairGramItem* d_items, int nitems, int total_wgs);
 
 }  // namespace tnqs

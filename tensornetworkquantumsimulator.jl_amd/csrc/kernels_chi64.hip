@@ -512,6 +512,11 @@ void rowgemm_tiles(FiberItem& it) {       // tile grid of an item rowgemm_covers
     it.TA = 32; it.TB = 1;
     if (it.PA >= 32) { it.nta = it.PA / 32; it.ntb = it.PB; } else { it.nta = 1; it.ntb = it.PB / (32 / it.PA); }
 }
+// tpw: tiles / 2048 clamped to [4, cap], rounded down to a multiple of 4; ceil(tiles / tpw) workgroups per item
+int plan_rowgemm(FiberItem* it, int n, int cap, int* nwg, int tpw) {
+    if (tpw <= 0) { double t = 0; for (int i = 0; i < n; ++i) t += (double)it[i].nta * it[i].ntb; tpw = (int)std::max(4.0, std::min((double)cap, t / 2048.0)); tpw &= ~3; }
+    return lay_out(it, n, &FiberItem::tile_begin, nwg, [&](FiberItem& f) { f.tpw = tpw; return (f.nta * f.ntb + tpw - 1) / tpw; });
+}
 template <int KB, int NB, int D> static void launch_rowgemm_t(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, double* d_norm_partials) {
     const size_t lds = (size_t)(16 * KB) * NB * 64 * sizeof(v2f);
     // three-multiplication product except for K = N = 128: its 16 blocks x 3 accumulators do not fit next to the operand registers (21 spills)

@@ -126,11 +126,15 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_f64_kernel(const FiberIte
 
 // shapes the kernel takes: contracted and produced index up to 64 each (X^T within the LDS, accumulators within the registers)
 bool fiber_gemm_f64_covers(const FiberItem& it) { return it.D * it.K >= 4 && it.D * it.K <= 64 && it.Do * it.No >= 1 && it.Do * it.No <= 64; }
-// tile grid of an item: TA x TB = 16 fibers
-void fiber_gemm_f64_tiles(FiberItem& it) {
-    it.TA = it.PA >= 16 ? 16 : (it.PA >= 8 ? 8 : (it.PA >= 4 ? 4 : (it.PA >= 2 ? 2 : 1)));
-    it.TB = 16 / it.TA;
-    it.nta = (it.PA + it.TA - 1) / it.TA; it.ntb = (it.PB + it.TB - 1) / it.TB;
+// tile grid of an item: TA x TB = 16 fibers; tpw: tiles / 4096 clamped to [8, 64], rounded down to a multiple of 4; ceil(tiles / tpw) workgroups per item
+int plan_fiber_gemm_f64(FiberItem* it, int n, int* nwg, int tpw) {
+    double t = 0;
+    for (FiberItem* f = it; f < it + n; ++f) {
+        f->TA = f->PA >= 16 ? 16 : (f->PA >= 8 ? 8 : (f->PA >= 4 ? 4 : (f->PA >= 2 ? 2 : 1))); f->TB = 16 / f->TA;
+        f->nta = (f->PA + f->TA - 1) / f->TA; f->ntb = (f->PB + f->TB - 1) / f->TB; t += (double)f->nta * f->ntb;
+    }
+    if (tpw <= 0) { tpw = (int)std::max(8.0, std::min(64.0, t / 4096.0)); tpw &= ~3; }
+    return lay_out(it, n, &FiberItem::tile_begin, nwg, [&](FiberItem& f) { f.tpw = tpw; return (f.nta * f.ntb + tpw - 1) / tpw; });
 }
 template <int NBLK, int KS, bool GEN> static void launch_one(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, size_t lds, double* np) {
     set_max_dynamic_lds((const void*)mfma_fiber_gemm_f64_kernel<NBLK, KS, GEN>, lds);

@@ -780,6 +780,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     #undef TNQS_PIN
 }
+static int pair_slices(const PairGeom& g) { return g.n0 * g.n1 * g.n2; }
+// spw: the largest power of two <= 16 that still gives >= 1024 workgroups; an item walks ceil(slices / spw) slice ranges in groups of 8, two
+// workgroups (one per 8-companion half) per range (the same on the bf16 kernel)
+int plan_pair(PairItem* it, int n, int spw) {
+    if (spw <= 0) {
+        double tot = 0; for (int i = 0; i < n; ++i) tot += pair_slices(it[i].g); spw = 16; while (spw > 1 && 2.0 * tot / spw < 1024.0) spw >>= 1;
+#ifdef TNQS_EXPERIMENTS
+        static const int forced = [] { const char* e = std::getenv("TNQS_PAIR_SPW"); return e ? std::atoi(e) : 0; }();
+        if (forced > 0) spw = forced;
+#endif
+    }
+    return lay_out(it, n, &PairItem::slice_begin, nullptr, [&](PairItem& p) { p.spw = spw; const int np = (pair_slices(p.g) + spw - 1) / spw; return 16 * ((np + 7) / 8); });
+}
 void launch_mfma_pair(hipStream_t s, const PairItem* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
     if (mfma_use_x3()) { launch_x3_pair(s, d_items, nitems, total_wgs); return; }
@@ -899,6 +912,11 @@ __global__ __launch_bounds__(512) void mfma_pair_gram_kernel(const PairGramItem*
         for (int ww = 0; ww < 8; ++ww) { const v2f v = R[ww * (32 * 33) + j * 33 + i]; sr += v[0]; si += v[1]; }
         cf o; o.re = sr; o.im = si; part[e] = o;
     }
+}
+// spw: slices / 2048 clamped to [4, 16]; ceil(slices / spw) workgroups per item, one partial each
+int plan_pair_gram(PairGramItem* it, int n, int* nwg, int spw) {
+    if (spw <= 0) { double tot = 0; for (int i = 0; i < n; ++i) tot += pair_slices(it[i].g); spw = (int)std::max(4.0, std::min(16.0, tot / 2048.0)); }
+    return lay_out(it, n, &PairGramItem::wg_begin, nwg, [&](PairGramItem& p) { p.spw = spw; return (pair_slices(p.g) + spw - 1) / spw; });
 }
 void launch_mfma_pair_gram(hipStream_t s, const PairGramItem* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
@@ -1069,7 +1087,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     #undef TNQS_PIN
 }
 int x3_pair_gram2_group();
-int pair_gram2_group() { return mfma_use_x3() ? x3_pair_gram2_group() : 32; }
+// spw: the largest power of two <= 16 that gives >= 1024 workgroups, counted as 16 per group of 8 slice ranges on either kernel; an item gets
+// groups of x3_pair_gram2_group() (bf16) or 32 workgroups (a workgroup walks one quarter of each slice), one 32 x 32 partial each per message
+int plan_pair_gram2(PairGram2Item* it, int n, int* nwg, int spw) {
+    auto groups = [](const PairGram2Item& p, int w) { const int np = (pair_slices(p.g) + w - 1) / w; return (np + 7) / 8; };
+    if (spw <= 0)
+        for (spw = 16; spw > 1; spw >>= 1) { long tot = 0; for (int i = 0; i < n; ++i) tot += 16 * groups(it[i], spw); if (tot >= 1024) break; }
+    const int per_group = mfma_use_x3() ? x3_pair_gram2_group() : 32;
+    return lay_out(it, n, &PairGram2Item::wg_begin, nwg, [&](PairGram2Item& p) { p.spw = spw; return per_group * groups(p, spw); });
+}
 void launch_mfma_pair_gram2(hipStream_t s, const PairGram2Item* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
     if (mfma_use_x3()) { launch_x3_pair_gram2(s, d_items, nitems, total_wgs); return; }

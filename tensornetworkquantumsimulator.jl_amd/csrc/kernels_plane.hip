@@ -279,6 +279,13 @@ bool pair16_whole_lines(const PlaneGeom& g) {
 #endif
     return g.cstr == 2;
 }
+// spw: 4 (4 slices at a time, as 8 waves x half slices or 4 waves x whole slices), doubled up to 64 while the batch keeps >= 2048 workgroups of
+// 2 spw slices (at least ~8 per CU); ceil(slices / spw) workgroups per item
+void plan_pair16(Pair16Item* it, int n, int wgs[2], int spw) {
+    if (spw <= 0) { double tot = 0; for (int i = 0; i < n; ++i) tot += it[i].g.nslices(); spw = 4; while (spw < 64 && tot / (2 * spw) >= 2048.0) spw *= 2; }
+    wgs[0] = wgs[1] = 0;
+    for (int i = 0; i < n; ++i) { int& w = wgs[pair16_whole_lines(it[i].g) ? 1 : 0]; it[i].spw = spw; it[i].wg_begin = w; w += (it[i].g.nslices() + spw - 1) / spw; }
+}
 void launch_mfma_pair16(hipStream_t s, const Pair16Item* d_items, int nitems, int total_wgs, bool whole_lines) {
     if (total_wgs > 0 && whole_lines) {
         const size_t lds = (size_t)4 * 16 * PS16 * sizeof(v2f);
@@ -479,6 +486,12 @@ __global__ __launch_bounds__(512) void mfma_pair_gram2x16_kernel(const PairGram2
 }
 // slices a workgroup walks at a time (eight waves x half slices): PairGram2x16Item::spw must be a multiple
 int pair_gram2x16_slices_at_a_time() { return 4; }
+// spw: those 4 slices, doubled up to 128 while the batch keeps >= 2048 workgroups of 2 spw slices; ceil(slices / spw) workgroups per item, one 16 x 16 partial
+// each per message
+int plan_pair_gram2x16(PairGram2x16Item* it, int n, int* nwg, int spw) {
+    if (spw <= 0) { double tot = 0; for (int i = 0; i < n; ++i) tot += it[i].g.nslices(); spw = 4; while (spw < 128 && tot / (2 * spw) >= 2048.0) spw *= 2; }
+    return lay_out(it, n, &PairGram2x16Item::wg_begin, nwg, [&](PairGram2x16Item& p) { p.spw = spw; return (p.g.nslices() + spw - 1) / spw; });
+}
 void launch_mfma_pair_gram2x16(hipStream_t s, const PairGram2x16Item* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
     const size_t lds = (size_t)8 * 8 * PS16 * sizeof(v2f);

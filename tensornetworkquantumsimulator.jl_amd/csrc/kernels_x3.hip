@@ -231,7 +231,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 #undef TNQS_PIN
 int x3_pair_gram2_group() { return 16; }
-// one message per item (the entries of a level that have no partner message: PairGram2Item with My = partial_x = null)
+// one message per item (the entries of a level that have no partner message: PairGram2Item with My = partial_x = null).  spw: 16, halved while
+// the batch would get fewer than 1024 half-slice workgroups; an item gets groups of 16 workgroups, one partial each
+int plan_x3_pair_gram1(PairGram2Item* it, int n, int* nwg, int spw) {
+    auto slices = [](const PairGram2Item& p) { return p.g.n0 * p.g.n1 * p.g.n2; };
+    if (spw <= 0) { double tot = 0; for (int i = 0; i < n; ++i) tot += (double)slices(it[i]); spw = 16; while (spw > 1 && 2.0 * tot / spw < 1024.0) spw >>= 1; }
+    return lay_out(it, n, &PairGram2Item::wg_begin, nwg, [&](PairGram2Item& p) { p.spw = spw; const int np = (slices(p) + spw - 1) / spw; return 16 * ((np + 7) / 8); });
+}
 void launch_x3_pair_gram1(hipStream_t s, const PairGram2Item* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
     const size_t lds = (size_t)16 * (32 * 34 + 2) * 2 * sizeof(float);
