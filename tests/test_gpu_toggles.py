@@ -67,6 +67,21 @@ def test_alternative_routes_match_the_default(switch):
         assert np.max(np.abs(np.array(a["z"]) - np.array(b["z"]))) < 1e-5, name
 
 
+def test_collapsed_cholesky_pivot_falls_back_to_the_eigen_route():
+    """a site whose gauged tensor has at least as many fibers as columns is factorised by Cholesky; when its Gram matrix is rank-deficient anyway (here: all
+    weight on physical index 0) a pivot collapses and the batch redoes that site on the eigen route (toggle_worker.cholfb).  The fallback must have been
+    taken (n_chol_fallbacks), and the results are those of the all-eigen route (TNQS_NO_CHOL=1) to the bounds of test_alternative_routes_match_the_default,
+    for ComplexF32 (one read-back) and ComplexF64 (two read-backs and the second factorisation pass)."""
+    ref, alt = run_worker({}, "cholfb"), run_worker({"TNQS_NO_CHOL": "1"}, "cholfb")
+    for name in ("complex64", "complex128"):
+        a, b = ref[name], alt[name]
+        assert a["chol_fallbacks"] >= 1 and b["chol_fallbacks"] == 0, (name, a["chol_fallbacks"], b["chol_fallbacks"])
+        assert a["dims"] == b["dims"], name
+        ea, eb = np.array(a["errs"]), np.array(b["errs"])
+        assert np.all(np.abs(ea - eb) < 2e-3 * np.maximum(ea, eb) + 2e-7), (name, float(np.max(np.abs(ea - eb))))
+        assert np.max(np.abs(np.array(a["z"]) - np.array(b["z"]))) < 1e-5, name
+
+
 def test_staging_arena_overflow_keeps_descriptors_alive():
     """the pinned staging arena of descriptor uploads wraps around in the middle of a phase (TNQS_ARENA_KB=48: a few uploads fill it): only the
     HOST staging may be recycled at that point -- the device copies of descriptor arrays whose kernels are not launched yet must stay

@@ -147,7 +147,29 @@ def specfail():
     print(json.dumps(out))
 
 
+def cholfb():
+    """a collapsed Cholesky pivot inside a batch (engine_gates.cpp: factor_G's fallback pass): one bulk site of a random chi = 2 state keeps only its
+    physical index 0.  Its gauged tensor has more fibers (8) than columns (4), so its R factor is taken by Cholesky, but half of the columns are zero;
+    Rzz gates are diagonal and keep them so.  ComplexF32 runs the one-round-trip route, ComplexF64 the two-round-trip route with its second pass."""
+    out = {}
+    for dt in (np.complex64, np.complex128):
+        g = tn.named_grid((4, 4))
+        bpc = tn.BeliefPropagationCache(tn.random_tensornetworkstate(dt, g, bond_dimension=2, seed=13))
+        v = next(u for u in g.vertices if g.degree(u) == 4)
+        t = np.array(bpc.tensor(v)); t[1:] = 0
+        bpc._set_tensor(v, t)
+        bpc = tn.update(bpc, maxiter=30, tolerance=None)
+        layer = [("Rzz", [a, b], 0.4) for grp in tn.edge_color(g, 4) for (a, b) in grp]
+        info = {}
+        b2, errs = tn.apply_gates(layer, bpc, apply_kwargs=dict(maxdim=2, cutoff=1e-10, normalize_tensors=True), bp_update_kwargs=dict(maxiter=20, tolerance=None), info=info)
+        out[np.dtype(dt).name] = dict(errs=errs.tolist(), z=[float(np.real(x)) for x in tn.expect_all(b2, "Z")], dims=[b2.bond_dim(a, b) for a, b in g.edges],
+                                      chol_fallbacks=info["n_chol_fallbacks"])
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "cholfb":
+        return cholfb()
     if len(sys.argv) > 1 and sys.argv[1] == "specfail":
         return specfail()
     if len(sys.argv) > 1 and sys.argv[1] == "hh16":
