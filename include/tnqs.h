@@ -197,6 +197,28 @@ int tnqs_rescale_vertices(tnqs_handle h, int n_vertices, const int32_t* vertices
  * diag(S) is a BP fixed point when the input messages were one.  regularization < 0: default 10 eps(real(eltype)). */
 int tnqs_symmetric_gauge(tnqs_handle h, double regularization);
 
+/* ---- sampling (src/sampling.jl:3-46, alg = "bp"; library version 102) ----------------------------------------------
+ * psi_v <- psi_v[config, ...]: the site leg of v gets dimension 1 (setindex_preserve!(cache, psi_v * onehot(s => config)),
+ * src/sampling.jl:35-36).  Bond dimensions and messages are kept; the tensor is not rescaled.  config in [0, d_v).  Afterwards
+ * tnqs_set_site_tensor on v takes a site dimension of 1 and tnqs_apply_gates on v is TNQS_ERR_INVALID.  Sharded handles: TNQS_ERR_UNSUPPORTED. */
+int tnqs_project_site(tnqs_handle h, int v, int config);
+int tnqs_site_dim(tnqs_handle h, int v, int* d);                     /* the CURRENT site dimension (1 after tnqs_project_site) */
+/* p[s] = real(diag rho_v)[s] / tr rho_v under the current messages, d_v doubles: the weights sample() draws from (src/sampling.jl:28-30),
+ * from the same kernel tnqs_sample_bp uses.  TNQS_ERR_NUMERIC: tr rho_v zero or not finite, or a diagonal entry below
+ * -(100 eps of the element's real type) tr rho_v (entries negative within that bound count as 0). */
+int tnqs_site_probabilities(tnqs_handle h, int v, double* out_p);
+/* sample(alg"bp") loop of src/sampling.jl:18-43 on COPIES of h (h is not changed; the caller has updated and, if wanted, gauged it): per
+ * sample, at every vertex in vertex order: the weights above, a draw, tnqs_project_site, and (except after the last vertex) tnqs_bp_update
+ * with bp_opts.  The draw takes ONE uniform u: x = the first s with u < p[0] + ... + p[s], the last s if there is none.
+ * uniforms: NULL = the library's counter-based generator (the uniform of (seed, sample, vertex) depends on those three numbers only, 53 bits,
+ * never 1); else nsamples*nv doubles in [0,1), sample-major.
+ * out_config: nsamples*nv int32 in 0..d-1, sample-major, vertex order.  out_prob (may be NULL): the probability p[x] with which
+ * each entry was drawn, same layout; log q(x) of a sample is the sum of their logs.  stats (may be NULL): BP updates / sweeps /
+ * non-converged updates summed over the call.  For the same uniforms the result is exactly what the host loop over tnqs_copy,
+ * tnqs_site_probabilities, that draw, tnqs_project_site and tnqs_bp_update gives.  Sharded handles: TNQS_ERR_UNSUPPORTED. */
+int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uint64_t seed, const double* uniforms,
+                   int32_t* out_config, double* out_prob, tnqs_apply_stats* stats);
+
 /* ---- multi-GPU sharding (no reference analogue).  A rank owns a vertex subset: it holds only
  *      those site tensors and does all per-vertex work for them; messages are replicated.  The library calls
  *      the host-supplied all-gather at the exchange points (host side: torch.distributed over RCCL). --------- */

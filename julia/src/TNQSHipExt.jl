@@ -421,6 +421,51 @@ function TN.symmetric_gauge!(c::HipBeliefPropagationCache; regularization = 10 *
     return c
 end
 
+# ---- sampling (src/sampling.jl:3-46, alg = "bp"; library version 102) ------------------------------------------------------------------
+const TNQS_MIN_VERSION_SAMPLING = 102
+sampling_available() = ccall((:tnqs_version, LIB), Cint, ()) >= TNQS_MIN_VERSION_SAMPLING
+site_dim(c::HipBeliefPropagationCache, v) = (d = Ref{Cint}(0); check(ccall((:tnqs_site_dim, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), c.handle, c.vid[v], d)); Int(d[]))
+# psi_v <- psi_v[config, ...] (config 0-based, as in the bitstrings): setindex_preserve!(cache, psi_v * onehot(s => config + 1), v), src/sampling.jl:35-36
+function project_site!(c::HipBeliefPropagationCache, v, config::Integer)
+    check(ccall((:tnqs_project_site, LIB), Cint, (Ptr{Cvoid}, Cint, Cint), c.handle, c.vid[v], config))
+    return c
+end
+function site_probabilities(c::HipBeliefPropagationCache, v)                 # real(diag rho_v) / tr rho_v, the weights of src/sampling.jl:28-31
+    p = zeros(Float64, site_dim(c, v))
+    GC.@preserve p check(ccall((:tnqs_site_probabilities, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), c.handle, c.vid[v], p))
+    return p
+end
+# the loop of src/sampling.jl:18-43 on the device, on copies of `c` (already updated and, if wanted, gauged); every per-step update runs with the caller's
+# bp_update_kwargs (default_bp_update_kwargs when omitted, as in apply_gates).  uniforms: nothing = the library's counter-based generator with `seed`; or an
+# nv x nsamples matrix of numbers in [0, 1) drawn with the caller's RNG (column j = sample j, row i = i-th vertex).
+# Returns (configs, probs), both nv x nsamples: the 0-based configurations and the probability each was drawn with.
+function sample_bp(c::HipBeliefPropagationCache, nsamples::Integer; bp_update_kwargs = TN.default_bp_update_kwargs(c), seed::Integer = 0,
+                   uniforms::Union{Nothing, Matrix{Float64}} = nothing)
+    sampling_available() || error("libtnqs_hip is older than version 102: no tnqs_sample_bp")
+    nv = length(vertices(c.g))
+    uniforms === nothing || size(uniforms) == (nv, nsamples) || error("sample_bp: uniforms must be nv x nsamples")
+    cfg = zeros(Int32, nv, nsamples); prob = zeros(Float64, nv, nsamples)
+    up = uniforms === nothing ? Ptr{Float64}(C_NULL) : pointer(uniforms)
+    with_bpopts(c, bp_update_kwargs) do bo
+        GC.@preserve uniforms cfg prob check(ccall((:tnqs_sample_bp, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{BpOpts}, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Cvoid}),
+                                                   c.handle, nsamples, bo, UInt64(seed), up, cfg, prob, C_NULL))
+    end
+    return cfg, prob
+end
+# sample(alg"bp", psi, nsamples; bp_update_kwargs, gauge_state) (src/sampling.jl:3-46) for a device cache: lines 11-14 (update, then the symmetric gauge on a
+# rescaled cache), then the loop above; returns the reference's vector of (bitstring = Dictionary(vertex => 0-based configuration),) and the cache
+function TN.sample(c::HipBeliefPropagationCache, nsamples::Integer; alg = "bp", bp_update_kwargs = TN.default_bp_update_kwargs(c), gauge_state = true, kwargs...)
+    alg == "bp" || error("HipBeliefPropagationCache: only alg = \"bp\" is implemented")
+    c = TN.update(c; bp_update_kwargs...)
+    if gauge_state                                                  # symmetrize_and_normalize (src/symmetric_gauge.jl:70-74): rescale!, then the gauge
+        TN.rescale!(c)
+        TN.symmetric_gauge!(c)
+    end
+    cfg, _ = sample_bp(c, nsamples; bp_update_kwargs = bp_update_kwargs, kwargs...)
+    vs = collect(vertices(c.g))
+    return [(bitstring = Dictionary(vs, Int[cfg[i, j] for i in 1:length(vs)]),) for j in 1:nsamples], c
+end
+
 # ---- Adapt parity (abstract…:261-287): moves between the CPU cache and the device cache ----------------------------------------------
 struct HipStorage end          # Adapt.adapt(HipStorage(), bpc::BeliefPropagationCache) -> HipBeliefPropagationCache, messages included
 function Adapt.adapt_structure(::HipStorage, b::TN.BeliefPropagationCache)

@@ -9,6 +9,7 @@ reference repo):
   truncate(bpc; maxdim, cutoff, edge_color, normalize_tensors)           src/truncate.jl:12-38
   expect(bpc, (op, [v]))                                                  src/expect.jl:54-82,114-121
   maxvirtualdim                                                           src/TensorNetworks/abstracttensornetwork.jl:27-29
+  sample(psi, nsamples; alg = "bp")                                       src/sampling.jl:3-46
 Every flop runs in libtnqs_hip.so; this file only marshals arguments through the C ABI (include/tnqs.h)."""
 from __future__ import annotations
 
@@ -161,12 +162,17 @@ class BeliefPropagationCache:
         return out
 
     def _site_dim(self, v) -> int:
-        n = C.c_int64()
-        L.check(L.lib.tnqs_site_tensor_size(self._h, self.graph.index[v], C.byref(n)))
-        p = 1
-        for w in self.graph.neighbors(v):
-            p *= self.bond_dim(v, w)
-        return int(n.value // p)
+        """the live site dimension (1 after `project`)"""
+        d = C.c_int()
+        L.check(L.lib.tnqs_site_dim(self._h, self.graph.index[v], C.byref(d)))
+        return d.value
+
+    def project(self, v, config: int) -> "BeliefPropagationCache":
+        """a copy with psi_v replaced by its slice psi_v[config, ...] (site dimension 1; bond dimensions and messages kept, no rescaling):
+        setindex_preserve!(cache, psi_v * onehot(s => config), v) of src/sampling.jl:35-36"""
+        out = self.copy()
+        L.check(L.lib.tnqs_project_site(out._h, self.graph.index[v], int(config)))
+        return out
 
     def bond_dim(self, a, b) -> int:
         c = C.c_int()
@@ -630,6 +636,70 @@ def symmetric_gauge(x, regularization: Optional[float] = None, cache_update_kwar
 def symmetrize_and_normalize(bpc: BeliefPropagationCache, regularization: Optional[float] = None) -> BeliefPropagationCache:
     """symmetrize_and_normalize (symmetric_gauge.jl:70-74): rescale, then symmetric gauge"""
     return symmetric_gauge(rescale(bpc), regularization=regularization)
+
+
+def site_probabilities(bpc: BeliefPropagationCache, v) -> np.ndarray:
+    """p[s] = real(diag rho_v)[s] / tr rho_v under the cache's messages: the weights `sample` draws the configuration of v from"""
+    out = np.zeros(bpc._site_dim(v), dtype=np.float64)
+    L.check(L.lib.tnqs_site_probabilities(bpc._h, bpc.graph.index[v], out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def _check_sample_args(graph, nsamples, alg, uniforms):
+    """the argument checks of `sample` that need no device"""
+    if alg != "bp":
+        raise L.TnqsError(f"sample: only alg = \"bp\" is implemented on the HIP path; received {alg!r}")
+    if int(nsamples) != nsamples or nsamples < 0:
+        raise L.TnqsArgumentError(f"sample: nsamples must be a non-negative integer; received {nsamples!r}")
+    if uniforms is None:
+        return None
+    u = np.ascontiguousarray(uniforms, dtype=np.float64)
+    if u.shape != (int(nsamples), graph.nv()):
+        raise L.TnqsArgumentError(f"sample: uniforms must have shape (nsamples, number of vertices) = {(int(nsamples), graph.nv())}; received {u.shape}")
+    if not np.all((u >= 0.0) & (u < 1.0)):
+        raise L.TnqsArgumentError("sample: uniforms must lie in [0, 1)")
+    return u
+
+
+def sample_with_probabilities(x, nsamples: int, alg: str = "bp", bp_update_kwargs: Optional[dict] = None, gauge_state: bool = True,
+                              seed: Optional[int] = None, uniforms=None, device: int = 0):
+    """sample(alg"bp", psi, nsamples; bp_update_kwargs, gauge_state) (src/sampling.jl:3-46) -> (bitstrings, logq): a list of {vertex: int}
+    dicts and, per sample, the log of the probability with which the sampler drew it (the sum of the logs of its step probabilities).
+    x: a TensorNetworkState or a BeliefPropagationCache; either is updated first and, with gauge_state, put into the symmetric gauge
+    (:11-14); then, per sample and vertex in vertex order: weights from rho_v, a draw, projection, BP update -- all on the device.
+    bp_update_kwargs = None: default_bp_update_kwargs of the cache.  uniforms: (nsamples, nv) numbers in [0, 1) to draw with instead of
+    the library's counter-based generator (seed; None: a fresh one from numpy)."""
+    if not isinstance(x, (TensorNetworkState, BeliefPropagationCache)):
+        raise TypeError("sample: expected a TensorNetworkState or a BeliefPropagationCache")
+    u = _check_sample_args(x.graph, nsamples, alg, uniforms)
+    nsamples = int(nsamples)
+    bpc = BeliefPropagationCache(x, device=device) if isinstance(x, TensorNetworkState) else x
+    g = bpc.graph
+    kw = bpc.default_bp_update_kwargs() if bp_update_kwargs is None else bp_update_kwargs
+    bpc = update(bpc, **kw)
+    if gauge_state:
+        bpc = symmetrize_and_normalize(bpc)
+    bo, keep = _bp_opts(g, kw)
+    nv = g.nv()
+    cfg = np.zeros((max(nsamples, 1), nv), dtype=np.int32)
+    prob = np.ones((max(nsamples, 1), nv), dtype=np.float64)
+    st = L.ApplyStats()
+    if seed is None:
+        seed = int(np.random.default_rng().integers(0, 2 ** 63))
+    L.check(L.lib.tnqs_sample_bp(bpc._h, nsamples, C.byref(bo), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                 None if u is None else u.ctypes.data_as(C.POINTER(C.c_double)), cfg.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 prob.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st)))
+    bitstrings = [{v: int(cfg[j, i]) for i, v in enumerate(g.vertices)} for j in range(nsamples)]
+    with np.errstate(divide="ignore"):
+        logq = np.log(prob[:nsamples]).sum(axis=1)
+    return bitstrings, logq
+
+
+def sample(x, nsamples: int, alg: str = "bp", bp_update_kwargs: Optional[dict] = None, gauge_state: bool = True, seed: Optional[int] = None,
+           uniforms=None, device: int = 0):
+    """sample(psi, nsamples; alg = "bp") (src/sampling.jl:3-46): a list of {vertex: int} dicts (see sample_with_probabilities)"""
+    return sample_with_probabilities(x, nsamples, alg=alg, bp_update_kwargs=bp_update_kwargs, gauge_state=gauge_state, seed=seed,
+                                     uniforms=uniforms, device=device)[0]
 
 
 def profile_enable(bpc: BeliefPropagationCache, on: bool = True):

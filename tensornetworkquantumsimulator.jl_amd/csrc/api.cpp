@@ -21,7 +21,7 @@ static State* S(tnqs_handle h) { if (!h || !h->s) throw Err(TNQS_ERR_INVALID, "n
 
 extern "C" {
 
-int tnqs_version(void) { return 101; }
+int tnqs_version(void) { return 102; }
 const char* tnqs_last_error(void) { return g_err.c_str(); }
 int tnqs_device_count(int* count) {
     return guard([&] { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) n = 0; if (count) *count = n; });
@@ -126,6 +126,12 @@ int tnqs_rescale_vertices(tnqs_handle h, int n_vertices, const int32_t* verts) {
     return guard([&] { if (n_vertices < 0) throw Err(TNQS_ERR_INVALID, "rescale_vertices: negative count"); rescale_vertices(S(h), n_vertices, verts); });
 }
 int tnqs_symmetric_gauge(tnqs_handle h, double regularization) { return guard([&] { symmetric_gauge(S(h), regularization); }); }
+int tnqs_project_site(tnqs_handle h, int v, int config) { return guard([&] { project_site(S(h), v, config); }); }
+int tnqs_site_dim(tnqs_handle h, int v, int* d) { return guard([&] { if (!d) throw Err(TNQS_ERR_INVALID, "site_dim: null output"); site_dim(S(h), v, d); }); }
+int tnqs_site_probabilities(tnqs_handle h, int v, double* out_p) { return guard([&] { if (!out_p) throw Err(TNQS_ERR_INVALID, "site_probabilities: null output"); site_probabilities(S(h), v, out_p); }); }
+int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uint64_t seed, const double* uniforms, int32_t* out_config, double* out_prob, tnqs_apply_stats* stats) {
+    return guard([&] { sample_bp(S(h), nsamples, bp_opts, seed, uniforms, out_config, out_prob, stats); });
+}
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out) {
     return guard([&] { if (!ops || !out) throw Err(TNQS_ERR_INVALID, "expect_all: null"); expect_all(S(h), ops, out); });
 }

@@ -132,7 +132,8 @@ struct State {
     // `adapt_gate` kept a complex gate complex (src/Apply/apply_gates.jl:41-44) and the contraction promoted the site tensors
     bool real_io = false;
     int device = 0;
-    std::vector<int> d;            // site dims
+    std::vector<int> d;            // site dims (1 for a vertex projected by project_site)
+    std::vector<char> projected;   // v was replaced by a slice psi_v[config, ...] (engine_sample.cpp): gates can no longer act on it
     std::vector<int> chi;          // bond dim per edge
     std::vector<Buf> site;         // canonical layout; null when not owned (sharding)
     std::vector<Buf> sscale;       // pending real scale factor of a site tensor (one device double; null = 1): the tensor the
@@ -202,6 +203,11 @@ void rescale(State* s);
 void rescale_messages(State* s, int n, const int32_t* eu, const int32_t* ev);     // null lists: all edges / all vertices
 void rescale_vertices(State* s, int n, const int32_t* verts);
 void symmetric_gauge(State* s, double regularization);
+// engine_sample.cpp: sample(alg = "bp") of src/sampling.jl:18-43 and its pieces
+void site_dim(const State* s, int v, int* d);
+void project_site(State* s, int v, int config);
+void site_probabilities(State* s, int v, double* out_p);
+void sample_bp(State* s, int nsamples, const tnqs_bp_opts* bp, uint64_t seed, const double* uniforms, int32_t* out_config, double* out_prob, tnqs_apply_stats* stats);
 void prof_collect(State* s);
 void materialize_pending_all(State* s);      // apply every deferred one-site gate (State::pend1)
 // sharding.cpp

@@ -222,7 +222,7 @@ State* state_create(int nv, int ne, const int32_t* es, const int32_t* ed, const 
     if (sd) for (int v = 0; v < nv; ++v) { if (sd[v] < 1 || sd[v] > 16) throw Err(TNQS_ERR_INVALID, "tnqs_create: site dimension out of range"); s->d[v] = sd[v]; }
     s->chi.assign(ne, 1);
     s->site.resize(nv); s->sscale.assign(nv, nullptr); s->msg.assign(2 * (size_t)ne, nullptr);
-    s->pend1.assign(nv, {}); s->unit_norm.assign(nv, 0);
+    s->pend1.assign(nv, {}); s->unit_norm.assign(nv, 0); s->projected.assign(nv, 0);
     s->pool = std::make_shared<Pool>(device);
     s->prof = std::make_shared<Prof>();
     s->stream = acquire_stream(device); s->own_stream = true;
@@ -234,7 +234,7 @@ State* state_copy(const State* o) {
     auto s = std::make_unique<State>();
     s->g = o->g; s->dtype = o->dtype; s->real_io = o->real_io; s->device = o->device; s->d = o->d; s->chi = o->chi;
     s->site = o->site; s->sscale = o->sscale; s->msg = o->msg; s->pool = o->pool; s->prof = o->prof;
-    s->pend1 = o->pend1; s->unit_norm = o->unit_norm;
+    s->pend1 = o->pend1; s->unit_norm = o->unit_norm; s->projected = o->projected;
     s->rank = o->rank; s->nranks = o->nranks; s->owner = o->owner; s->ag_fn = o->ag_fn; s->ag_ctx = o->ag_ctx;
     s->exch = o->exch; s->exch_bytes = o->exch_bytes; s->comm = o->comm; s->force_exchange = o->force_exchange; s->msg_hermitian = o->msg_hermitian;
     HIPCHK(hipSetDevice(o->device));

@@ -1141,7 +1141,9 @@ template <class T> static void apply_gates_t(State* s, int ngates, const int32_t
         if (nv < 1 || nv > 2) throw Err(TNQS_ERR_INVALID, "apply_gate!: only one- and two-site gates are supported; received a gate acting on " + std::to_string(nv) + " vertices.");
         voff[i + 1] = voff[i] + nv;
         size_t dd = 1;
-        for (int k = 0; k < nv; ++k) { int v = verts[voff[i] + k]; if (v < 0 || v >= g.nv) throw Err(TNQS_ERR_INVALID, "apply_gates: vertex out of range"); dd *= s->d[v]; }
+        for (int k = 0; k < nv; ++k) { int v = verts[voff[i] + k]; if (v < 0 || v >= g.nv) throw Err(TNQS_ERR_INVALID, "apply_gates: vertex out of range");
+                                       if (s->projected[v]) throw Err(TNQS_ERR_INVALID, "apply_gates: vertex " + std::to_string(v) + " was projected onto a configuration (tnqs_project_site: its site dimension is 1); gates cannot act on it");
+                                       dd *= s->d[v]; }
         moff[i + 1] = moff[i] + 2 * dd * dd;
         if (nv == 2) {
             int a = verts[voff[i]], b = verts[voff[i] + 1];

@@ -4,6 +4,7 @@
 //   engine_bp.cpp     BP update (default sequence, level schedule, message kernels)
 //   engine_gates.cpp  apply_gates scheduler, one- and two-site gate batches, truncate
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
+//   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
 //   sharding.cpp      exchange step (RCCL or host callback)
 #pragma once
 #include "engine.hpp"
@@ -18,6 +19,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
+#include <memory>
 #include <mutex>
 #include <numeric>
 #include <set>

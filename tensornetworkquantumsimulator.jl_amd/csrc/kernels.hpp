@@ -282,6 +282,14 @@ template <class T> void launch_permute(hipStream_t s, const PermItem& item);
 template <class T> void launch_identity(hipStream_t s, void* out, int n);
 template <class T> void launch_random_fill(hipStream_t s, void* out, size_t n, unsigned long long seed, double scale, bool real_only);   // iid normal entries, counter-based
 void launch_sum_doubles(hipStream_t s, const double* in, int n, double* out);
+// sampling (kernels_sample.hip): diag(rho_v) partials [workgroup][16] from T = psi_v x messages and psi_v (n complex elements each, site index fastest);
+// the draw (sums the partials, p = diag / tr, x from one uniform by the cumulative sum; status bits 1: bad trace, 2: negative diagonal entry);
+// out[i] = psi[x + d i] with x from device memory (d_x) or, when d_x is null, from the host
+int plan_site_prob(size_t n, int d);                                                              // workgroups of the partial pass
+template <class T> void launch_site_prob_partial(hipStream_t s, const void* tabs, const void* psi, size_t n, int d, int nblocks, double* d_partial);
+void launch_site_draw(hipStream_t s, const double* d_partial, int nblocks, int d, double neg_tol, const double* d_uniform, unsigned long long seed,
+                      unsigned long long sample, unsigned long long step, bool draw, double* d_p, int* d_x, double* d_px, int* d_status);
+template <class T> void launch_site_project(hipStream_t s, const void* psi, void* out, size_t nout, int d, const int* d_x, int x_host);
 // one-site gates on d = 2, ComplexF32: streaming 2x2 apply, norm partials [item][nbx]
 void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int nbx, double* d_norm_partials);
 
