@@ -49,6 +49,8 @@ int tnqs_dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double
 #define TNQS_DBG_ROUTE_F64_SHARED 4    /* mfma_gram128_f64_kernel<true, true> (every item has D K = 128) */
 #define TNQS_DBG_ROUTE_HALF_LINES 5    /* mfma_pair16_kernel (planes that contain leg 0) */
 #define TNQS_DBG_ROUTE_WHOLE_LINES 6   /* mfma_pair16w_kernel */
+#define TNQS_DBG_ROUTE_SMALL_SCALAR 7  /* bp_small_site_kernel<1024>, scalar form */
+#define TNQS_DBG_ROUTE_SMALL_MFMA16 8  /* bp_small_site_kernel<1024>, matrix-core form (bp_small_site_mfma16) */
 /* register-direct fiber GEMM (the chi = 32 gate epilogue: D = 2, K = 32; chi = 64 mode products / epilogue; chi = 32 mode products): item i is
  * out_i[(s',n),(a,b)] = sum_{(s,k)} in_i[(s,k),(a,b)] X_i[(s,k),(s',n)] with in_i element (s,a,k,b) at s + D*(a + PA[i]*(k + K*b)), X_i (D K) x (D No[i]),
  * out_i element (s',a,n,b) at s' + D*(a + PA[i]*(n + No[i]*b)); D in {1, 2}, K in {32, 64}, 1 <= No[i] <= K; PA[i] a multiple of 32, or a divisor of 32
@@ -71,6 +73,23 @@ int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, cons
  * A_i (m[i] x n[i], 2 <= n <= 128, n <= m <= 256): A_i <- U Sigma (columns); chol_fail[i]: a Cholesky pivot was refused; polished[i]: the polishing sweeps
  * ran on the item; sweeps[i]: sweeps of the Jacobi on R (each output array may be NULL) */
 int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps);
+/* the whole BP message of a small site (kernels.hip bp_small_site_kernel<1024>): ONE launch over nitems (site, outgoing leg) pairs, sized by the largest item as
+ * the engine sizes it.  Item i is a site tensor [d[i]][chi_0]..[chi_{z[i]-1}] (column-major) with the outgoing leg jo[i]; chi, present: the items' legs one after
+ * the other; psi: the items' tensors one after the other; M: one chi_k x chi_k matrix M[q + chi_k qo] per leg of every item, in leg order (the slot of leg jo
+ * included: the kernel has to skip it), read only where present[leg] != 0 -- 0 hands the kernel a null pointer, i.e. the identity.  On the device every tensor and
+ * matrix starts at a multiple of 256 bytes, like the engine's sub-buffers.  form: -1 the engine's rule (matrix-core form iff every leg is 16-dimensional and the
+ * element count is a multiple of 256), 0 the scalar form, 1 the matrix-core form (refused where the rule does not allow it).  out, new_msg, old_msg: chi_jo^2 numbers
+ * per item, out[b + chi_jo b'], the items one after the other.  new_msg == NULL: out_i = the raw message.  new_msg != NULL: the epilogue runs as well (m / sum(m)
+ * when normalize != 0 and the sum is not exactly zero; diff_out[i] = message_diff against old_msg_i, the identity where has_old[i] == 0 or old_msg == NULL) --
+ * inside the kernel in the matrix-core form, by msg_finalize_kernel<float> on the one partial in the scalar form -- and out is left as it was.  route_out (may be
+ * NULL): TNQS_DBG_ROUTE_SMALL_* per item.  z > 8, a leg > 32 or more than 8192 elements: TNQS_ERR_UNSUPPORTED, nothing is written */
+int tnqs_dbg_small_site(int nitems, const int* d, const int* z, const int* chi, const int* jo, const void* psi, const void* M, const int* present, int form,
+                        const void* old_msg, const int* has_old, int normalize, void* out, void* new_msg, double* diff_out, int* route_out);
+/* the BP message epilogue (kernels.hip msg_finalize_kernel<T>; dtype 0 c64, 1 c128): ONE launch over nitems messages.  Item i: nchunks[i] partials of chi[i]^2
+ * numbers laid out [chunk][element], the items one after the other; new_msg_i = their sum, divided by its element sum when normalize != 0 and that sum is not
+ * exactly zero; diff_out[i] = message_diff(new_msg_i, old_msg_i) (the identity where has_old[i] == 0 or old_msg == NULL) */
+int tnqs_dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchunks, const void* partials, const void* old_msg, const int* has_old, int normalize,
+                          void* new_msg, double* diff_out);
 /* the BP sweep order bp_update uses when no edge_sequence is given, as (src[i] -> dst[i]) vertex indices; *n_out = its length (2 ne) */
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out);
 /* the same order from the graph alone (nv vertices, ne undirected edges esrc[e] - edst[e]) together with the dependency level bp_update runs every message in

@@ -208,7 +208,11 @@ namespace tnqs { void dbg_default_sequence(const State* s, std::vector<int>& src
                  void dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const void* in, const void* M, void* out, int spw, int* route);
                  void dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const int* both, const void* X, const void* Y, const void* M,
                                         void* out_y, void* out_x, int spw);
-                 void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps); }
+                 void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps);
+                 void dbg_small_site(int nitems, const int* d, const int* z, const int* chi, const int* jo, const void* psi, const void* M, const int* present, int form,
+                                     const void* old_msg, const int* has_old, int normalize, void* out, void* new_msg, double* diff, int* route);
+                 void dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchunks, const void* partials, const void* old_msg, const int* has_old, int normalize,
+                                       void* new_msg, double* diff); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
     return guard([&] { std::vector<int> a, b; dbg_default_sequence(S(h), a, b); *n_out = (int)a.size();
@@ -253,5 +257,13 @@ int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, cons
 }
 int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps) {
     return guard([&] { dbg_svd_tall(nitems, m, n, A, chol_fail, polished, sweeps); });
+}
+int tnqs_dbg_small_site(int nitems, const int* d, const int* z, const int* chi, const int* jo, const void* psi, const void* M, const int* present, int form,
+                        const void* old_msg, const int* has_old, int normalize, void* out, void* new_msg, double* diff_out, int* route_out) {
+    return guard([&] { dbg_small_site(nitems, d, z, chi, jo, psi, M, present, form, old_msg, has_old, normalize, out, new_msg, diff_out, route_out); });
+}
+int tnqs_dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchunks, const void* partials, const void* old_msg, const int* has_old, int normalize,
+                          void* new_msg, double* diff_out) {
+    return guard([&] { dbg_msg_finalize(dtype, nitems, chi, nchunks, partials, old_msg, has_old, normalize, new_msg, diff_out); });
 }
 }

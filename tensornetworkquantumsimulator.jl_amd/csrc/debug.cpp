@@ -5,6 +5,7 @@
 #include <vector>
 #include <algorithm>
 #include <memory>
+#include <string>
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "launch_util.hpp"
@@ -638,5 +639,128 @@ void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fai
         if (sweeps) dS.down(sweeps, sizeof(int) * nitems);
         for (int i = 0; i < nitems; ++i) { if (chol_fail) chol_fail[i] = f[i]; if (polished) polished[i] = w[i] >= 0; }
     }
+}
+
+// ---- the small-site BP message kernel and the message epilogue, set up as engine_bp.cpp sets them up --------------------------------------------------------
+namespace {
+inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+// a device array of slots that start at 256-byte multiples (the engine's sub-buffers); the gaps keep a 0xff filling that is checked after the launch, so a
+// kernel that writes past its slot is reported instead of going unnoticed
+struct Slots {
+    std::vector<size_t> off, len; std::vector<char> host; std::unique_ptr<DBuf> dev;
+    void add(size_t bytes) { off.push_back(total); len.push_back(bytes); total += round256(bytes); }
+    void alloc() { host.assign(total ? total : 1, (char)0xff); dev.reset(new DBuf(total)); }
+    void put(size_t i, const void* src) { std::memcpy(host.data() + off[i], src, len[i]); }
+    void get(size_t i, void* dst) const { std::memcpy(dst, host.data() + off[i], len[i]); }
+    void up() { dev->up(host.data(), total); }
+    void down(const char* what) {
+        dev->down(host.data(), total);
+        for (size_t i = 0; i < off.size(); ++i)
+            for (size_t b = off[i] + len[i]; b < off[i] + round256(len[i]); ++b)
+                if (host[b] != (char)0xff) throw Err(TNQS_ERR_INVALID, std::string("dbg: a kernel wrote past the end of a slot of ") + what);
+    }
+    char* at(size_t i) const { return (char*)dev->p + off[i]; }
+    size_t total = 0;
+};
+}
+// ONE launch_bp_small_site over nitems (site, outgoing leg) pairs (ComplexF32): item i is a site tensor [d[i]][chi_0]..[chi_{z[i]-1}] with the outgoing leg jo[i];
+// chi / present: the items' legs one after the other; psi: the items' tensors one after the other; M: one chi_k x chi_k matrix (M[q + chi_k qo]) per leg of every
+// item in leg order, read only where present[leg] != 0 (0: a null pointer = identity; the slot of leg jo is handed over as well -- the kernel must skip it).
+// form: -1 the engine's rule (matrix-core form iff every leg is 16-dimensional and the element count a multiple of 256), 0 scalar form, 1 matrix-core form or refusal.
+// new_msg == NULL: out[i] = the raw message.  Otherwise the epilogue runs as in the engine -- inside the kernel (matrix-core form) or as launch_msg_finalize<float>
+// on the one partial (scalar form) -- and out is not written.  out / new_msg / old_msg hold chi_jo^2 numbers per item, one item after the other
+void dbg_small_site(int nitems, const int* d, const int* z, const int* chi, const int* jo, const void* psi, const void* M, const int* present, int form,
+                    const void* old_msg, const int* has_old, int normalize, void* out, void* new_msg, double* diff, int* route) {
+    need_gpu();
+    if (nitems < 1 || !d || !z || !chi || !jo || !psi || !M || !present || !out || form < -1 || form > 1 || (old_msg && !has_old))
+        throw Err(TNQS_ERR_INVALID, "dbg_small_site: bad arguments");
+    std::vector<SmallMsgItem> items(nitems); std::vector<int> leg0(nitems + 1, 0);
+    Slots sPsi, sM, sOut, sNew, sOld, sRaw;
+    int max_elems = 0;
+    for (int i = 0; i < nitems; ++i) {
+        if (z[i] < 1 || z[i] > 8) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_small_site: 1 <= z <= 8");
+        const int* c = chi + leg0[i]; leg0[i + 1] = leg0[i] + z[i];
+        size_t n = (size_t)std::max(d[i], 0);
+        for (int k = 0; k < z[i]; ++k) { if (c[k] < 1) throw Err(TNQS_ERR_INVALID, "dbg_small_site: leg dimension < 1"); n *= (size_t)c[k]; }
+        if (!bp_small_site_covers(d[i], z[i], c, n)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_small_site: site not covered by bp_small_site_kernel (z <= 8, chi <= 32, <= 8192 elements)");
+        if (jo[i] < 0 || jo[i] >= z[i]) throw Err(TNQS_ERR_INVALID, "dbg_small_site: outgoing leg out of range");
+        bool all16 = (n % 256) == 0; for (int k = 0; k < z[i]; ++k) all16 = all16 && c[k] == 16;      // the engine's rule (engine_bp.cpp)
+        if (form == 1 && !all16) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_small_site: the matrix-core form takes sites whose legs are all 16-dimensional");
+        SmallMsgItem& it = items[i]; it = SmallMsgItem{};
+        it.d = d[i]; it.z = z[i]; it.jo = jo[i]; it.mfma = (form != 0 && all16) ? 1 : 0; it.normalize = normalize;
+        for (int k = 0; k < z[i]; ++k) { it.chi[k] = c[k]; sM.add((size_t)c[k] * c[k] * 8); }
+        const size_t mb = (size_t)c[jo[i]] * c[jo[i]] * 8;
+        sPsi.add(n * 8); sOut.add(mb); sNew.add(mb); sOld.add(mb); sRaw.add(mb);
+        max_elems = std::max(max_elems, (int)n);
+    }
+    sPsi.alloc(); sM.alloc(); sOut.alloc(); sNew.alloc(); sOld.alloc(); sRaw.alloc();
+    DBuf dDiff(sizeof(double) * nitems), dI(sizeof(SmallMsgItem) * nitems), dF(sizeof(MsgFinalItem) * nitems);
+    std::vector<double> hdiff(nitems, 0.0); if (diff) std::copy(diff, diff + nitems, hdiff.begin());
+    std::vector<MsgFinalItem> fin;
+    const char *hpsi = (const char*)psi, *hM = (const char*)M, *hold = (const char*)old_msg; char *hout = (char*)out, *hnew = (char*)new_msg;
+    size_t opsi = 0, oM = 0, omsg = 0;
+    for (int i = 0; i < nitems; ++i) {
+        SmallMsgItem& it = items[i];
+        sPsi.put(i, hpsi + opsi); opsi += sPsi.len[i];
+        for (int k = 0; k < it.z; ++k) {
+            const size_t q = (size_t)leg0[i] + k;
+            if (present[q]) { sM.put(q, hM + oM); it.M[k] = sM.at(q); }
+            oM += sM.len[q];
+        }
+        sOut.put(i, hout + omsg); if (hnew) sNew.put(i, hnew + omsg);
+        const bool old = hold && has_old[i]; if (old) sOld.put(i, hold + omsg);
+        omsg += sOut.len[i];
+        it.psi = sPsi.at(i); it.out = sOut.at(i);
+        if (hnew && it.mfma) { it.new_msg = sNew.at(i); it.old_msg = old ? sOld.at(i) : nullptr; it.diff_out = diff ? (double*)dDiff.p + i : nullptr; }
+        else if (hnew) {                                      // the raw message is the one partial of the message's msg_finalize item
+            it.out = sRaw.at(i);
+            fin.push_back(MsgFinalItem{sRaw.at(i), 1, it.chi[it.jo], old ? sOld.at(i) : nullptr, sNew.at(i), diff ? (double*)dDiff.p + i : nullptr, normalize});
+        }
+    }
+    sPsi.up(); sM.up(); sOut.up(); sNew.up(); sOld.up(); sRaw.up();
+    dDiff.up(hdiff.data(), sizeof(double) * nitems); dI.up(items.data(), sizeof(SmallMsgItem) * nitems);
+    if (!fin.empty()) dF.up(fin.data(), sizeof(MsgFinalItem) * fin.size());
+    launch_bp_small_site(nullptr, (const SmallMsgItem*)dI.p, nitems, max_elems);
+    launch_msg_finalize<float>(nullptr, (const MsgFinalItem*)dF.p, (int)fin.size());
+    HIPCHK(hipDeviceSynchronize());
+    sOut.down("out"); sNew.down("new_msg"); sRaw.down("the raw message");
+    omsg = 0;
+    for (int i = 0; i < nitems; ++i) { sOut.get(i, hout + omsg); if (hnew) sNew.get(i, hnew + omsg); omsg += sOut.len[i]; }
+    if (diff) dDiff.down(diff, sizeof(double) * nitems);
+    if (route) for (int i = 0; i < nitems; ++i) route[i] = items[i].mfma ? TNQS_DBG_ROUTE_SMALL_MFMA16 : TNQS_DBG_ROUTE_SMALL_SCALAR;
+}
+// ONE launch_msg_finalize<T> over nitems messages: item i has nchunks[i] partials of chi[i]^2 numbers, [chunk][element], the items one after the other; old_msg /
+// new_msg: chi[i]^2 numbers per item (has_old[i] == 0 or old_msg == NULL: identity); diff[i] = message_diff(new_i, old_i)
+void dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchunks, const void* partials, const void* old_msg, const int* has_old, int normalize,
+                      void* new_msg, double* diff) {
+    need_gpu();
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !chi || !nchunks || !partials || !new_msg || (old_msg && !has_old))
+        throw Err(TNQS_ERR_INVALID, "dbg_msg_finalize: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sP, sNew, sOld;
+    for (int i = 0; i < nitems; ++i) {
+        if (chi[i] < 1 || chi[i] > 128 || nchunks[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_msg_finalize: 1 <= chi <= 128, nchunks >= 1");
+        const size_t mb = (size_t)chi[i] * chi[i] * esz;
+        sP.add(mb * nchunks[i]); sNew.add(mb); sOld.add(mb);
+    }
+    sP.alloc(); sNew.alloc(); sOld.alloc();
+    DBuf dDiff(sizeof(double) * nitems), dF(sizeof(MsgFinalItem) * nitems);
+    std::vector<double> hdiff(nitems, 0.0); if (diff) std::copy(diff, diff + nitems, hdiff.begin());
+    std::vector<MsgFinalItem> fin(nitems);
+    size_t op = 0, om = 0;
+    for (int i = 0; i < nitems; ++i) {
+        sP.put(i, (const char*)partials + op); op += sP.len[i];
+        sNew.put(i, (const char*)new_msg + om);
+        const bool old = old_msg && has_old[i]; if (old) sOld.put(i, (const char*)old_msg + om);
+        om += sNew.len[i];
+        fin[i] = MsgFinalItem{sP.at(i), nchunks[i], chi[i], old ? sOld.at(i) : nullptr, sNew.at(i), diff ? (double*)dDiff.p + i : nullptr, normalize};
+    }
+    sP.up(); sNew.up(); sOld.up(); dDiff.up(hdiff.data(), sizeof(double) * nitems); dF.up(fin.data(), sizeof(MsgFinalItem) * nitems);
+    if (dtype == TNQS_C64) launch_msg_finalize<float>(nullptr, (const MsgFinalItem*)dF.p, nitems); else launch_msg_finalize<double>(nullptr, (const MsgFinalItem*)dF.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    sNew.down("new_msg");
+    om = 0;
+    for (int i = 0; i < nitems; ++i) { sNew.get(i, (char*)new_msg + om); om += sNew.len[i]; }
+    if (diff) dDiff.down(diff, sizeof(double) * nitems);
 }
 }  // namespace tnqs
