@@ -187,7 +187,7 @@ int tnqs_profile_reset(tnqs_handle h) {
 // ---- kernel-level debug entry points (include/tnqs_debug.h) ---------------------------------------------------
 #include "../../include/tnqs_debug.h"
 #include "kernels.hpp"
-namespace tnqs { void dbg_default_sequence(const State* s, std::vector<int>& src, std::vector<int>& dst);
+namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src, std::vector<int>& dst);
                  std::shared_ptr<Graph> dbg_make_graph(int nv, int ne, const int32_t* es, const int32_t* ed);
                  void dbg_default_sequence_graph(const Graph& g, std::vector<int>& src, std::vector<int>& dst, std::vector<int>& level);
                  void dbg_pair(int C0, int NMID, int NHI, const void* in, const void* Mx, const void* My, void* out);
@@ -215,7 +215,7 @@ namespace tnqs { void dbg_default_sequence(const State* s, std::vector<int>& src
                                        void* new_msg, double* diff); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
-    return guard([&] { std::vector<int> a, b; dbg_default_sequence(S(h), a, b); *n_out = (int)a.size();
+    return guard([&] { std::vector<int> a, b; dbg_default_sequence(*S(h)->g, a, b); *n_out = (int)a.size();
                        for (int i = 0; i < (int)a.size() && i < cap; ++i) { src[i] = a[i]; dst[i] = b[i]; } });
 }
 int tnqs_dbg_default_sequence_graph(int nv, int ne, const int32_t* esrc, const int32_t* edst, int* src, int* dst, int* level, int cap, int* n_out) {

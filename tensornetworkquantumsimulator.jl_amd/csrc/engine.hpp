@@ -8,6 +8,7 @@
 //   src/MessagePassing/abstractbeliefpropagationcache.jl:223-259   update
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <climits>
 #include <cstdint>
 #include <deque>
 #include <functional>
@@ -59,6 +60,23 @@ inline Buf sub_buffer(const Buf& parent, size_t off, size_t bytes) {
     Buf b = std::make_shared<DevBuf>(); b->p = reinterpret_cast<char*>(parent->p) + off; b->bytes = bytes; b->parent = parent; return b;
 }
 
+// The level schedule of a BP sweep order (bp_schedule.cpp): a function of the graph and the sequence alone.
+struct BPPlan {
+    std::vector<int> seq;                       // directed edge ids in sequence order
+    std::vector<std::vector<int>> levels;       // positions in seq grouped by dependency level
+    std::vector<int> pos_of;                    // de -> position in seq or -1
+    std::vector<int> level_of;                  // position -> level
+    bool in_place = false;                      // duplicates in the sequence: strictly sequential, single buffer
+    int nlev = 0;                               // levels.size()
+    std::vector<std::vector<int>> out_level, in_level;     // per site and leg: level of the outgoing / incoming message (-1: not in the sequence)
+    // levels from level `from` until level L comes round (next sweep when it lies behind); L == from: 0, a change inside the current level is not seen in it
+    int levels_until(int L, int from) const { return L > from ? L - from : (L < from ? nlev - from + L : 0); }
+    // the same for a USE at level L: one in the current level does not count, the next one is a whole sweep away
+    int levels_until_next(int L, int from) const { return L > from ? L - from : nlev - from + L; }
+    // levels until the message entering src through leg j changes again, seen from position t of the sequence (INT_MAX: never)
+    int horizon(int src, int j, int t) const { const int L = in_level[src][j]; return L < 0 ? INT_MAX : levels_until(L, level_of[t]); }
+};
+
 struct Graph {
     int nv = 0, ne = 0;
     std::vector<int> esrc, edst;
@@ -66,15 +84,19 @@ struct Graph {
     std::unordered_map<uint64_t, int> emap;
     bool is_tree = false;
     std::vector<int> ecolor; int ncolors = 0;     // deterministic greedy proper edge colouring
-    mutable std::vector<int> default_seq;         // default BP sweep order (engine.cpp default_sequence), built on first use
+    mutable std::vector<int> default_seq;         // default BP sweep order (bp_schedule.cpp default_sequence), built on first use
     mutable std::vector<int> default_set_starts;  // positions of default_seq where a set that may close cycles begins (empty: linear forests): a set's levels follow the previous set's
-    mutable std::shared_ptr<const void> default_plan;   // its level schedule (engine.cpp BPPlan), built on first use
-    mutable std::shared_ptr<const void> forest_plan;    // level schedule of the forest-cover order (n_sequence = -1), built on first use
+    mutable std::shared_ptr<const BPPlan> default_plan;   // its level schedule, built on first use (bp_schedule.cpp plan_for)
+    mutable std::shared_ptr<const BPPlan> forest_plan;    // level schedule of the forest-cover order (n_sequence = -1), built on first use
     mutable int spec_penalty = 0;                       // apply_gates: steps to run one step deep after a failed deferred verification (engine_gates.cpp); shared by the copies of a handle
     int edge(int u, int v) const;                 // -1 if absent
     int leg(int v, int w) const;                  // position of neighbour w in nbr[v], -1 if absent
     int dedge(int src, int dst) const;            // directed edge id 2*e + (src == edst[e]), -1 if absent
+    int src_of(int de) const { return (de & 1) ? edst[de / 2] : esrc[de / 2]; }       // the way back from dedge()
+    int dst_of(int de) const { return (de & 1) ? esrc[de / 2] : edst[de / 2]; }
 };
+// the plan of an update: explicit sequence (built per call) / forest cover / default (kept with the graph)
+std::shared_ptr<const BPPlan> plan_for(const Graph& g, const tnqs_bp_opts* o);
 
 struct ProfClass { int64_t launches = 0; double ms = 0, bytes = 0, flops = 0; };
 struct Prof {
@@ -180,7 +202,7 @@ struct State {
     ~State();
 };
 
-// ---- operations (implemented in engine.cpp, templated internally on the real type) ---------------------------
+// ---- operations (implemented in engine_*.cpp, templated internally on the real type) ---------------------------
 State* state_create(int nv, int ne, const int32_t* es, const int32_t* ed, const int32_t* sd, int dtype, int device);
 State* state_copy(const State* s);
 void state_set_site(State* s, int v, const void* host, int ndim, const int64_t* dims, const int32_t* role);

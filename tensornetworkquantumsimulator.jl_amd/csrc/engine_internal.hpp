@@ -1,7 +1,8 @@
 // engine_internal.hpp -- declarations shared by the translation units of the host engine:
 //   engine_core.cpp   pool, graph, state container, tensor / message I/O
 //   engine_batch.cpp  batched building blocks: mode-product chains, Gram jobs, the SVD batch
-//   engine_bp.cpp     BP update (default sequence, level schedule, message kernels)
+//   bp_schedule.cpp   BP sweep order: default sequence, forest-cover sequence, level schedule (BPPlan; host graph code, no device call)
+//   engine_bp.cpp     BP update: sweep driver (BpUpdate), the launches of one level (BpLevelBatch), products kept across levels (ProdCache)
 //   engine_gates.cpp  apply_gates scheduler, one- and two-site gate batches, truncate
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop

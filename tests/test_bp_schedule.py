@@ -1,5 +1,5 @@
 """Host-side logic of the BP update (no GPU): the library's default sweep order and the dependency levels it is launched in, read through the host-only
-entry point tnqs_dbg_default_sequence_graph (include/tnqs_debug.h; csrc/engine_bp.cpp default_sequence / sequence_levels).  The order must be an ordinary
+entry point tnqs_dbg_default_sequence_graph (include/tnqs_debug.h; csrc/bp_schedule.cpp default_sequence / sequence_levels).  The order must be an ordinary
 sequential one -- every directed edge exactly once (abstractbeliefpropagationcache.jl:204-218 sweeps `edge_sequence` in order) -- and the levels a valid
 schedule of it: a message that reads the NEW value of another one runs in a later level.  On top of that the structure the order is built for: both
 messages a site sends into a linear forest / an edge set that closes cycles leave in one level (one pass over the site tensor for two messages)."""

@@ -384,6 +384,29 @@ def test_bp_update_chi32_bulk_sites_matches_oracle(seq_name):
         assert abs(tn.expect(out2, ("Z", [v])) - o.expect_1site(oc2, Z, v)) < 2e-5
 
 
+@pytest.mark.parametrize("dtype,tol", [(np.complex64, 5e-5), (np.complex128, 1e-10)])
+def test_bp_update_with_repeated_messages_in_the_sequence_matches_oracle(dtype, tol):
+    """A sequence that lists a message more than once (BPPlan::in_place, csrc/bp_schedule.cpp make_plan): strictly sequential, one level per position, the new
+    value replaces the old at once and the diff is averaged over len(seq).  The reference sweeps the list as given (abstractbeliefpropagationcache.jl:223-259),
+    so does the oracle: messages elementwise after two sweeps without a tolerance, then three more with a tolerance that is not met (diff / len(seq))."""
+    g = tn.named_grid((3, 3))
+    psi = tn.random_tensornetworkstate(dtype, g, bond_dimension=3, seed=21)
+    seq = colour_sequence(g, tn.edge_color(g))
+    seq = seq + [seq[3], seq[0], seq[10], seq[3]]
+    assert len(set(seq)) == 2 * g.ne() and len(seq) == 2 * g.ne() + 4
+    kw = dict(maxiter=2, tolerance=None, edge_sequence=seq)
+    out = tn.update(tn.BeliefPropagationCache(psi), **kw)
+    oc = o.update(o.BeliefPropagationCache(to_oracle_state(psi)), **kw)
+    print("repeated messages, no tolerance:", np.dtype(dtype).name, compare_messages(out, oc, tol))
+    info, oinfo = {}, {}
+    kw = dict(maxiter=3, tolerance=1e-14, edge_sequence=seq)
+    out2 = tn.update(out, info=info, **kw)
+    oc2 = o.update(oc, info=oinfo, **kw)
+    print("repeated messages, tolerance:", np.dtype(dtype).name, compare_messages(out2, oc2, tol), info, oinfo)
+    assert info["niter"] == oinfo["niter"] == 3
+    assert abs(info["diff"] - oinfo["diff"]) < tol
+
+
 @pytest.mark.parametrize("lattice", ["hh11", "hh22", "ring6"])
 def test_small_sites_with_16_dimensional_legs_match_oracle(lattice):
     """heavy-hex sites at chi = 16 (BASELINE configs[2] per-site shape: 2 x 16^3 = 64 KiB, 2 x 16^2 at the degree-2 sites): the whole message of such a site is ONE
@@ -406,7 +429,7 @@ def test_small_sites_with_16_dimensional_legs_match_oracle(lattice):
 
 
 def sequence_levels(g, seq):
-    """dependency levels of a sequential sweep order (a message waits for the EARLIER messages that enter its source; engine_bp.cpp sequence_levels)"""
+    """dependency levels of a sequential sweep order (a message waits for the EARLIER messages that enter its source; bp_schedule.cpp sequence_levels)"""
     pos = {m: t for t, m in enumerate(seq)}
     level = []
     for t, (s, d) in enumerate(seq):
@@ -418,7 +441,7 @@ def sequence_levels(g, seq):
 @pytest.mark.parametrize("lattice", ["torus4x4_chi32", "cubic3_chi4", "ring5_chi6"])
 def test_default_order_on_periodic_lattices_matches_oracle(lattice):
     """Periodic lattices: the library's default order takes edge sets that close cycles (round a cycle every site but one sends both its
-    messages in one level, the last site both of its own in the next; engine_bp.cpp path_cycle_sequence) where that saves passes over the site
+    messages in one level, the last site both of its own in the next; bp_schedule.cpp path_cycle_sequence) where that saves passes over the site
     tensors.  It is still an ordinary sequential order: the oracle replaying it (abstractbeliefpropagationcache.jl:204-218) must reproduce the
     trajectory sweep by sweep, on the plane route (chi = 32 torus, every site of degree 4) and on the generic one."""
     g, chi = {"torus4x4_chi32": (tn.named_grid((4, 4), periodic=True), 32), "cubic3_chi4": (tn.named_grid((3, 3, 3), periodic=True), 4),
