@@ -96,6 +96,13 @@ int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n
  * (messages of one level are launched together; which value a message reads is decided by the positions).  HOST ONLY: no device is touched, so the scheduling
  * logic of the BP update -- linear forests, edge sets that close cycles on periodic lattices -- is testable without a GPU (tests/test_bp_schedule.py) */
 int tnqs_dbg_default_sequence_graph(int nv, int ne, const int32_t* esrc, const int32_t* edst, int* src, int* dst, int* level, int cap, int* n_out);
+/* the step schedule tnqs_apply_gates walks, from the graph and the gates' vertex lists alone (nverts[i] = 1 or 2 vertices of gate i, one list after the other in
+ * verts): steps are batches (maximal runs of pairwise vertex-disjoint gates, in list order) and BP updates (in front of a gate on two vertices that touches a
+ * vertex a gate has acted on since the last update, and once at the end; none when update_cache == 0 -- apply_gates.jl:64-95).  step_of_gate[i] = the step gate i
+ * runs in; step_is_bp[k] = 1 where step k is an update (the first cap steps); *nsteps_out = the number of steps.  Arity and vertex range are checked
+ * (TNQS_ERR_INVALID), adjacency is not.  HOST ONLY: no device is touched (tests/test_gate_schedule.py) */
+int tnqs_dbg_gate_schedule(int nv, int ne, const int32_t* esrc, const int32_t* edst, int ngates, const int32_t* nverts, const int32_t* verts, int update_cache,
+                           int* step_of_gate, int* step_is_bp, int cap, int* nsteps_out);
 #ifdef __cplusplus
 }
 #endif

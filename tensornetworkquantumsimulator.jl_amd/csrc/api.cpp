@@ -223,6 +223,14 @@ int tnqs_dbg_default_sequence_graph(int nv, int ne, const int32_t* esrc, const i
                        auto g = dbg_make_graph(nv, ne, esrc, edst); std::vector<int> a, b, l; dbg_default_sequence_graph(*g, a, b, l); *n_out = (int)a.size();
                        for (int i = 0; i < (int)a.size() && i < cap; ++i) { if (src) src[i] = a[i]; if (dst) dst[i] = b[i]; if (level) level[i] = l[i]; } });
 }
+int tnqs_dbg_gate_schedule(int nv, int ne, const int32_t* esrc, const int32_t* edst, int ngates, const int32_t* nverts, const int32_t* verts, int update_cache,
+                           int* step_of_gate, int* step_is_bp, int cap, int* nsteps_out) {
+    return guard([&] { if (nv < 0 || ne < 0 || (ne > 0 && (!esrc || !edst)) || ngates < 0 || (ngates > 0 && (!nverts || !verts)) || !nsteps_out) throw Err(TNQS_ERR_INVALID, "tnqs_dbg_gate_schedule: bad arguments");
+                       for (int i = 0, o = 0; i < ngates; o += nverts[i], ++i) { if (nverts[i] < 1 || nverts[i] > 2) throw Err(TNQS_ERR_INVALID, "tnqs_dbg_gate_schedule: only one- and two-site gates");
+                                                                                 for (int k = 0; k < nverts[i]; ++k) if (verts[o + k] < 0 || verts[o + k] >= nv) throw Err(TNQS_ERR_INVALID, "tnqs_dbg_gate_schedule: vertex out of range"); }
+                       auto g = dbg_make_graph(nv, ne, esrc, edst); const GateSchedule steps = build_gate_schedule(*g, ngates, nverts, verts, update_cache != 0); *nsteps_out = (int)steps.size();
+                       for (int k = 0; k < (int)steps.size(); ++k) { if (step_is_bp && k < cap) step_is_bp[k] = steps[k].is_bp ? 1 : 0; if (step_of_gate) for (int i = steps[k].begin; i < steps[k].end; ++i) step_of_gate[i] = k; } });
+}
 int tnqs_dbg_jacobi(int dtype, int m, int n, void* A, void* V, int* sweeps) { return guard([&] { dbg_jacobi(dtype, m, n, A, V, sweeps); }); }
 int tnqs_dbg_theta_svd_pre(int m, int n, int nq, void* A, const void* Q, void* V, int* sweeps, int copies, int reps, double* ms, double* phase_us, int cap) { return guard([&] { dbg_theta_svd_pre(m, n, nq, A, Q, V, sweeps, copies, reps, ms, phase_us, cap); }); }
 int tnqs_dbg_time_jacobi_f32(int m, int n, const void* A, int copies, int reps, double* ms, int* sweeps) { return guard([&] { dbg_time_jacobi_f32(m, n, A, copies, reps, ms, sweeps); }); }

@@ -88,7 +88,7 @@ struct Graph {
     mutable std::vector<int> default_set_starts;  // positions of default_seq where a set that may close cycles begins (empty: linear forests): a set's levels follow the previous set's
     mutable std::shared_ptr<const BPPlan> default_plan;   // its level schedule, built on first use (bp_schedule.cpp plan_for)
     mutable std::shared_ptr<const BPPlan> forest_plan;    // level schedule of the forest-cover order (n_sequence = -1), built on first use
-    mutable int spec_penalty = 0;                       // apply_gates: steps to run one step deep after a failed deferred verification (engine_gates.cpp); shared by the copies of a handle
+    mutable int spec_penalty = 0;                       // apply_gates: steps to run one step deep after a failed deferred verification (engine_runahead.cpp); shared by the copies of a handle
     int edge(int u, int v) const;                 // -1 if absent
     int leg(int v, int w) const;                  // position of neighbour w in nbr[v], -1 if absent
     int dedge(int src, int dst) const;            // directed edge id 2*e + (src == edst[e]), -1 if absent
@@ -97,6 +97,13 @@ struct Graph {
 };
 // the plan of an update: explicit sequence (built per call) / forest cover / default (kept with the graph)
 std::shared_ptr<const BPPlan> plan_for(const Graph& g, const tnqs_bp_opts* o);
+
+// The step schedule of an apply_gates call (gate_schedule.cpp): a function of the graph and the gates' vertex lists alone.
+struct GateStep { bool is_bp; int begin, end; };      // a batch: the gates [begin, end) of the caller's list, pairwise vertex-disjoint; a BP update: begin == end
+using GateSchedule = std::vector<GateStep>;
+struct State;
+void validate_gates(const State& s, int ngates, const int32_t* nverts, const int32_t* verts, std::vector<int>& voff, std::vector<size_t>& moff);
+GateSchedule build_gate_schedule(const Graph& g, int ngates, const int32_t* nverts, const int32_t* verts, bool update_cache);
 
 struct ProfClass { int64_t launches = 0; double ms = 0, bytes = 0, flops = 0; };
 struct Prof {
@@ -117,25 +124,15 @@ struct RcclComm {
     ~RcclComm();
 };
 
+constexpr int kCheckEvents = 16;      // events of pending checks (engine_internal.hpp: more than apply_gates ever leaves pending)
 struct HostArena {   // pinned staging for descriptor uploads, reset at host sync points
     char* base = nullptr; size_t cap = 0, off = 0;
     // pinned ring behind the arena proper: the staged read-backs of pending checks (State::checks) -- they outlive the arena's own resets
     char* ring = nullptr; size_t ring_cap = 0, ring_off = 0;
-    hipEvent_t cev[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; unsigned cevn = 0;
+    hipEvent_t cev[kCheckEvents] = {}; unsigned cevn = 0;      // the events of those checks, taken round robin and created on first use
 };
 
-// ---- deferred verification (round 6) ---------------------------------------------------------------------------------------------------
-// apply_gates runs ahead of the device: a gate batch whose outcome is predictable (every bond already at its cap: the new bond dimension is the cap, no
-// factorisation falls back) and a BP update that is expected to converge in its first sweep are ENQUEUED on those assumptions -- no host round trip in the
-// dependent launch chains -- and leave a Check behind: the staged copy of what decides the assumption, an event behind that copy, and the decision.  Site tensors
-// and messages are never mutated in place, so the state before any step is a vector of references (Snapshot); a check that fails (rare: a cutoff that bites at a
-// saturated bond, a collapsed pivot, a sweep that misses the tolerance) puts the snapshot back, drains the stream and runs the step again the careful way.
-// Checks are settled in order; every host synchronisation point of the path settles what is pending, and apply_gates settles everything before it returns.
-struct State;
-struct Snapshot {
-    std::vector<int> chi; std::vector<Buf> site, sscale, msg; std::vector<std::vector<double>> pend1; std::vector<char> unit_norm;
-    tnqs_apply_stats stats{}; bool real_io = false;
-};
+// what a step that apply_gates enqueued on assumptions leaves behind (deferred verification: engine_internal.hpp, engine_runahead.cpp)
 struct Check {
     int kind = 0;                          // 0: gate batch enqueued on assumptions; 1: BP update whose verdict is pending
     int step = 0;                          // step of the apply_gates schedule it belongs to
@@ -143,7 +140,6 @@ struct Check {
     hipEvent_t ev = nullptr;               // recorded behind the staged copy (HostArena::cev, not owned)
     std::function<bool(State*)> eval;      // true: the assumption held (results and statistics booked); false: roll back
 };
-struct SpecFailed { int kind, step, iters_done; };       // thrown by settle() for the first check that does not hold
 
 struct State {
     std::shared_ptr<Graph> g;
@@ -187,7 +183,7 @@ struct State {
     size_t keep_mark = 0;          // keepalive[0, keep_mark) belongs to phases that have ended: released at the next stream synchronisation (soft_sync)
     HostArena arena;               // this handle's pinned staging arena (taken from / returned to a small free list, engine_core.cpp)
     tnqs_apply_stats stats{};
-    std::deque<Check> checks;          // pending, oldest first (see Check above)
+    std::deque<Check> checks;          // pending, oldest first (see Check above; pushed by post_check only)
     int cur_step = -1;                 // apply_gates: the schedule step being executed (labels the checks it leaves behind)
 
     size_t esz() const { return dtype == TNQS_C64 ? 8 : 16; }

@@ -16,7 +16,6 @@ static int fused_leg(const State* s, const SD& sd, int jo) {
 
 static double default_tol(const State* s) { return s->dtype == TNQS_C64 ? 1e-5 : 1e-8; }   // beliefpropagationcache.jl:104-108
 static bool small_site_on() { static const bool v = !envflag("TNQS_NO_SMALL_SITE_BP"); return v; }
-static bool speculation_on() { static const bool v = !envflag("TNQS_NO_SPECULATION"); return v; }
 
 // ---- shared pair products ---------------------------------------------------------------------------------------
 // A degree-4 site sends four messages per sweep, each needing the other three incoming messages absorbed.  Its legs are
@@ -211,19 +210,15 @@ template <class T> struct BpUpdate {
         launch_sum_doubles(s->stream, reinterpret_cast<const double*>(d_diffs->p), (int)nseq, reinterpret_cast<double*>(d_sum->p));
         if (go_optimistic) {
             double* slot = reinterpret_cast<double*>(ring_alloc(s, sizeof(double)));       // (may settle older checks -- and throw -- first: nothing is committed yet)
-            HIPCHK(hipMemcpyAsync(slot, d_sum->p, sizeof(double), hipMemcpyDeviceToHost, s->stream));
-            Check c; c.kind = 1; c.step = s->cur_step; c.iters_done = iter; c.ev = check_event(s);
-            HIPCHK(hipEventRecord(c.ev, s->stream));
             const size_t nseq_ = nseq; const int maxiter_ = at.maxiter; const double tol_ = tol;
-            c.eval = [slot, tol_, nseq_, iter, maxiter_](State* st) {
+            post_check(s, reinterpret_cast<char*>(slot), d_sum->p, sizeof(double), /*kind=*/1, s->cur_step, iter, [slot, tol_, nseq_, iter, maxiter_](State* st) {
                 const double a = *slot / (double)nseq_;
                 st->stats.last_bp_diff = a;
                 if (a <= tol_) return true;
                 if (iter >= maxiter_) { st->stats.bp_not_converged += 1; return true; }      // the reference stops here too (and warns)
                 return false;
-            };
+            });
             s->keepalive.push_back(d_diffs); s->keepalive.push_back(d_sum);
-            s->checks.push_back(std::move(c));
             s->msg = cur; s->stats.n_bp_updates += 1;
             soft_sync(s);
             return BpVerdict::Deferred;

@@ -833,14 +833,11 @@ template <class T> struct TwoSiteBatch {
     // no host round trip: the results travel to the check's staging and are verified when they have arrived; the rest of the batch runs on what they are
     // expected to be -- every factor of full rank, every new bond dimension at its cap, no fallback taken
     void defer(char* stage) {
-        HIPCHK(hipMemcpyAsync(stage, d_rb->p, rb.total, hipMemcpyDeviceToHost, s->stream));
-        Check c; c.kind = 0; c.step = s->cur_step; c.ev = check_event(s);
-        HIPCHK(hipEventRecord(c.ev, s->stream));
         std::vector<GateBook> books(npg);
         for (int q = 0; q < npg; ++q) books[q] = book_of(q);
         std::vector<char> chol_site(sj.size(), 0);
         for (size_t i = 0; i < sj.size(); ++i) chol_site[i] = (part[i / 2] && is_chol[i]) ? 1 : 0;
-        c.eval = [st = (const char*)stage, L = rb, books = std::move(books), chol_site = std::move(chol_site), nenv = envs.size(), errs = errs, qr2 = qr2](State* z) {
+        post_check(s, stage, d_rb->p, rb.total, /*kind=*/0, s->cur_step, 0, [st = (const char*)stage, L = rb, books = std::move(books), chol_site = std::move(chol_site), nenv = envs.size(), errs = errs, qr2 = qr2](State* z) {
             const int* hi = L.info_of(st); const double* ht = L.terr_of(st); const int* fl = L.env_of(st); const int* cf = L.chol_of(st);
             for (size_t q = 0; q < books.size(); ++q) if (hi[8 * q + 2] != books[q].cap || hi[8 * q + 3] != 0 || (qr2 && hi[8 * q + 6] != 0)) return false;      // a bond below its cap, a failed gate, an ill-conditioned ComplexF64 site (second factorisation pass)
             for (size_t i = 0; i < nenv; ++i) if (!fl[2 * i] || fl[2 * i + 1]) return false;                                  // a rank-deficient message (projector pass), or a negative eigenvalue
@@ -850,8 +847,7 @@ template <class T> struct TwoSiteBatch {
                 if (errs) errs[books[q].index] = ht[q];
             }
             return true;
-        };
-        s->checks.push_back(std::move(c));
+        });
         for (size_t i = 0; i < envs.size(); ++i) { h_flags[2 * i] = 1; h_flags[2 * i + 1] = 0; }
         s->stats.n_spec_batches += 1;
     }
@@ -1090,7 +1086,7 @@ template <class T> struct TwoSiteBatch {
     }
 };
 
-// allow_spec: the batch may be enqueued WITHOUT its host round trip when its outcome is predictable (TwoSiteBatch::may_defer); it then leaves a Check behind (engine.hpp)
+// allow_spec: the batch may be enqueued WITHOUT its host round trip when its outcome is predictable (TwoSiteBatch::may_defer); it then leaves a Check behind (engine_internal.hpp)
 template <class T> static void apply_two_site_batch(State* s, const std::vector<Gate2>& gates_in, const tnqs_apply_opts& ao, double* errs, bool allow_spec = false) {
     if (gates_in.empty()) return;
     TwoSiteBatch<T> b(s, gates_in, ao, errs, allow_spec);
@@ -1121,134 +1117,36 @@ template <class T> static void apply_two_site_batch(State* s, const std::vector<
 // ---------------------------------------------------------------------------------------------------------------
 // apply_gates (src/Apply/apply_gates.jl:46-98)
 // ---------------------------------------------------------------------------------------------------------------
-// The walk over the gate list -- which gates form a batch, where a BP update is due -- depends on the gate list alone (apply_gates.jl:64-90: vertex sets), not on
-// any number computed on the way.  So the SCHEDULE is built first: steps = maximal runs of pairwise-disjoint gates ("batch") and the cache updates between them
-// ("bp"), in the reference's order.  It is then executed AHEAD of the device (engine.hpp: Check): a batch whose outcome is predictable and an update expected to
-// converge in one sweep are enqueued without waiting for their results, the state in front of every step is remembered as a vector of references, and a step
-// whose deferred verification fails is run again the careful way from that state.  Results are those of the sequential walk either way.
-struct Step { bool is_bp = false; std::vector<Gate1> b1; std::vector<Gate2> b2; };
-
+// Options, validation and the step schedule (gate_schedule.cpp: a function of the vertex lists alone); the schedule is then executed AHEAD of the device by
+// the run-ahead driver (engine_runahead.cpp), which is handed the two kinds of step: a batch of gates of the list, a BP update.
 template <class T> static void apply_gates_t(State* s, int ngates, const int32_t* nverts, const int32_t* verts, const double* mats,
                                              const tnqs_apply_opts* opts, const tnqs_bp_opts* bp, double* errs) {
-    const Graph& g = *s->g;
     HIPCHK(hipSetDevice(s->device));
     tnqs_apply_opts ao; ao.maxdim = 0; ao.cutoff = -1; ao.normalize_tensors = 1; ao.sqrt_cutoff = -1; ao.update_cache = 1;
     if (opts) ao = *opts;
-    // validation first (apply_gates.jl:109-120): nothing is mutated when an argument is bad
-    std::vector<int> voff(ngates + 1, 0); std::vector<size_t> moff(ngates + 1, 0);
-    for (int i = 0; i < ngates; ++i) {
-        int nv = nverts[i];
-        if (nv < 1 || nv > 2) throw Err(TNQS_ERR_INVALID, "apply_gate!: only one- and two-site gates are supported; received a gate acting on " + std::to_string(nv) + " vertices.");
-        voff[i + 1] = voff[i] + nv;
-        size_t dd = 1;
-        for (int k = 0; k < nv; ++k) { int v = verts[voff[i] + k]; if (v < 0 || v >= g.nv) throw Err(TNQS_ERR_INVALID, "apply_gates: vertex out of range");
-                                       if (s->projected[v]) throw Err(TNQS_ERR_INVALID, "apply_gates: vertex " + std::to_string(v) + " was projected onto a configuration (tnqs_project_site: its site dimension is 1); gates cannot act on it");
-                                       dd *= s->d[v]; }
-        moff[i + 1] = moff[i] + 2 * dd * dd;
-        if (nv == 2) {
-            int a = verts[voff[i]], b = verts[voff[i] + 1];
-            if (a == b || g.edge(a, b) < 0)
-                throw Err(TNQS_ERR_INVALID, "apply_gate!: cannot apply a two-site gate on the non-adjacent vertices " + std::to_string(a) + " and " + std::to_string(b) +
-                                                ". Simple update requires the two sites to share an edge of the tensor-network graph.");
-        }
-    }
+    std::vector<int> voff; std::vector<size_t> moff;
+    validate_gates(*s, ngates, nverts, verts, voff, moff);
     if (errs) std::fill(errs, errs + ngates, 0.0);
     if (s->real_io) {       // adapt_gate (apply_gates.jl:41-44): a real gate takes the state's real type, a complex gate stays complex and promotes
         bool cplx = false;
         for (size_t k = 1; k < moff[ngates] && !cplx; k += 2) cplx = mats[k] != 0.0;
         if (cplx) s->real_io = false;
     }
-    // ---- the schedule (vertex flags instead of std::set: this walk sits in front of the first kernel of a call) ----------------------------------------
-    struct VSet { std::vector<char> f; std::vector<int> l; explicit VSet(int n) : f(n, 0) {} bool count(int v) const { return f[v] != 0; }
-                  void insert(int v) { if (!f[v]) { f[v] = 1; l.push_back(v); } } void clear() { for (int v : l) f[v] = 0; l.clear(); } };
-    std::vector<Step> steps;
-    {
-        VSet affected(g.nv), batch_verts(g.nv);
-        Step cur;
-        auto flush = [&]() { if (!cur.b1.empty() || !cur.b2.empty()) { steps.push_back(std::move(cur)); cur = Step{}; } };
-        for (int i = 0; i < ngates; ++i) {
-            const int nv = nverts[i]; const int32_t* vs = verts + voff[i];
-            bool need = false;
-            if (nv >= 2) for (int k = 0; k < nv; ++k) need = need || affected.count(vs[k]);            // apply_gates.jl:68
-            if (ao.update_cache && need) {
-                flush(); batch_verts.clear();
-                Step u; u.is_bp = true; steps.push_back(std::move(u));                                 // :76
-                affected.clear();                                                                      // :78
-            }
-            bool overlap = false;
-            for (int k = 0; k < nv; ++k) overlap = overlap || batch_verts.count(vs[k]);
-            if (overlap) { flush(); batch_verts.clear(); }
-            if (nv == 1) cur.b1.push_back(Gate1{vs[0], mats + moff[i]}); else cur.b2.push_back(Gate2{vs[0], vs[1], mats + moff[i], i});
-            for (int k = 0; k < nv; ++k) { batch_verts.insert(vs[k]); affected.insert(vs[k]); }         // :88-90
+    const GateSchedule steps = build_gate_schedule(*s->g, ngates, nverts, verts, ao.update_cache != 0);
+    auto batch = [&](const GateStep& st, bool ahead) {
+        std::vector<Gate1> b1; std::vector<Gate2> b2;
+        for (int i = st.begin; i < st.end; ++i) {
+            const int32_t* vs = verts + voff[i];
+            if (nverts[i] == 1) b1.push_back(Gate1{vs[0], mats + moff[i]}); else b2.push_back(Gate2{vs[0], vs[1], mats + moff[i], i});
         }
-        flush();
-        if (ao.update_cache) { Step u; u.is_bp = true; steps.push_back(std::move(u)); }                 // :93-95
-    }
-    struct InApply { State* s; explicit InApply(State* st) : s(st) { s->in_apply = true; } ~InApply() { s->in_apply = false; s->cur_step = -1; } } in_apply_guard(s);
-    // ---- how far ahead?  Running ahead keeps the state in front of every unverified step alive (the site tensors a batch replaced): up to a layer's worth of
-    // extra copies.  Handles with more than 2 GiB of site tensors stay one step deep -- the round-5 flow: a batch reads its results back, an update
-    // leaves its verdict pending until the next batch has prepared itself --, and so does a handle on which a verification failed a moment ago
-    // (Graph::spec_penalty, shared by the copies of a handle: an evolution whose updates need several sweeps would throw away a batch per update otherwise).
-    size_t own_bytes = 0; for (auto& b : s->site) if (b) own_bytes += b->bytes;
-    size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) != hipSuccess) tot = 0;
-    static const bool spec_off = envflag("TNQS_NO_SPECULATION");
-    (void)fr; (void)tot;
-    // (measured, round 6: heavy-hex 3.0 -> 2.6 ms per layer, 7 x 7 unchanged -- its launch chain is 97 % busy either way --, 20 x 20 112.6 against 111.5 ms and 37 against
-    //  22 GiB at the peak: where the tensor passes fill the device there is no idle time to win, only memory to lose.  Hence the bound: 2 GiB of site tensors)
-    const bool deep = !spec_off && !s->sharded() && own_bytes <= (size_t(2) << 30);
-    const size_t nst = steps.size();
-    std::vector<std::unique_ptr<Snapshot>> snaps(nst + 1);
-    size_t k = 0; bool careful = false;
-    auto drop_old_snaps = [&]() { const size_t keep_from = s->checks.empty() ? k : (size_t)std::max(0, s->checks.front().step); for (size_t q = 0; q < keep_from && q < snaps.size(); ++q) snaps[q].reset(); };
-    // after SpecFailed: nothing enqueued behind the failed step may leave a trace -- drain, drop the younger checks, put the state back
-    auto recover = [&](const SpecFailed& f) {
-        HIPCHK(hipStreamSynchronize(s->stream)); if (s->aux_stream) HIPCHK(hipStreamSynchronize(s->aux_stream));
-        drained(s); drop_checks(s);
-        const tnqs_apply_stats st_now = s->stats;
-        g.spec_penalty = 12;
-        if (f.kind == 0) {                          // a gate batch: back to the state in front of it, run it the careful way
-            restore_snapshot(s, *snaps[f.step]);
-            k = (size_t)f.step; careful = true;
-        } else {                                    // a BP update whose first sweep missed the tolerance: the state right behind that sweep, then the remaining sweeps
-            if ((size_t)f.step + 1 < snaps.size() && snaps[f.step + 1]) restore_snapshot(s, *snaps[f.step + 1]);
-            s->cur_step = f.step;
-            bp_update_t<T>(s, bp, nullptr, nullptr, false, f.iters_done);
-            k = (size_t)f.step + 1; careful = false;
-        }
-        s->stats.n_spec_redone = st_now.n_spec_redone + 1;
-        for (size_t q = k + 1; q < snaps.size(); ++q) snaps[q].reset();
+        apply_one_site_batch<T>(s, b1, ao.normalize_tensors != 0, false);
+        apply_two_site_batch<T>(s, b2, ao, errs, /*allow_spec=*/ahead);
+        s->stats.n_batches += 1;
+        soft_sync(s);
     };
-    try {
-        while (k < nst || !s->checks.empty()) {
-            try {
-                if (k >= nst) { settle(s, true); break; }
-                Step& st = steps[k];
-                s->cur_step = (int)k;
-                const bool ahead = deep && g.spec_penalty == 0 && !careful;
-                if (deep || !s->checks.empty()) snaps[k] = std::make_unique<Snapshot>(take_snapshot(s));
-                if (st.is_bp) {
-                    bp_update_t<T>(s, bp, nullptr, nullptr, /*optimistic=*/true);
-                } else {
-                    apply_one_site_batch<T>(s, st.b1, ao.normalize_tensors != 0, false);
-                    apply_two_site_batch<T>(s, st.b2, ao, errs, /*allow_spec=*/ahead);
-                    s->stats.n_batches += 1;
-                    soft_sync(s);
-                }
-                careful = false; ++k;
-                if (g.spec_penalty > 0 && s->checks.empty()) g.spec_penalty -= 1;
-                if (!ahead && s->checks.size() > 1) settle(s, true);        // one step deep: at most the verdict of the update just enqueued stays pending
-                else if (s->checks.size() >= 12) settle(s, true);
-                else settle(s, false);
-                drop_old_snaps();
-            } catch (const SpecFailed& f) { recover(f); }
-        }
-    } catch (...) {
-        // an error of a step: what is still unverified is settled -- or rolled back to the last verified state -- before the handle is handed back; the first error wins
-        try { settle(s, true); }
-        catch (const SpecFailed& f) { (void)hipStreamSynchronize(s->stream); drop_checks(s); if (f.step >= 0 && (size_t)f.step < snaps.size() && snaps[f.step + (f.kind ? 1 : 0)]) restore_snapshot(s, *snaps[f.step + (f.kind ? 1 : 0)]); }
-        catch (...) { drop_checks(s); }
-        throw;
-    }
+    auto update = [&](int iters_before) { bp_update_t<T>(s, bp, nullptr, nullptr, /*optimistic=*/iters_before == 0, iters_before); };
+    RunAhead run_ahead(s, steps, batch, update);
+    run_ahead.run();
     if (s->sharded()) materialize_pending_all(s);      // sharded: nothing stays pending between calls (State::in_apply)
     sync(s);                                                                                        // the call returns with the stream drained
 }

@@ -3,7 +3,9 @@
 //   engine_batch.cpp  batched building blocks: mode-product chains, Gram jobs, the SVD batch
 //   bp_schedule.cpp   BP sweep order: default sequence, forest-cover sequence, level schedule (BPPlan; host graph code, no device call)
 //   engine_bp.cpp     BP update: sweep driver (BpUpdate), the launches of one level (BpLevelBatch), products kept across levels (ProdCache)
-//   engine_gates.cpp  apply_gates scheduler, one- and two-site gate batches, truncate
+//   gate_schedule.cpp apply_gates: validation of the gate list, the step schedule (GateSchedule; host code, no device call)
+//   engine_runahead.cpp  deferred verification: checks, snapshots, the driver that runs a GateSchedule ahead of the device (RunAhead)
+//   engine_gates.cpp  apply_gates, one- and two-site gate batches, truncate
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
 //   sharding.cpp      exchange step (RCCL or host callback)
@@ -48,10 +50,10 @@ TNQS_SWITCH(use_precond_svd, !envflag("TNQS_NO_PRECOND_SVD"))    // low-rank the
 TNQS_SWITCH(use_small_svd, !envflag("TNQS_NO_SMALLSVD"))         // sites with fewer fibers than columns: Gram + eigen instead of the direct SVD
 TNQS_SWITCH(defer_site1, !envflag("TNQS_NO_DEFER_1SITE"))        // unitary one-site gates are applied in a pass of their own instead of being carried to the next two-site gate
 TNQS_SWITCH(use_chi64, !envflag("TNQS_NO_CHI64"))                // the chi = 64 kernel family (kernels_chi64.hip: register-direct fiber GEMM, 64 x 64 / 128 x 128 Grams, packed Cholesky, Cholesky-QR theta SVD)
+TNQS_SWITCH(speculation_on, !envflag("TNQS_NO_SPECULATION"))     // apply_gates never runs ahead of the device: every batch reads its results back, every BP update waits for its verdict
 #undef TNQS_SWITCH
 // TNQS_NO_BF16X3=1 (launch_util.hpp): the chi = 32 / 64 plane kernels on v_mfma_f32_32x32x2_f32 instead of the bf16 matrix cores with exact three-way operand splits
 //                   (kernels_x3.hip; bench.py's A/B leg);
-// TNQS_NO_SPECULATION=1 (engine_gates.cpp): apply_gates never runs ahead of the device -- every batch reads its results back, every BP update waits for its verdict;
 // TNQS_NO_SMALL_SITE_BP=1 (engine_bp.cpp): sites of at most 8192 elements take the generic chain + Gram route instead of the one-kernel LDS-resident message;
 // TNQS_JACOBI_GLOBAL=1: every Jacobi factorisation in the global-memory kernel (the route matrices beyond the LDS take);
 // tunables: TNQS_ARENA_KB (pinned staging arena; tests of its overflow path), TNQS_BP_WS_MB (workspace bound of a BP sub-batch), TNQS_BP_CACHE_MB, TNQS_RCCL_LIB (sharding.cpp),
@@ -263,46 +265,63 @@ void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail = nullp
 // update has already run (the continuation after a verdict turned out negative)
 template <class T> void bp_update_t(State* s, const tnqs_bp_opts* o, int* niter_out, double* diff_out, bool optimistic = false, int iters_before = 0);
 
-// ---- deferred verification (engine.hpp: Check, Snapshot) ---------------------------------------------------------------------------------
+// ---- deferred verification (round 6; engine_runahead.cpp) ---------------------------------------------------------------------------------
+// apply_gates runs ahead of the device: a gate batch whose outcome is predictable (every bond already at its cap: the new bond dimension is the cap, no
+// factorisation falls back) and a BP update that is expected to converge in its first sweep are ENQUEUED on those assumptions -- no host round trip in the
+// dependent launch chains -- and leave a Check behind: the staged copy of what decides the assumption, an event behind that copy, and the decision.  Site tensors
+// and messages are never mutated in place, so the state before any step is a vector of references (Snapshot); a check that fails (rare: a cutoff that bites at a
+// saturated bond, a collapsed pivot, a sweep that misses the tolerance) puts the snapshot back, drains the stream and runs the step again the careful way.
+// Checks are settled in order; every host synchronisation point of the path settles what is pending, and apply_gates settles everything before it returns.
+constexpr size_t kMaxPendingChecks = 12;      // apply_gates waits for the oldest check before it leaves more than this many pending
+static_assert(kMaxPendingChecks < (size_t)kCheckEvents, "a pending check's event must not be handed out again (HostArena::cev is a ring)");
+constexpr int kPenaltySteps = 12;             // steps a handle and its copies run one step deep after a failed verification (Graph::spec_penalty)
+// Running ahead keeps the state in front of every unverified step alive (the site tensors a batch replaced): up to a layer's worth of extra copies.  Handles with
+// more site tensors than this stay one step deep.  (measured, round 6: heavy-hex 3.0 -> 2.6 ms per layer, 7 x 7 unchanged -- its launch chain is 97 % busy either
+// way --, 20 x 20 112.6 against 111.5 ms and 37 against 22 GiB at the peak: where the tensor passes fill the device there is no idle time to win, only memory to lose)
+constexpr size_t kRunAheadMaxSiteBytes = size_t(2) << 30;
+
+struct Snapshot {      // everything of a State that a step of apply_gates replaces
+    std::vector<int> chi; std::vector<Buf> site, sscale, msg; std::vector<std::vector<double>> pend1; std::vector<char> unit_norm;
+    tnqs_apply_stats stats{}; bool real_io = false;
+    explicit Snapshot(const State& s) : chi(s.chi), site(s.site), sscale(s.sscale), msg(s.msg), pend1(s.pend1), unit_norm(s.unit_norm), stats(s.stats), real_io(s.real_io) {}
+    void restore(State& s) const { s.chi = chi; s.site = site; s.sscale = sscale; s.msg = msg; s.pend1 = pend1; s.unit_norm = unit_norm; s.stats = stats; s.real_io = real_io; }
+};
+struct SpecFailed { int kind, step, iters_done; };       // thrown by settle() for the first check that does not hold (the fields of its Check)
+
 // Evaluate the pending checks, oldest first.  block: wait for each; otherwise stop at the first whose event has not fired.  The first check that does not
-// hold is removed and thrown as SpecFailed -- the caller (apply_gates_t) drains the stream, drops the younger checks and puts the snapshot back.  Call it only
+// hold is removed and thrown as SpecFailed -- the caller (RunAhead) drains the stream, drops the younger checks and puts the snapshot back.  Call it only
 // where nothing of the State has been replaced since the last consistent point, or where a snapshot covers what has.
-inline void settle(State* s, bool block) {
-    while (!s->checks.empty()) {
-        Check& c = s->checks.front();
-        if (block) HIPCHK(hipEventSynchronize(c.ev));
-        else { const hipError_t q = hipEventQuery(c.ev); if (q == hipErrorNotReady) return; HIPCHK(q); }
-        const bool ok = c.eval(s);
-        const SpecFailed f{c.kind, c.step, c.iters_done};
-        s->checks.pop_front();
-        if (s->checks.empty()) s->arena.ring_off = 0;
-        if (!ok) throw f;
-    }
-}
-// `bytes` of pinned staging for a check's read-back (valid until the check is settled); makes room by settling what is pending when the ring is full
-inline char* ring_alloc(State* s, size_t bytes) {
-    HostArena& ar = s->arena;
-    if (!ar.base) ar = acquire_arena();
-    const size_t b = round256(std::max<size_t>(bytes, 1));
-    if (b > ar.ring_cap) return nullptr;                                   // (the caller takes the careful route)
-    if (ar.ring_off + b > ar.ring_cap) { settle(s, true); ar.ring_off = 0; }
-    char* p = ar.ring + ar.ring_off; ar.ring_off += b; return p;
-}
-// the event a new check records behind its staged copy (a ring of 16: apply_gates never leaves more than 12 checks pending)
-inline hipEvent_t check_event(State* s) {
-    HostArena& ar = s->arena;
-    if (!ar.base) ar = acquire_arena();
-    hipEvent_t& e = ar.cev[ar.cevn++ & 15];
-    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return e;
-}
-inline Snapshot take_snapshot(const State* s) {
-    Snapshot n; n.chi = s->chi; n.site = s->site; n.sscale = s->sscale; n.msg = s->msg; n.pend1 = s->pend1; n.unit_norm = s->unit_norm; n.stats = s->stats; n.real_io = s->real_io; return n;
-}
-inline void restore_snapshot(State* s, const Snapshot& n) {
-    s->chi = n.chi; s->site = n.site; s->sscale = n.sscale; s->msg = n.msg; s->pend1 = n.pend1; s->unit_norm = n.unit_norm; s->stats = n.stats; s->real_io = n.real_io;
-}
+void settle(State* s, bool block);
+// `bytes` of pinned staging for a check's read-back (valid until the check is settled); makes room by settling what is pending when the ring is full -- so it may
+// throw SpecFailed: call it before anything is enqueued on assumptions.  nullptr: too large for the ring (the caller takes the careful route)
+char* ring_alloc(State* s, size_t bytes);
+// Leave a check behind: the copy of `bytes` at dsrc into `stage` (from ring_alloc) is enqueued, an event taken and recorded behind it, the Check pushed
+void post_check(State* s, char* stage, const void* dsrc, size_t bytes, int kind, int cur_step, int iters_done, std::function<bool(State*)> eval);
 // drop every pending check unevaluated (the stream has been drained, a snapshot is about to be put back)
-inline void drop_checks(State* s) { s->checks.clear(); s->arena.ring_off = 0; }
+void drop_checks(State* s);
+
+// Executes a GateSchedule AHEAD of the device: a batch whose outcome is predictable and an update expected to converge in one sweep are enqueued without waiting
+// for their results, the state in front of every unverified step is remembered, and a step whose check fails is run again the careful way from that state.
+// Results are those of the sequential walk either way.
+struct RunAhead {
+    using BatchFn = std::function<void(const GateStep&, bool ahead)>;      // one batch step; ahead: it may leave a Check instead of reading its results back
+    using UpdateFn = std::function<void(int iters_before)>;               // a BP update; 0: optimistic (its verdict may stay a Check), n > 0: the sweeps after the first n
+    RunAhead(State* s, const GateSchedule& steps, BatchFn batch, UpdateFn update);
+    void run();      // returns with every check settled; on an error the handle holds the last verified state it could be put back to
+private:
+    State* const s; const Graph& g; const GateSchedule& steps; const BatchFn batch; const UpdateFn update;
+    struct InApply { State* s; explicit InApply(State* st) : s(st) { s->in_apply = true; } ~InApply() { s->in_apply = false; s->cur_step = -1; } } in_apply;
+    const bool deep;                                     // the depth policy of the call: false = one step deep (sharded, large, or switched off)
+    std::vector<std::unique_ptr<Snapshot>> snaps;        // snaps[k]: the state in front of step k, kept while a check of step k - 1 or later is pending
+    size_t k = 0; bool careful = false;                  // the step to run next; careful: it failed its check a moment ago
+    bool ahead() const { return deep && g.spec_penalty == 0 && !careful; }
+    void step();
+    void snapshot_in_front();
+    void settle_behind(bool was_ahead);
+    void drop_old_snaps();
+    const Snapshot* snapshot_for(const SpecFailed& f) const;
+    void recover(const SpecFailed& f);
+    void unwind();
+};
 
 }  // namespace tnqs

@@ -328,3 +328,54 @@ def test_a_failing_batch_leaves_the_state_as_it_was():
         "print('ok')\n") % (sys.path,)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-1500:] + r.stderr[-3000:]
+
+
+def test_an_error_behind_a_batch_that_ran_ahead_leaves_the_same_state_as_the_careful_walk():
+    """the C ABI called IN PLACE, update_cache = 0, two batches: two Rzz gates on disjoint edges of a saturated 4 x 4 grid (the batch runs ahead and leaves a
+    check), then a gate that overlaps them -- a second batch -- together with a gate on an edge (a, b) next to a message with a negative eigenvalue (DomainError in
+    the reference, src/utils.jl:21).  With and without TNQS_NO_SPECULATION the call returns the same error, and the handle is bit for bit the same afterwards:
+    the state behind the first batch (compared with a copy that only ran that batch), so everything of the second batch that the first did not touch is what it
+    was before the call.  (tnqs_apply_gates does not fill its stats out-parameter when it returns an error, so that the first batch did run ahead cannot be
+    asserted here; in this circuit the second batch is enqueued on assumptions as well, its check fails, and the error is thrown by the careful re-run.)"""
+    code = (
+        "import sys, json, hashlib, ctypes as C; sys.path[:0] = %r\n"
+        "import numpy as np, tnqs_amd as tn\n"
+        "from tnqs_amd import core, _lib as L\n"
+        "g = tn.named_grid((4, 4))\n"
+        "bpc = tn.update(tn.BeliefPropagationCache(tn.random_tensornetworkstate(np.complex64, g, bond_dimension=4, seed=3)), maxiter=10, tolerance=None)\n"
+        "one = [('Rzz', [(1, 1), (1, 2)], 0.3), ('Rzz', [(3, 1), (3, 2)], 0.3)]\n"
+        "a, b, w = (3, 3), (3, 4), (2, 3)\n"
+        "two = [('Rzz', [(1, 2), (1, 3)], 0.3), ('Rzz', [a, b], 0.3)]\n"
+        "assert w in g.neighbors(a) and not {w, a, b} & {v for gate in one for v in gate[1]}\n"
+        "bpc.setmessage((w, a), np.diag([1.0, 0.5, 0.2, -0.3]).astype(np.complex64))\n"
+        "des = list(g.edges) + [(y, x) for (x, y) in g.edges]\n"
+        "state = lambda c: ({v: c.tensor(v) for v in g.vertices}, {e: c.message(e) for e in des}, {e: c.bond_dim(*e) for e in g.edges})\n"
+        "before = state(bpc)\n"
+        "kw = dict(maxdim=4, cutoff=1e-10, normalize_tensors=True)\n"
+        "first, _ = tn.apply_gates(one, bpc, apply_kwargs=kw, update_cache=False)\n"
+        "ng, nv_a, nv_p, vs_a, vs_p, mat_a = core._marshal_circuit(one + two, g)\n"
+        "ao = core._apply_opts(kw, False); ao.update_cache = 0\n"
+        "bo, keep = core._bp_opts(g, dict(maxiter=1, tolerance=None))\n"
+        "errs = np.zeros(ng); st = L.ApplyStats()\n"
+        "rc = L.lib.tnqs_apply_gates(bpc._h, ng, nv_p, vs_p, mat_a.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ao), C.byref(bo), errs.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st))\n"
+        "msg = L.lib.tnqs_last_error().decode()\n"
+        "assert rc != 0, rc\n"
+        "after, ref = state(bpc), state(first)\n"
+        "for k in range(2):\n"
+        "    for key in after[k]: assert np.array_equal(after[k][key], ref[k][key]), key\n"
+        "assert after[2] == ref[2]\n"
+        "for v in {v for gate in two for v in gate[1]} - {v for gate in one for v in gate[1]}: assert np.array_equal(after[0][v], before[0][v]), v\n"
+        "for (x, y) in [tuple(gate[1]) for gate in two]:\n"
+        "    for e in ((x, y), (y, x)): assert np.array_equal(after[1][e], before[1][e]), e\n"
+        "h = hashlib.sha256()\n"
+        "for k in range(2):\n"
+        "    for key in sorted(after[k]): h.update(np.ascontiguousarray(after[k][key]).tobytes())\n"
+        "print(json.dumps(dict(rc=rc, msg=msg, digest=h.hexdigest(), dims=sorted(after[2].values()))))\n") % (sys.path,)
+    out = {}
+    for mode, env in (("ahead", {}), ("careful", {"TNQS_NO_SPECULATION": "1"})):
+        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (mode, r.stdout[-1500:] + r.stderr[-3000:])
+        out[mode] = json.loads(r.stdout.strip().splitlines()[-1])
+        print(mode, out[mode])
+    assert out["ahead"]["rc"] == out["careful"]["rc"] != 0 and out["ahead"]["msg"] == out["careful"]["msg"] and "negative eigenvalue" in out["ahead"]["msg"]
+    assert out["ahead"]["digest"] == out["careful"]["digest"] and out["ahead"]["dims"] == out["careful"]["dims"]
