@@ -9,7 +9,7 @@ extern "C" {
 #endif
 /* one-sided Jacobi on A (m x n): on return A = U*Sigma (columns), V (n x n) with A_in = (U Sigma) V^dagger. dtype: 0 c64, 1 c128 */
 int tnqs_dbg_jacobi(int dtype, int m, int n, void* A_inout, void* V_out, int* sweeps_out);
-/* preconditioned theta SVD kernel (kernels.hip theta_svd_pre_kernel) on one ComplexF32 factor A (m x n, 2 <= n <= 64, n <= nq <= m <= 128) of theta = A Q^T with Q
+/* preconditioned theta SVD kernel (kernels_svd.hip theta_svd_pre_kernel) on one ComplexF32 factor A (m x n, 2 <= n <= 64, n <= nq <= m <= 128) of theta = A Q^T with Q
  * (nq x n complex128, orthonormal columns): on return A = U Sigma (columns, any order), V (nq x n ComplexF32) = right singular vectors of theta in the same column
  * order.  reps > 0: also the average duration (ms, HIP events) of a launch over `copies` device-resident copies */
 int tnqs_dbg_theta_svd_pre(int m, int n, int nq, void* A_inout, const void* Q, void* V_out, int* sweeps_out, int copies, int reps, double* ms_out, double* phase_us_out /* 6 doubles or NULL: load, Gram, Cholesky + conversion, sweeps, U Sigma, V */,
@@ -73,7 +73,7 @@ int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, cons
  * A_i (m[i] x n[i], 2 <= n <= 128, n <= m <= 256): A_i <- U Sigma (columns); chol_fail[i]: a Cholesky pivot was refused; polished[i]: the polishing sweeps
  * ran on the item; sweeps[i]: sweeps of the Jacobi on R (each output array may be NULL) */
 int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps);
-/* the whole BP message of a small site (kernels.hip bp_small_site_kernel<1024>): ONE launch over nitems (site, outgoing leg) pairs, sized by the largest item as
+/* the whole BP message of a small site (kernels_bp.hip bp_small_site_kernel<1024>): ONE launch over nitems (site, outgoing leg) pairs, sized by the largest item as
  * the engine sizes it.  Item i is a site tensor [d[i]][chi_0]..[chi_{z[i]-1}] (column-major) with the outgoing leg jo[i]; chi, present: the items' legs one after
  * the other; psi: the items' tensors one after the other; M: one chi_k x chi_k matrix M[q + chi_k qo] per leg of every item, in leg order (the slot of leg jo
  * included: the kernel has to skip it), read only where present[leg] != 0 -- 0 hands the kernel a null pointer, i.e. the identity.  On the device every tensor and
@@ -85,7 +85,7 @@ int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol
  * NULL): TNQS_DBG_ROUTE_SMALL_* per item.  z > 8, a leg > 32 or more than 8192 elements: TNQS_ERR_UNSUPPORTED, nothing is written */
 int tnqs_dbg_small_site(int nitems, const int* d, const int* z, const int* chi, const int* jo, const void* psi, const void* M, const int* present, int form,
                         const void* old_msg, const int* has_old, int normalize, void* out, void* new_msg, double* diff_out, int* route_out);
-/* the BP message epilogue (kernels.hip msg_finalize_kernel<T>; dtype 0 c64, 1 c128): ONE launch over nitems messages.  Item i: nchunks[i] partials of chi[i]^2
+/* the BP message epilogue (kernels_bp.hip msg_finalize_kernel<T>; dtype 0 c64, 1 c128): ONE launch over nitems messages.  Item i: nchunks[i] partials of chi[i]^2
  * numbers laid out [chunk][element], the items one after the other; new_msg_i = their sum, divided by its element sum when normalize != 0 and that sum is not
  * exactly zero; diff_out[i] = message_diff(new_msg_i, old_msg_i) (the identity where has_old[i] == 0 or old_msg == NULL) */
 int tnqs_dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchunks, const void* partials, const void* old_msg, const int* has_old, int normalize,

@@ -1,5 +1,5 @@
 """theta SVD of a colour batch, kernel level: the plain LDS-resident Jacobi on the 128 x 64 low-rank factor against the preconditioned kernel
-(kernels.hip theta_svd_pre_kernel) on the same factors -- R factors harvested from oracle runs (tests/golden/theta_factors.npz), `copies` gates per launch.
+(kernels_svd.hip theta_svd_pre_kernel) on the same factors -- R factors harvested from oracle runs (tests/golden/theta_factors.npz), `copies` gates per launch.
     python profiles/svd_bench.py [copies] [reps]"""
 import ctypes as C, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -184,7 +184,7 @@ template <class T> struct BpUpdate {
         const int din = g.dedge(g.nbr[src][j], src), pp = plan.pos_of[din];
         return ((plan.in_place || (pp >= 0 && pp < t)) && fresh[din]) ? fresh[din] : cur[din];
     }
-    // small sites (<= 8192 elements, ComplexF32): the whole message in ONE kernel with the tensor resident in LDS (kernels.hip bp_small_site_kernel);
+    // small sites (<= 8192 elements, ComplexF32): the whole message in ONE kernel with the tensor resident in LDS (kernels_bp.hip bp_small_site_kernel);
     // TNQS_NO_SMALL_SITE_BP=1: the generic chain + Gram route
     bool small_site(const SD& sd) const {
         return small_site_on() && std::is_same<T, float>::value && sd.n >= 64 && bp_small_site_covers(sd.d, sd.z, sd.chi.data(), sd.n);

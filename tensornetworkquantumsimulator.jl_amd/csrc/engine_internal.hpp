@@ -9,6 +9,15 @@
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
 //   sharding.cpp      exchange step (RCCL or host callback)
+// and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
+//   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
+//   kernels_bp.hip     message epilogue, small-site message, rescale,    kernels_x3.hip     the same on the bf16 matrix cores (three-way split)
+//                      edge scalars, symmetric gauge                     kernels_plane.hip  16-dimensional planes (chi = 16)
+//   kernels_svd.hip    Jacobi (global / LDS), preconditioned theta SVD,  kernels_chi64.hip  chi = 64 family
+//                      V recovery, small-SVD prepare / finish            kernels_gate.hip   fused gauge + f64 Gram of the gate path
+//   kernels_chol.hip   Cholesky (square / packed), env prepare / finish  kernels_f64.hip    ComplexF64 on the f64 matrix cores
+//   kernels_theta.hip  per-gate small algebra: gate_eigs .. gate_finish  kernels_sample.hip sampling
+//   kernels_util.hip   diag, norm factor, scale, pack, permute, fills
 #pragma once
 #include "engine.hpp"
 #include "kernels.hpp"
@@ -46,7 +55,7 @@ TNQS_SWITCH(use_prodcache, !envflag("TNQS_NO_PRODCACHE"))        // BP: no parti
 TNQS_SWITCH(use_chol, !envflag("TNQS_NO_CHOL"))                  // R factor from the eigen factorisation of the Gram matrix instead of Cholesky (the route a collapsed pivot falls back to)
 TNQS_SWITCH(use_qr2, !envflag("TNQS_NO_QR2"))                    // ComplexF64: no second factorisation pass
 TNQS_SWITCH(use_lowrank, !envflag("TNQS_NO_LOWRANK"))            // theta SVD on the full theta instead of the low-rank factor (the route a refused pivot falls back to)
-TNQS_SWITCH(use_precond_svd, !envflag("TNQS_NO_PRECOND_SVD"))    // low-rank theta SVD on the plain LDS Jacobi instead of the preconditioned one-kernel route (kernels.hip theta_svd_pre_kernel)
+TNQS_SWITCH(use_precond_svd, !envflag("TNQS_NO_PRECOND_SVD"))    // low-rank theta SVD on the plain LDS Jacobi instead of the preconditioned one-kernel route (kernels_svd.hip theta_svd_pre_kernel)
 TNQS_SWITCH(use_small_svd, !envflag("TNQS_NO_SMALLSVD"))         // sites with fewer fibers than columns: Gram + eigen instead of the direct SVD
 TNQS_SWITCH(defer_site1, !envflag("TNQS_NO_DEFER_1SITE"))        // unitary one-site gates are applied in a pass of their own instead of being carried to the next two-site gate
 TNQS_SWITCH(use_chi64, !envflag("TNQS_NO_CHI64"))                // the chi = 64 kernel family (kernels_chi64.hip: register-direct fiber GEMM, 64 x 64 / 128 x 128 Grams, packed Cholesky, Cholesky-QR theta SVD)

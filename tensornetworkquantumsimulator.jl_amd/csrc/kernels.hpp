@@ -230,7 +230,7 @@ struct RecoverItem { const void* A0; const void* A; void* V; int m; int n; int n
 // LDS bytes the LDS-resident Jacobi needs for an m x n matrix (columns padded by 2 elements)
 inline size_t jacobi_lds_bytes(int m, int n, bool withV, size_t esz) { return ((size_t)(m + 2) * n + (withV ? (size_t)(n + 2) * n : 0)) * esz; }
 template <class T> void launch_jacobi(hipStream_t s, const JacobiItem* d_items, int nitems, int max_sweeps, size_t lds_bytes, int mmax, int ncols = 0);   // ncols: expected columns (sizes the workgroup of the LDS kernel)
-// Preconditioned theta SVD in one kernel (kernels.hip theta_svd_pre_kernel): ComplexF32, no V, m >= n, n <= 64, m <= 128 (upper bounds when JacobiItem::dyn
+// Preconditioned theta SVD in one kernel (kernels_svd.hip theta_svd_pre_kernel): ComplexF32, no V, m >= n, n <= 64, m <= 128 (upper bounds when JacobiItem::dyn
 // decides the dimensions on the device).  LDS: the sorted A (f32) + the n x n Gram / Cholesky array (f64)
 inline bool theta_svd_pre_covers(int m, int n) { return n >= 2 && n <= 64 && m >= n && m <= 128; }
 inline size_t theta_svd_pre_lds_bytes(int m, int n) { return ((((size_t)(m + 2) * n * 8) + 15) & ~(size_t)15) + (size_t)(n + 1) * n * 16; }

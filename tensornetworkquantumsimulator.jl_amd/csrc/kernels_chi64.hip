@@ -7,11 +7,7 @@
 //   mfma_gram128_f64_kernel   gate-path Gram G = psi~^dagger psi~ over the outer legs, 128 x 128 (s, b) output, f64 MFMA accumulation
 //   mfma_rowgemm_kernel       mode products / gate epilogue  out[.., n] = sum_k in[.., k] X[k, n]  with K, N up to 128: the tensor operand
 //                             goes from global memory straight into MFMA operand registers (no LDS staging of the tensor at all)
-#include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <stdexcept>
-#include <string>
-#define TNQS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP kernel launch failed (") + __func__ + "): " + hipGetErrorString(e_)); } while (0)
 #include "kernels.hpp"
 #include "launch_util.hpp"
 #include "mfma_common.hpp"
@@ -227,26 +223,24 @@ __global__ __launch_bounds__(256) void tall_gram_kernel(const TallSvdItem* __res
         }
         __syncthreads();
     }
-    struct alignas(16) cd { double re, im; };
-    cd* __restrict__ G = reinterpret_cast<cd*>(it.G);
+    cx<double>* __restrict__ G = reinterpret_cast<cx<double>*>(it.G);
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int i = 32 * I + 2 * tx + p, j = 32 * J + 2 * ty + q;
-            if (i < n && j < n) { G[i + (size_t)n * j] = cd{cr[p][q], ci[p][q]}; if (I != J) G[j + (size_t)n * i] = cd{cr[p][q], -ci[p][q]}; }
+            if (i < n && j < n) { G[i + (size_t)n * j] = cx<double>{cr[p][q], ci[p][q]}; if (I != J) G[j + (size_t)n * i] = cx<double>{cr[p][q], -ci[p][q]}; }
         }
 }
 __global__ __launch_bounds__(256) void tall_rt_kernel(const TallSvdItem* __restrict__ items) {
     const TallSvdItem it = items[blockIdx.x];
     const int n = it.n;
-    struct alignas(16) cd { double re, im; };
-    const cd* __restrict__ L = reinterpret_cast<const cd*>(it.L);
+    const cx<double>* __restrict__ L = reinterpret_cast<const cx<double>*>(it.L);
     cf* __restrict__ R0 = reinterpret_cast<cf*>(it.R0); cf* __restrict__ Rr = reinterpret_cast<cf*>(it.Rrot);
     for (int e = threadIdx.x; e < n * n; e += 256) {
         const int i = e % n, j = e / n;                      // R[i, j] = conj(L[j, i]) for i <= j
         cf v = {0.f, 0.f};
-        if (i <= j) { const cd l = L[j + (size_t)n * i]; v.re = (float)l.re; v.im = (float)(-l.im); }
+        if (i <= j) { const cx<double> l = L[j + (size_t)n * i]; v.re = (float)l.re; v.im = (float)(-l.im); }
         R0[e] = v; Rr[e] = v;
     }
 }
@@ -259,11 +253,10 @@ __global__ __launch_bounds__(256) void tall_w_kernel(const TallSvdItem* __restri
     const int n = it.n, nt = (n + 31) >> 5;
     const int I = blockIdx.y % nt, J = blockIdx.y / nt;
     if (J >= nt) return;
-    struct alignas(16) cd { double re, im; };
     __shared__ double Ar[32][33], Ai[32][33], Br[32][33], Bi[32][33];       // A = Rinv[32 I + i][j0 + j], B = Rrot[j0 + j][32 J + c]
-    const cd* __restrict__ Rinv = reinterpret_cast<const cd*>(it.L);        // the caller passes R^-1 in the L slot of this launch
+    const cx<double>* __restrict__ Rinv = reinterpret_cast<const cx<double>*>(it.L);        // the caller passes R^-1 in the L slot of this launch
     const cf* __restrict__ Rrot = reinterpret_cast<const cf*>(it.Rrot);
-    cd* __restrict__ W = reinterpret_cast<cd*>(it.R0);                     // and the output in the R0 slot, complex128: J is multiplied into A in f64 (tall_mj_kernel)
+    cx<double>* __restrict__ W = reinterpret_cast<cx<double>*>(it.R0);                     // and the output in the R0 slot, complex128: J is multiplied into A in f64 (tall_mj_kernel)
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     // a Cholesky pivot of this item collapsed in spite of the shift (flag in the G slot of this launch): R is not a usable preconditioner,
     // so J := I -- A stays as it is and the sweeps on A that follow (svd_batch, full sweep cap) do the whole factorisation themselves
@@ -274,7 +267,7 @@ __global__ __launch_bounds__(256) void tall_w_kernel(const TallSvdItem* __restri
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int i = 32 * I + 2 * tx + p, c = 32 * J + 2 * ty + q;
-                if (i < n && c < n) { cd v; v.re = (i == c) ? 1.0 : 0.0; v.im = 0.0; W[i + (size_t)n * c] = v; }
+                if (i < n && c < n) { cx<double> v; v.re = (i == c) ? 1.0 : 0.0; v.im = 0.0; W[i + (size_t)n * c] = v; }
             }
         return;
     }
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(256) void tall_w_kernel(const TallSvdItem* __restri
     for (int j0 = 32 * I; j0 < n; j0 += 32) {                               // Rinv is upper triangular: rows 32 I.. only see columns >= 32 I
         for (int e = tid; e < 1024; e += 256) {
             const int a = e & 31, b = e >> 5;
-            cd x = {0.0, 0.0}; cf y = {0.f, 0.f};
+            cx<double> x = {0.0, 0.0}; cf y = {0.f, 0.f};
             if (32 * I + a < n && j0 + b < n) x = Rinv[(32 * I + a) + (size_t)n * (j0 + b)];
             if (j0 + a < n && 32 * J + b < n) y = Rrot[(j0 + a) + (size_t)n * (32 * J + b)];
             Ar[a][b] = x.re; Ai[a][b] = x.im; Br[a][b] = (double)y.re; Bi[a][b] = (double)y.im;
@@ -304,7 +297,7 @@ __global__ __launch_bounds__(256) void tall_w_kernel(const TallSvdItem* __restri
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int i = 32 * I + 2 * tx + p, c = 32 * J + 2 * ty + q;
-            if (i < n && c < n) { cd v; v.re = cr[p][q]; v.im = ci[p][q]; W[i + (size_t)n * c] = v; }
+            if (i < n && c < n) { cx<double> v; v.re = cr[p][q]; v.im = ci[p][q]; W[i + (size_t)n * c] = v; }
         }
 }
 void launch_tall_w(hipStream_t s, const TallSvdItem* d_items, int nitems, int nmax) {
@@ -317,12 +310,10 @@ void launch_tall_w(hipStream_t s, const TallSvdItem* d_items, int nitems, int nm
 // in f64 and the product in f64 every column of A J keeps the accuracy the Jacobi sweeps on R gave it RELATIVE TO ITS OWN NORM
 // (A J = Q (R J): the columns are Q times the sweeps' output), so no polishing sweeps on A J are needed -- the f32 product they followed
 // left a residue of eps32 sigma_max in every column.
-typedef double v4d_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(1024) void tall_mj_kernel(const SmallGemmItem* __restrict__ items) {
     const SmallGemmItem it = items[blockIdx.x];
-    struct alignas(16) cd { double re, im; };
     const cf* __restrict__ A = reinterpret_cast<const cf*>(it.A);
-    const cd* __restrict__ J = reinterpret_cast<const cd*>(it.B);
+    const cx<double>* __restrict__ J = reinterpret_cast<const cx<double>*>(it.B);
     cf* __restrict__ C = reinterpret_cast<cf*>(it.C);
     const int m = it.m, n = it.n, k = it.k;
     const int lane = threadIdx.x & 63, l15 = lane & 15, kq = lane >> 4;
@@ -331,10 +322,10 @@ __global__ __launch_bounds__(1024) void tall_mj_kernel(const SmallGemmItem* __re
     for (int t = w; t < tr * tc; t += nw) {
         const int j0 = 16 * (t % tr), i0 = 16 * (t / tr);
         const int jj = j0 + l15, ii = i0 + l15;
-        v4d_t cr = {0, 0, 0, 0}, ci = {0, 0, 0, 0};
+        v4d cr = {0, 0, 0, 0}, ci = {0, 0, 0, 0};
         for (int k0 = 0; k0 < k; k0 += 4) {
             const int kk = k0 + kq;
-            cd a = {0.0, 0.0}; double br = 0.0, bi = 0.0;
+            cx<double> a = {0.0, 0.0}; double br = 0.0, bi = 0.0;
             if (kk < k) { if (jj < n) a = J[kk + (size_t)k * jj]; if (ii < m) { const cf v = A[ii + (size_t)m * kk]; br = (double)v.re; bi = (double)v.im; } }
             cr = __builtin_amdgcn_mfma_f64_16x16x4f64(a.re, br, cr, 0, 0, 0);       // C'[j][i] = sum_k J[k, j] A[i, k]
             cr = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.im, bi, cr, 0, 0, 0);
@@ -489,7 +480,7 @@ __global__ __launch_bounds__(256, (KB * NB <= 4 ? 2 : 1)) void mfma_rowgemm_kern
         nrm += (double)nf;
     }
     if (it.want_norm) {
-        nrm = wave_sum_d(nrm);
+        nrm = wave_sum(nrm);
         if (lane == 0) sh_red[w] = nrm;
         __syncthreads();
         if (tid == 0) norm_partials[gw] = sh_red[0] + sh_red[1] + sh_red[2] + sh_red[3];
@@ -709,8 +700,7 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
         }
         lds_barrier();                                           // tile t consumed by everybody, tile t+1 committed by everybody
     }
-    struct alignas(16) cd { double re, im; };
-    cd* __restrict__ part = reinterpret_cast<cd*>(it.partial) + (size_t)lc * KK * KK;
+    cx<double>* __restrict__ part = reinterpret_cast<cx<double>*>(it.partial) + (size_t)lc * KK * KK;
 #pragma unroll
     for (int q = 0; q < NBW; ++q) {
         if (!bOn[q]) continue;
@@ -718,8 +708,8 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * bI[q] + kq + 4 * r, j = 16 * bJ[q] + l15;
             if (i < KK && j < KK) {
-                cd v; v.re = M3 ? Cr[q][r] - Ci[q][r] : Cr[q][r]; v.im = M3 ? Cr[q][r] - Cc[q][r] : Ci[q][r]; part[i + (size_t)KK * j] = v;
-                if (bI[q] != bJ[q]) { cd c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }
+                cx<double> v; v.re = M3 ? Cr[q][r] - Ci[q][r] : Cr[q][r]; v.im = M3 ? Cr[q][r] - Cc[q][r] : Ci[q][r]; part[i + (size_t)KK * j] = v;
+                if (bI[q] != bJ[q]) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }
             }
         }
     }

@@ -13,11 +13,6 @@
 // The 16 fibers of a tile are (al, bl) = (l % TA, l / TA) with TA = min(PA, 16): on the first leg (PA = 2) a tile takes 8 values of b.
 // Four real products per complex one: the kernel is memory-bound, the f64 pipe runs at a quarter of its rate.
 // The next tile's operand is loaded before the products of the current one (double register set).
-#include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <stdexcept>
-#include <string>
-#define TNQS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP kernel launch failed (") + __func__ + "): " + hipGetErrorString(e_)); } while (0)
 #include "kernels.hpp"
 #include "mfma_common.hpp"
 #include "launch_util.hpp"
@@ -29,7 +24,7 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ zc ldgz(const zc* p) { const v2d t = *(const v2d TNQS_AS1*)(p); zc r; r.re = t[0]; r.im = t[1]; return r; }
 __device__ __forceinline__ void stgz(zc* p, zc v) { v2d t = {v.re, v.im}; *(v2d TNQS_AS1*)(p) = t; }
 __device__ __forceinline__ double block_sum_f64(double v, double* sh /* >= 17 doubles */) {      // 256 threads
-    v = wave_sum_d(v);
+    v = wave_sum(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     __syncthreads();
     if (lane == 0) sh[w] = v;

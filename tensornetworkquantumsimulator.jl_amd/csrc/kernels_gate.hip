@@ -7,11 +7,6 @@
 // product is a (128 x 32) x (32 x 32) complex GEMM inside the tile: it runs on the f32 matrix cores, in place in LDS, before the f64
 // Gram of the tile.  psi~ is rounded to f32 exactly where the separate pass rounded it, so G is still the exact Gram matrix of a rounded
 // tensor.  One pass over the tensor instead of three.
-#include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <stdexcept>
-#include <string>
-#define TNQS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP kernel launch failed (") + __func__ + "): " + hipGetErrorString(e_)); } while (0)
 #include "kernels.hpp"
 #include "mfma_common.hpp"
 #include "launch_util.hpp"
@@ -183,21 +178,20 @@ __global__ __launch_bounds__(256, 2) void mfma_gauge_gram64_kernel(const GramIte
         }
         lds_barrier();                                              // tile t consumed by everybody, tile t+1 transformed by everybody
     }
-    struct alignas(16) cd { double re, im; };
     int aI[3], aJ[3], bI[2], bJ[2];
 #pragma unroll
     for (int q = 0; q < 3; ++q) { aI[q] = (w & 1) ? q : 0; aJ[q] = (w & 1) ? 3 : q; }
     bI[0] = (w & 1) ? 2 : 1; bJ[0] = (w & 1) ? 2 : 1; bI[1] = (w & 1) ? 3 : 1; bJ[1] = (w & 1) ? 3 : 2;
-    auto write_block = [&](cd* __restrict__ part, int I, int J, const v4d& cr, const v4d& ci, const v4d& cc) {
+    auto write_block = [&](cx<double>* __restrict__ part, int I, int J, const v4d& cr, const v4d& ci, const v4d& cc) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * I + kq + 4 * r, j = 16 * J + l15;
-            cd v; v.re = cr[r] - ci[r]; v.im = cr[r] - cc[r]; part[i + (size_t)64 * j] = v;
-            if (I != J) { cd c; c.re = v.re; c.im = -v.im; part[j + (size_t)64 * i] = c; }     // G[j][i] = conj(G[i][j])
+            cx<double> v; v.re = cr[r] - ci[r]; v.im = cr[r] - cc[r]; part[i + (size_t)64 * j] = v;
+            if (I != J) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)64 * i] = c; }     // G[j][i] = conj(G[i][j])
         }
     };
-    cd* __restrict__ partA = reinterpret_cast<cd*>(it.partial) + (size_t)(2 * lc + parA) * 4096;
-    cd* __restrict__ partB = reinterpret_cast<cd*>(it.partial) + (size_t)(2 * lc + (parA ^ 1)) * 4096;
+    cx<double>* __restrict__ partA = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + parA) * 4096;
+    cx<double>* __restrict__ partB = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + (parA ^ 1)) * 4096;
 #pragma unroll
     for (int q = 0; q < 3; ++q) write_block(partA, aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
 #pragma unroll
@@ -328,9 +322,8 @@ __global__ __launch_bounds__(256, 3) void mfma_gauge_gram32_kernel(const GramIte
         __builtin_amdgcn_wave_barrier();                          // the slab has been consumed: the next commit may overwrite it
     }
     // ---- the four waves' accumulators -> one partial: (2, 3) -> LDS, (0, 1) add; 1 -> LDS, 0 adds and writes ---------------------
-    struct alignas(16) cd { double re, im; };
-    cd* const R = reinterpret_cast<cd*>(smem);                   // [2 waves][3 blocks][256]
-    cd v[3][4];
+    cx<double>* const R = reinterpret_cast<cx<double>*>(smem);                   // [2 waves][3 blocks][256]
+    cx<double> v[3][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         v[0][r].re = G00r[r] - G00i[r]; v[0][r].im = G00r[r] - G00c[r];
@@ -349,7 +342,7 @@ __global__ __launch_bounds__(256, 3) void mfma_gauge_gram32_kernel(const GramIte
 #pragma unroll
         for (int b = 0; b < 3; ++b)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { const cd o = R[(w * 3 + b) * 256 + 64 * r + lane]; v[b][r].re += o.re; v[b][r].im += o.im; }
+            for (int r = 0; r < 4; ++r) { const cx<double> o = R[(w * 3 + b) * 256 + 64 * r + lane]; v[b][r].re += o.re; v[b][r].im += o.im; }
     }
     __syncthreads();
     if (w == 1) {
@@ -360,17 +353,17 @@ __global__ __launch_bounds__(256, 3) void mfma_gauge_gram32_kernel(const GramIte
     }
     __syncthreads();
     if (w == 0) {
-        cd* __restrict__ part = reinterpret_cast<cd*>(it.partial) + (size_t)lc * 1024;
+        cx<double>* __restrict__ part = reinterpret_cast<cx<double>*>(it.partial) + (size_t)lc * 1024;
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
             const int I = b == 2 ? 1 : 0, J = b == 0 ? 0 : 1;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const cd o = R[b * 256 + 64 * r + lane];
-                cd g; g.re = v[b][r].re + o.re; g.im = v[b][r].im + o.im;
+                const cx<double> o = R[b * 256 + 64 * r + lane];
+                cx<double> g; g.re = v[b][r].re + o.re; g.im = v[b][r].im + o.im;
                 const int i = 16 * I + kq + 4 * r, j = 16 * J + l15;
                 part[i + 32 * j] = g;
-                if (I != J) { cd c; c.re = g.re; c.im = -g.im; part[j + 32 * i] = c; }      // G[j][i] = conj(G[i][j])
+                if (I != J) { cx<double> c; c.re = g.re; c.im = -g.im; part[j + 32 * i] = c; }      // G[j][i] = conj(G[i][j])
             }
         }
     }

@@ -6,11 +6,7 @@
 //      A[i = ln][k = h]   B[k = h][j = ln]   C[row = (r&3) + 8*(r>>2) + 4*h][col = ln],  r = 0..15
 // Because the k index only has to be consistent between A and B, k-step t of a 32-deep block is mapped to
 // k = t + 16*h, so every lane reads 16 CONSECUTIVE floats of its operand row from LDS (4 x ds_read_b128).
-#include <hip/hip_runtime.h>
 #include <cstdlib>
-#include <stdexcept>
-#include <string>
-#define TNQS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP kernel launch failed (") + __func__ + "): " + hipGetErrorString(e_)); } while (0)
 #include "kernels.hpp"
 #include "mfma_common.hpp"
 #include <type_traits>
@@ -185,7 +181,7 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_kernel(const FiberItem* _
         }
     }
     if (it.want_norm) {
-        nrm = wave_sum_d(nrm);
+        nrm = wave_sum(nrm);
         if (lane == 0) sh_red[w] = nrm;
         __syncthreads();
         if (tid == 0) norm_partials[gw] = sh_red[0] + sh_red[1] + sh_red[2] + sh_red[3];
@@ -231,8 +227,8 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_w_kernel(const FiberItem*
     }
     for (int e = lane; e < 32 * PT; e += 64) { At_re[e] = 0.f; At_im[e] = 0.f; }
     __syncthreads();                                   // the only workgroup barrier: X^T is staged
-    const TileMap mi = make_map_wave(lane, D, TA, TB, PA, K);
-    const TileMap mo = make_map_wave(lane, Do, TA, TB, PA, No);
+    const TileMap mi = make_map(lane, D, TA, TB, PA, K, 64);
+    const TileMap mo = make_map(lane, Do, TA, TB, PA, No, 64);
     const long long kstride_in = (long long)D * PA, kstride_out = (long long)Do * PA;
     const bool fast = mi.U <= 64 && mo.U <= 64 && (K + mi.KP - 1) / mi.KP <= NU;
     v4f pre[NU];
@@ -361,7 +357,7 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_w_kernel(const FiberItem*
         }
     }
     if (it.want_norm) {
-        nrm = wave_sum_d(nrm);
+        nrm = wave_sum(nrm);
         if (lane == 0) sh_red[w] = nrm;
         __syncthreads();
         if (tid == 0) norm_partials[gw] = sh_red[0] + sh_red[1] + sh_red[2] + sh_red[3];
@@ -568,7 +564,7 @@ __global__ __launch_bounds__(256) void mfma_gram32_fused_kernel(const GramItem* 
     v16f Or, Oi;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { Or[r] = 0.f; Oi[r] = 0.f; }
-    const TileMap m = make_map_wave(lane, 1, TA, TB, PA, K);
+    const TileMap m = make_map(lane, 1, TA, TB, PA, K, 64);
     const long long kstride = PA;
     v4f pre[NU];
     auto issue = [&](const cf* __restrict__ G, int t) {
@@ -1343,20 +1339,19 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem*
         }
         lds_barrier();                                           // tile t consumed by everybody, tile t+1 committed by everybody
     }
-    struct alignas(16) cd { double re, im; };
-    auto write_block = [&](cd* __restrict__ part, int I, int J, const v4d& cr, const v4d& ci, const v4d& cc) {
+    auto write_block = [&](cx<double>* __restrict__ part, int I, int J, const v4d& cr, const v4d& ci, const v4d& cc) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             int i = 16 * I + kq + 4 * r, j = 16 * J + l15;
             if (i < KK && j < KK) {
-                cd v; v.re = M3 ? cr[r] - ci[r] : cr[r]; v.im = M3 ? cr[r] - cc[r] : ci[r]; part[i + (size_t)KK * j] = v;
-                if (I != J) { cd c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }     // G[j][i] = conj(G[i][j])
+                cx<double> v; v.re = M3 ? cr[r] - ci[r] : cr[r]; v.im = M3 ? cr[r] - cc[r] : ci[r]; part[i + (size_t)KK * j] = v;
+                if (I != J) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }     // G[j][i] = conj(G[i][j])
             }
         }
     };
     // partial 2*lc + p collects the blocks accumulated on tiles of parity p (each block exactly once per parity)
-    cd* __restrict__ partA = reinterpret_cast<cd*>(it.partial) + (size_t)(2 * lc + parA) * KK * KK;
-    cd* __restrict__ partB = reinterpret_cast<cd*>(it.partial) + (size_t)(2 * lc + (parA ^ 1)) * KK * KK;
+    cx<double>* __restrict__ partA = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + parA) * KK * KK;
+    cx<double>* __restrict__ partB = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + (parA ^ 1)) * KK * KK;
 #pragma unroll
     for (int q = 0; q < 3; ++q) if (aOn[q]) write_block(partA, aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
 #pragma unroll

@@ -17,14 +17,10 @@
 // k only has to be consistent between A and B: k-step t of group g is mapped to index 4 g + t, so a lane reads FOUR CONSECUTIVE complex
 // numbers of its operand row from LDS (2 x ds_read_b128).  Chaining as in the chi = 32 kernels: accumulator register r of a product
 // holds row 4 g + r, which is exactly the k index instruction r of the next product consumes -- the intermediate never leaves registers.
-#include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <map>
 #include <mutex>
-#include <stdexcept>
-#include <string>
 #include <type_traits>
-#define TNQS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP kernel launch failed (") + __func__ + "): " + hipGetErrorString(e_)); } while (0)
 #include "kernels.hpp"
 #include "launch_util.hpp"
 #include "mfma_common.hpp"

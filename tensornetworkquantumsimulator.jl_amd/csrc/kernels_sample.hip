@@ -10,12 +10,9 @@
 //                              (seed, sample, step) alone, 53 bits, never 1.
 //   site_project_kernel        out[i] = psi_v[x + d i] with x read from device memory: the host enqueues it (and the BP update behind it) without knowing x.
 // Every reduction runs in a fixed order, so the same inputs give the same bits whichever entry point (tnqs_site_probabilities, tnqs_sample_bp) launched them.
-#include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <stdexcept>
-#include <string>
 #include "kernels.hpp"
-#define TNQS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP kernel launch failed (") + __func__ + "): " + hipGetErrorString(e_)); } while (0)
+#include "device_common.hpp"
 
 namespace tnqs {
 

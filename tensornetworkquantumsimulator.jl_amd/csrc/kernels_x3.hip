@@ -14,12 +14,8 @@
 // instructions per f32 value (and, subtract, and, subtract, 1.5 byte-permutes to pack pairs), on the VALU next to the matrix pipe.
 // The kernels keep the data movement of the f32 kernels they replace (kernels_mfma.hip); with the matrix time halved they are bound by HBM.
 // TNQS_NO_BF16X3=1 selects the f32 kernels.
-#include <hip/hip_runtime.h>
 #include <cstdlib>
-#include <stdexcept>
-#include <string>
 #include <type_traits>
-#define TNQS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP kernel launch failed (") + __func__ + "): " + hipGetErrorString(e_)); } while (0)
 #include "kernels.hpp"
 #include "mfma_common.hpp"
 #include "launch_util.hpp"
@@ -523,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void x3_rowgemm64_kernel(const FiberItem* _
         nrm += (double)nf;
     }
     if (it.want_norm) {
-        nrm = wave_sum_d(nrm);
+        nrm = wave_sum(nrm);
         if (lane == 0) sh_red[w] = nrm;
         __syncthreads();
         if (tid == 0) norm_partials[gw] = sh_red[0] + sh_red[1] + sh_red[2] + sh_red[3];

@@ -1,4 +1,4 @@
-// launch_util.hpp -- host-side helpers shared by the kernel translation units.
+// launch_util.hpp -- host-side helpers shared by the kernel translation units (the device-side ones: device_common.hpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <cstdlib>

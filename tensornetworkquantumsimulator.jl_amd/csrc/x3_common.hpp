@@ -1,6 +1,5 @@
 // x3_common.hpp -- f32 products on the bf16 matrix cores: exact three-way operand split and the six-product accumulate (kernels_x3.hip has the derivation).
 #pragma once
-#include <hip/hip_runtime.h>
 #include "mfma_common.hpp"
 
 namespace tnqs {

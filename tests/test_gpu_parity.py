@@ -410,7 +410,7 @@ def test_bp_update_with_repeated_messages_in_the_sequence_matches_oracle(dtype, 
 @pytest.mark.parametrize("lattice", ["hh11", "hh22", "ring6"])
 def test_small_sites_with_16_dimensional_legs_match_oracle(lattice):
     """heavy-hex sites at chi = 16 (BASELINE configs[2] per-site shape: 2 x 16^3 = 64 KiB, 2 x 16^2 at the degree-2 sites): the whole message of such a site is ONE
-    kernel with the tensor in LDS, on the f32 matrix cores when every leg is 16-dimensional (kernels.hip bp_small_site_mfma16).  Messages elementwise against the
+    kernel with the tensor in LDS, on the f32 matrix cores when every leg is 16-dimensional (kernels_bp.hip bp_small_site_mfma16).  Messages elementwise against the
     oracle over three sweeps, default order replayed (updated_message, abstractbeliefpropagationcache.jl:162-190)."""
     g = {"hh11": lambda: tn.heavy_hexagonal_lattice(1, 1), "hh22": lambda: tn.heavy_hexagonal_lattice(2, 2), "ring6": lambda: tn.named_grid((6,), periodic=True)}[lattice]()
     psi = tn.random_tensornetworkstate(np.complex64, g, bond_dimension=16, seed=5)

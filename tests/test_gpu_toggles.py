@@ -147,7 +147,7 @@ def test_chi16_plane_kernels_match_the_single_leg_route():
 
 
 def test_small_site_message_kernel_matches_the_generic_route():
-    """heavy-hex at chi = 16: the whole message of a small site in one LDS-resident kernel (kernels.hip bp_small_site_kernel) -- on the f32 matrix cores when every
+    """heavy-hex at chi = 16: the whole message of a small site in one LDS-resident kernel (kernels_bp.hip bp_small_site_kernel) -- on the f32 matrix cores when every
     leg is 16-dimensional, with the normalisation and message_diff of msg_finalize_kernel inside -- against the generic chain + Gram route.  Messages after three
     sweeps elementwise (same site tensors, same order), then one layer."""
     switch = "TNQS_NO_SMALL_SITE_BP"
