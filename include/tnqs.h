@@ -219,6 +219,18 @@ int tnqs_site_probabilities(tnqs_handle h, int v, double* out_p);
 int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uint64_t seed, const double* uniforms,
                    int32_t* out_config, double* out_prob, tnqs_apply_stats* stats);
 
+/* ---- loop corrections (src/MessagePassing/loopcorrection.jl:79-89 `weight`, for simple cycles) ------------------
+ * Cycle c is the vertex list v_0 .. v_{L-1} (cycle_len[c] = L >= 3 distinct vertices, consecutive ones and the closing pair neighbours),
+ * the lists one after the other in cycle_verts.  out_re_im[2c, 2c+1] = W(c) = Tr prod_k (A_k T_k): T_k the double-layer transfer matrix of
+ * v_k on the bond pair (from v_{k-1}, to v_{k+1}) with the cache's messages on its other legs, A_k = I - vec(m_{v_k -> v_{k+1}})
+ * vec(m_{v_{k+1} -> v_k})^T the antiprojector of the bond (bilinear, no conjugate).
+ * PRECONDITION (not checked): the handle is rescaled (tnqs_rescale: every vertex and edge scalar is 1) -- only then is W the weight of the
+ * loop series, Z = Z_bp (1 + sum W).  The handle is not changed.  ncycles = 0 is allowed.
+ * Cycles are processed in batches whose workspace stays under min(2 GiB, a quarter of the free device memory); a single cycle that needs more than that is
+ * still run on its own (its allocation may then fail with TNQS_ERR_HIP).
+ * TNQS_ERR_INVALID: a list that is not a cycle of the graph; TNQS_ERR_UNSUPPORTED: sharded handles, vertex degree > 7. */
+int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im);
+
 /* ---- multi-GPU sharding (no reference analogue).  A rank owns a vertex subset: it holds only
  *      those site tensors and does all per-vertex work for them; messages are replicated.  The library calls
  *      the host-supplied all-gather at the exchange points (host side: torch.distributed over RCCL). --------- */
@@ -258,7 +270,9 @@ enum { TNQS_PROF_BP_MODEPROD = 0, TNQS_PROF_BP_GRAM = 1, TNQS_PROF_GATE_MODEPROD
        TNQS_PROF_GATE_APPLY = 4, TNQS_PROF_JACOBI = 5, TNQS_PROF_SMALL = 6, TNQS_PROF_BP_FUSED = 7, TNQS_PROF_BP_PAIR = 8, TNQS_PROF_BP_PAIRGRAM = 9,
        /* whole phases, first to last kernel on the handle's stream (side streams join it before a phase ends): the CRITICAL-PATH time of the BP updates (launches =
         * sweeps) and of the batches of two-site gates (launches = batches) -- the kernel classes above overlap each other where a phase runs on two streams */
-       TNQS_PROF_PHASE_BP_UPDATE = 10, TNQS_PROF_PHASE_GATE_BATCH = 11, TNQS_PROF_NCLASSES = 12 };
+       TNQS_PROF_PHASE_BP_UPDATE = 10, TNQS_PROF_PHASE_GATE_BATCH = 11,
+       /* every launch of tnqs_loop_weights; flops: 8 m n k per complex product of the batched GEMM */
+       TNQS_PROF_LOOP = 12, TNQS_PROF_NCLASSES = 13 };
 int tnqs_profile_enable(tnqs_handle h, int on);
 /* launches, total ms, algorithmic bytes (min traffic: operands read once + result written once) and flops */
 int tnqs_profile_get(tnqs_handle h, int cls, int64_t* launches, double* total_ms, double* alg_bytes, double* alg_flops);

@@ -103,6 +103,17 @@ int tnqs_dbg_default_sequence_graph(int nv, int ne, const int32_t* esrc, const i
  * (TNQS_ERR_INVALID), adjacency is not.  HOST ONLY: no device is touched (tests/test_gate_schedule.py) */
 int tnqs_dbg_gate_schedule(int nv, int ne, const int32_t* esrc, const int32_t* edst, int ngates, const int32_t* nverts, const int32_t* verts, int update_cache,
                            int* step_of_gate, int* step_is_bp, int cap, int* nsteps_out);
+/* ---- loop corrections (csrc/kernels_loop.hip; dtype 0 c64, 1 c128; column-major matrices, the items' matrices one after the other in every array) ----
+ * loop_cgemm_kernel<T>, ONE launch: C_i (m[i] x n[i]) = A_i (m[i] x k[i]) op(B_i); opB = 0: B_i is k[i] x n[i]; opB = 1: B_i is n[i] x k[i], op = conjugate transpose.
+ * C holds `guard` elements, then C_0, `guard` elements, C_1, ..., `guard` elements: the whole array goes to the device as the caller filled it and comes back,
+ * so the caller sees that nothing outside the C_i was written. */
+int tnqs_dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int* n, const int* k, const void* A, const void* B, void* C, int guard);
+/* loop_antiproject_kernel<T>, ONE launch: T_i (nr[i] x nc[i], in place) <- T_i - f_i (b_i^T T_i), f_i, b_i of nr[i] elements, no conjugate */
+int tnqs_dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* T_inout, const void* f, const void* b);
+/* loop_trace_kernel<T> + its tail: out[i] (complex128) = sum_ab X_i[a,b] Y_i[b,a], X_i p[i] x q[i], Y_i q[i] x p[i] */
+int tnqs_dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out_re_im);
+/* the pending real scale factor of the site tensor of v (a normalising gate only records 1/||psi_v||; the tensor the reference holds is the stored one times it): 1 when none is pending */
+int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor);
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ reference repo):
   expect(bpc, (op, [v]))                                                  src/expect.jl:54-82,114-121
   maxvirtualdim                                                           src/TensorNetworks/abstracttensornetwork.jl:27-29
   sample(psi, nsamples; alg = "bp")                                       src/sampling.jl:3-46
+  norm_sqr / norm (alg = "bp", "loopcorrections"), loopcorrected_partitionfunction   src/norm_sqr.jl:10-18,62-78, src/MessagePassing/loopcorrection.jl:3-14
 Every flop runs in libtnqs_hip.so; this file only marshals arguments through the C ABI (include/tnqs.h)."""
 from __future__ import annotations
 
@@ -22,7 +23,7 @@ import numpy as np
 
 from . import _lib as L
 from .gates import gate_matrix, resolve_gate, resolve_gate_flat
-from .graphs import NamedGraph, edge_color as _edge_color
+from .graphs import NamedGraph, edge_color as _edge_color, leafless_edge_induced_subgraphs, connected_edge_components
 
 _DT = {np.dtype(np.complex64): L.TNQS_C64, np.dtype(np.complex128): L.TNQS_C128, np.dtype(np.float32): L.TNQS_F32, np.dtype(np.float64): L.TNQS_F64}
 _DT_INV = {v: k for k, v in _DT.items()}
@@ -638,6 +639,164 @@ def symmetrize_and_normalize(bpc: BeliefPropagationCache, regularization: Option
     return symmetric_gauge(rescale(bpc), regularization=regularization)
 
 
+# ---- loop corrections (src/MessagePassing/loopcorrection.jl, src/norm_sqr.jl) -------------------------------------
+HOST_CONTRACTION_LIMIT = 2 ** 24      # a configuration is contracted on the host only while every intermediate stays BELOW this many elements
+
+
+def loop_weights(bpc: BeliefPropagationCache, cycles) -> np.ndarray:
+    """W(c) = Tr prod_k (A_k T_k) of simple cycles (vertex lists, consecutive vertices and the closing pair neighbours) on the device, in one
+    call (tnqs_loop_weights); `bpc` must be rescaled for these to be the weights of the loop series"""
+    g = bpc.graph
+    out = np.zeros(len(cycles), dtype=np.complex128)
+    ln, lnp = L.i32([len(c) for c in cycles] or [0])
+    vs, vsp = L.i32([g.index[v] for c in cycles for v in c] or [0])
+    L.check(L.lib.tnqs_loop_weights(bpc._h, len(cycles), lnp, vsp, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def _cycle_order(edges):
+    """the vertices of a simple cycle, given as its edge set, in ring order (None: some vertex has another degree than 2)"""
+    nb: Dict = {}
+    for (a, b) in edges:
+        nb.setdefault(a, []).append(b); nb.setdefault(b, []).append(a)
+    if any(len(x) != 2 for x in nb.values()):
+        return None
+    start = edges[0][0]
+    ring, prev, cur = [start], None, start
+    while True:
+        nxt = nb[cur][0] if nb[cur][0] != prev else nb[cur][1]
+        if nxt == start:
+            return ring
+        ring.append(nxt); prev, cur = cur, nxt
+
+
+def _host_plan(bpc: BeliefPropagationCache, edges):
+    """einsum operands (as shapes) and index lists of the configuration `edges`: per vertex the ket and the bra, per leg outside the configuration
+    the incoming message, per edge of the configuration its antiprojector (loopcorrection.jl:79-89)"""
+    g = bpc.graph
+    inside = {frozenset(e) for e in edges}
+    verts = sorted({v for e in edges for v in e}, key=g.index.__getitem__)
+    label: Dict = {}
+
+    def ix(*key):
+        return label.setdefault(key, len(label))
+    ops = []          # (kind, payload, shape, indices)
+    for v in verts:
+        nbs = g.neighbors(v)
+        shape = (bpc._site_dim(v),) + tuple(bpc.bond_dim(v, w) for w in nbs)
+        ops.append(("ket", v, shape, [ix("s", v)] + [ix("k", v, w) for w in nbs]))
+        ops.append(("bra", v, shape, [ix("s", v)] + [ix("b", v, w) for w in nbs]))
+        for w in nbs:
+            if frozenset((v, w)) not in inside:
+                chi = bpc.bond_dim(v, w)
+                ops.append(("msg", (w, v), (chi, chi), [ix("k", v, w), ix("b", v, w)]))
+    for (u, v) in edges:
+        chi = bpc.bond_dim(u, v)
+        ops.append(("anti", (u, v), (chi,) * 4, [ix("k", u, v), ix("b", u, v), ix("k", v, u), ix("b", v, u)]))
+    return ops, len(label)
+
+
+def _largest_intermediate(ops, path) -> int:
+    """largest intermediate (elements) of a pairwise contraction path as np.einsum_path returns it"""
+    dims: Dict[int, int] = {}
+    for (_, _, shape, idx) in ops:
+        dims.update(zip(idx, shape))
+    cur = [frozenset(idx) for (_, _, _, idx) in ops]
+    worst = 1
+    for step in path:
+        taken = [cur[q] for q in step]
+        cur = [c for q, c in enumerate(cur) if q not in step]
+        rest = frozenset().union(*cur) if cur else frozenset()
+        res = frozenset(i for t in taken for i in t if i in rest)
+        worst = max(worst, int(np.prod([dims[i] for i in res], dtype=np.float64)) if res else 1)
+        cur.append(res)
+    return worst
+
+
+def _host_weight(bpc: BeliefPropagationCache, edges) -> complex:
+    """weight of a connected configuration that is not a simple cycle (a vertex of internal degree >= 3), contracted in complex128 on the host"""
+    ops, nlabels = _host_plan(bpc, edges)
+    if nlabels > 52:
+        raise L.TnqsError(f"loopcorrected_partitionfunction: configuration {tuple(edges)} has {nlabels} indices; the host contraction takes at most 52")
+    # the path and its largest intermediate from the shapes alone (zero-stride stand-ins: nothing is read back or allocated before the check)
+    fake = [np.lib.stride_tricks.as_strided(np.zeros(1), shape=sh, strides=(0,) * len(sh)) for (_, _, sh, _) in ops]
+    args = [x for f, (_, _, _, idx) in zip(fake, ops) for x in (f, idx)]
+    # numpy's greedy search only takes pairwise steps within the element limit it is given; what it cannot place is left as ONE step over all remaining
+    # operands (a naive nested loop): such a step means the limit cannot be kept
+    path = np.einsum_path(*args, [], optimize=("greedy", HOST_CONTRACTION_LIMIT - 1))[0][1:]
+    big = _largest_intermediate(ops, path)
+    if big >= HOST_CONTRACTION_LIMIT or any(len(step) > 2 for step in path):
+        big = max(big, HOST_CONTRACTION_LIMIT)
+        raise L.TnqsError(f"loopcorrected_partitionfunction: configuration {tuple(edges)} is not a simple cycle and its host contraction needs an intermediate "
+                          f"of at least {big} elements; intermediates must stay below {HOST_CONTRACTION_LIMIT} (2^24)")
+    real = []
+    for (kind, what, sh, idx) in ops:
+        if kind == "ket":
+            t = bpc.tensor(what).astype(np.complex128)
+        elif kind == "bra":
+            t = np.conj(bpc.tensor(what).astype(np.complex128))
+        elif kind == "msg":
+            t = bpc.message(what).astype(np.complex128)
+        else:
+            u, v = what
+            chi = sh[0]
+            eye = np.eye(chi)
+            # u's side pairs with the message INTO u, v's side with the message into v (bilinear)
+            t = np.einsum("ac,bd->abcd", eye, eye) - np.einsum("ab,cd->abcd", bpc.message((v, u)).astype(np.complex128), bpc.message((u, v)).astype(np.complex128))
+        real += [t, idx]
+    return complex(np.einsum(*real, [], optimize=["einsum_path"] + list(path)))
+
+
+def loopcorrected_partitionfunction(bpc: BeliefPropagationCache, max_configuration_size: int, connected_only: bool = False) -> complex:
+    """loopcorrected_partitionfunction (loopcorrection.jl:3-14): Z_bp (1 + sum_c W(c)) over the leafless edge-induced subgraphs c of at most
+    `max_configuration_size` edges, on a rescaled copy of the cache.  A disconnected configuration weighs the product of its components' weights
+    (`connected_only` leaves those out: DESIGN.md section 5 on what the reference's enumeration is not pinned to).  Simple cycles are weighed on the
+    device in one call; a connected configuration with a vertex of internal degree >= 3 is contracted on the host (_host_weight)."""
+    zbp = partitionfunction(bpc)
+    configs = leafless_edge_induced_subgraphs(bpc.graph, max_configuration_size, connected_only=connected_only)
+    if not configs:
+        return zbp
+    r = rescale(bpc)
+    parts = [connected_edge_components(c) for c in configs]
+    weight: Dict = {}
+    cycles, keys = [], []
+    for comp in dict.fromkeys(c for p in parts for c in p):
+        ring = _cycle_order(comp)
+        if ring is None:
+            weight[comp] = _host_weight(r, comp)
+        else:
+            cycles.append(ring); keys.append(comp)
+    if cycles:
+        for k, w in zip(keys, loop_weights(r, cycles)):
+            weight[k] = complex(w)
+    total = sum(complex(np.prod([weight[c] for c in p])) for p in parts)
+    return zbp * (1 + total)
+
+
+def norm_sqr(x, alg: str, max_configuration_size: Optional[int] = None, cache_update_kwargs: Optional[dict] = None, device: int = 0) -> complex:
+    """norm_sqr(psi; alg) (src/norm_sqr.jl:10-18,62-78) for alg = "bp" and "loopcorrections".  x: a TensorNetworkState (a cache is built and
+    updated with cache_update_kwargs, default default_bp_update_kwargs, on `device`) or an updated BeliefPropagationCache (which stays on its own device: `device` is not used)."""
+    if alg not in ("bp", "loopcorrections"):
+        raise L.TnqsError(f'norm_sqr: algorithm choice not supported; supported on the HIP path: "bp" and "loopcorrections" (received {alg!r})')
+    if alg == "loopcorrections" and max_configuration_size is None:
+        raise L.TnqsArgumentError('norm_sqr: alg = "loopcorrections" needs max_configuration_size')
+    if isinstance(x, TensorNetworkState):
+        bpc = BeliefPropagationCache(x, device=device)
+        bpc = update(bpc, **(bpc.default_bp_update_kwargs() if cache_update_kwargs is None else cache_update_kwargs))
+    elif isinstance(x, BeliefPropagationCache):
+        bpc = x
+    else:
+        raise TypeError("norm_sqr: expected a TensorNetworkState or a BeliefPropagationCache")
+    if alg == "bp":
+        return partitionfunction(bpc)
+    return loopcorrected_partitionfunction(bpc, int(max_configuration_size))
+
+
+def norm(x, alg: str, **kwargs) -> complex:
+    """norm = sqrt(norm_sqr) (src/norm_sqr.jl:80-81)"""
+    return complex(np.sqrt(complex(norm_sqr(x, alg, **kwargs))))
+
+
 def site_probabilities(bpc: BeliefPropagationCache, v) -> np.ndarray:
     """p[s] = real(diag rho_v)[s] / tr rho_v under the cache's messages: the weights `sample` draws the configuration of v from"""
     out = np.zeros(bpc._site_dim(v), dtype=np.float64)
@@ -708,7 +867,9 @@ def profile_enable(bpc: BeliefPropagationCache, on: bool = True):
 
 PROF_CLASSES = ("bp_modeprod", "bp_gram", "gate_modeprod", "gate_gram", "gate_apply", "jacobi", "small", "bp_fused", "bp_pair", "bp_pairgram",
                 # whole phases on the handle's stream (critical path; the kernel classes above overlap where a phase uses two streams): launches = sweeps / batches
-                "phase_bp_update", "phase_gate_batch")
+                "phase_bp_update", "phase_gate_batch",
+                # every launch of tnqs_loop_weights (loopcorrected_partitionfunction); flops = 8 m n k per complex product of the batched GEMM
+                "loop")
 
 
 def profile_get(bpc: BeliefPropagationCache) -> dict:

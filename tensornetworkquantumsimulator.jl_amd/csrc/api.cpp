@@ -132,6 +132,9 @@ int tnqs_site_probabilities(tnqs_handle h, int v, double* out_p) { return guard(
 int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uint64_t seed, const double* uniforms, int32_t* out_config, double* out_prob, tnqs_apply_stats* stats) {
     return guard([&] { sample_bp(S(h), nsamples, bp_opts, seed, uniforms, out_config, out_prob, stats); });
 }
+int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im) {
+    return guard([&] { loop_weights(S(h), ncycles, cycle_len, cycle_verts, out_re_im); });
+}
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out) {
     return guard([&] { if (!ops || !out) throw Err(TNQS_ERR_INVALID, "expect_all: null"); expect_all(S(h), ops, out); });
 }
@@ -212,7 +215,11 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                  void dbg_small_site(int nitems, const int* d, const int* z, const int* chi, const int* jo, const void* psi, const void* M, const int* present, int form,
                                      const void* old_msg, const int* has_old, int normalize, void* out, void* new_msg, double* diff, int* route);
                  void dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchunks, const void* partials, const void* old_msg, const int* has_old, int normalize,
-                                       void* new_msg, double* diff); }
+                                       void* new_msg, double* diff);
+                 void dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int* n, const int* k, const void* A, const void* B, void* C, int guard);
+                 void dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* T, const void* f, const void* b);
+                 void dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out);
+                 double dbg_pending_scale(State* s, int v); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
     return guard([&] { std::vector<int> a, b; dbg_default_sequence(*S(h)->g, a, b); *n_out = (int)a.size();
@@ -274,4 +281,10 @@ int tnqs_dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchu
                           void* new_msg, double* diff_out) {
     return guard([&] { dbg_msg_finalize(dtype, nitems, chi, nchunks, partials, old_msg, has_old, normalize, new_msg, diff_out); });
 }
+int tnqs_dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int* n, const int* k, const void* A, const void* B, void* C, int guard_elems) {
+    return guard([&] { dbg_loop_cgemm(dtype, opB, nitems, m, n, k, A, B, C, guard_elems); });
+}
+int tnqs_dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* T, const void* f, const void* b) { return guard([&] { dbg_loop_antiproject(dtype, nitems, nr, nc, T, f, b); }); }
+int tnqs_dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out) { return guard([&] { dbg_loop_trace(dtype, nitems, p, q, X, Y, out); }); }
+int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor) { return guard([&] { if (!factor) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: null output"); *factor = dbg_pending_scale(S(h), v); }); }
 }

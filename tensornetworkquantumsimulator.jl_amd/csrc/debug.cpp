@@ -763,4 +763,78 @@ void dbg_msg_finalize(int dtype, int nitems, const int* chi, const int* nchunks,
     for (int i = 0; i < nitems; ++i) { sNew.get(i, (char*)new_msg + om); om += sNew.len[i]; }
     if (diff) dDiff.down(diff, sizeof(double) * nitems);
 }
+
+// ---- loop corrections (kernels_loop.hip): ONE launch over nitems items of different shapes, the items' matrices one after the other in A, B (and C, between
+// guard bands of `guard` elements that the caller has filled and gets back: whatever the kernel must leave alone is seen to be left alone) ----
+void dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int* n, const int* k, const void* A, const void* B, void* C, int guard) {
+    need_gpu();
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !m || !n || !k || !A || !B || !C || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_loop_cgemm: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    size_t na = 0, nb = 0, nc = (size_t)guard;
+    std::vector<LoopGemmItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        if (m[i] < 1 || n[i] < 1 || k[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_loop_cgemm: m, n, k >= 1");
+        LoopGemmItem& it = items[i]; it = LoopGemmItem{};
+        it.A = (const void*)(na * esz); it.B = (const void*)(nb * esz); it.C = (void*)(nc * esz);      // offsets for now
+        it.m = m[i]; it.n = n[i]; it.k = k[i]; it.opB = opB ? 1 : 0; it.I0 = m[i]; it.si0 = 1; it.J0 = n[i]; it.sj0 = m[i];
+        na += (size_t)m[i] * k[i]; nb += (size_t)n[i] * k[i]; nc += (size_t)m[i] * n[i] + guard;
+    }
+    DBuf dA(na * esz), dB(nb * esz), dC(nc * esz), dI(sizeof(LoopGemmItem) * nitems);
+    for (auto& it : items) { it.A = (char*)dA.p + (size_t)it.A; it.B = (char*)dB.p + (size_t)it.B; it.C = (char*)dC.p + (size_t)it.C; }
+    const int tiles = plan_loop_cgemm(items.data(), nitems);
+    dA.up(A, na * esz); dB.up(B, nb * esz); dC.up(C, nc * esz); dI.up(items.data(), sizeof(LoopGemmItem) * nitems);
+    if (dtype == TNQS_C64) launch_loop_cgemm<float>(nullptr, (const LoopGemmItem*)dI.p, nitems, tiles); else launch_loop_cgemm<double>(nullptr, (const LoopGemmItem*)dI.p, nitems, tiles);
+    HIPCHK(hipDeviceSynchronize());
+    dC.down(C, nc * esz);
+}
+// T_i (nr[i] x nc[i], in place) <- T_i - f_i (b_i^T T_i); f, b: nr[i] elements per item
+void dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* Tm, const void* f, const void* b) {
+    need_gpu();
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !nr || !nc || !Tm || !f || !b) throw Err(TNQS_ERR_INVALID, "dbg_loop_antiproject: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    size_t nt = 0, nv = 0;
+    std::vector<LoopProjItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        if (nr[i] < 1 || nc[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_loop_antiproject: nr, nc >= 1");
+        items[i] = LoopProjItem{(void*)(nt * esz), (const void*)(nv * esz), (const void*)(nv * esz), nr[i], nc[i], 0};
+        nt += (size_t)nr[i] * nc[i]; nv += (size_t)nr[i];
+    }
+    DBuf dT(nt * esz), dF(nv * esz), dB(nv * esz), dI(sizeof(LoopProjItem) * nitems);
+    for (auto& it : items) { it.T = (char*)dT.p + (size_t)it.T; it.f = (char*)dF.p + (size_t)it.f; it.b = (char*)dB.p + (size_t)it.b; }
+    const int wgs = plan_loop_antiproject(items.data(), nitems);
+    dT.up(Tm, nt * esz); dF.up(f, nv * esz); dB.up(b, nv * esz); dI.up(items.data(), sizeof(LoopProjItem) * nitems);
+    if (dtype == TNQS_C64) launch_loop_antiproject<float>(nullptr, (const LoopProjItem*)dI.p, nitems, wgs); else launch_loop_antiproject<double>(nullptr, (const LoopProjItem*)dI.p, nitems, wgs);
+    HIPCHK(hipDeviceSynchronize());
+    dT.down(Tm, nt * esz);
+}
+// out[i] (complex128) = sum_ab X_i[a,b] Y_i[b,a]; X_i: p[i] x q[i], Y_i: q[i] x p[i]
+void dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out) {
+    need_gpu();
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !p || !q || !X || !Y || !out) throw Err(TNQS_ERR_INVALID, "dbg_loop_trace: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    size_t ne = 0;
+    std::vector<LoopTraceItem> items(nitems);
+    DBuf dP(sizeof(double) * 128 * nitems), dO(sizeof(double) * 2 * nitems);
+    for (int i = 0; i < nitems; ++i) {
+        if (p[i] < 1 || q[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_loop_trace: p, q >= 1");
+        items[i] = LoopTraceItem{(const void*)(ne * esz), (const void*)(ne * esz), p[i], q[i], (double*)dP.p + 128 * (size_t)i, (double*)dO.p + 2 * (size_t)i, 0, 0};
+        ne += (size_t)p[i] * q[i];
+    }
+    DBuf dX(ne * esz), dY(ne * esz), dI(sizeof(LoopTraceItem) * nitems);
+    for (auto& it : items) { it.X = (char*)dX.p + (size_t)it.X; it.Y = (char*)dY.p + (size_t)it.Y; }
+    const int wgs = plan_loop_trace(items.data(), nitems);
+    dX.up(X, ne * esz); dY.up(Y, ne * esz); dI.up(items.data(), sizeof(LoopTraceItem) * nitems);
+    if (dtype == TNQS_C64) launch_loop_trace<float>(nullptr, (const LoopTraceItem*)dI.p, nitems, wgs); else launch_loop_trace<double>(nullptr, (const LoopTraceItem*)dI.p, nitems, wgs);
+    HIPCHK(hipDeviceSynchronize());
+    dO.down(out, sizeof(double) * 2 * nitems);
+}
+// the pending real scale factor of site v (State::sscale): 1 when none is pending
+double dbg_pending_scale(State* s, int v) {
+    if (v < 0 || v >= s->g->nv) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: bad vertex");
+    if (!s->sscale[v]) return 1.0;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    double f = 1.0; HIPCHK(hipMemcpy(&f, s->sscale[v]->p, 8, hipMemcpyDeviceToHost));
+    return f;
+}
 }  // namespace tnqs

@@ -226,6 +226,8 @@ void site_dim(const State* s, int v, int* d);
 void project_site(State* s, int v, int config);
 void site_probabilities(State* s, int v, double* out_p);
 void sample_bp(State* s, int nsamples, const tnqs_bp_opts* bp, uint64_t seed, const double* uniforms, int32_t* out_config, double* out_prob, tnqs_apply_stats* stats);
+// engine_loops.cpp: W(cycle) = Tr prod_k (A_k T_k) for simple cycles of a rescaled cache (loopcorrection.jl:79-89); out: one complex128 per cycle
+void loop_weights(State* s, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im);
 void prof_collect(State* s);
 void materialize_pending_all(State* s);      // apply every deferred one-site gate (State::pend1)
 // sharding.cpp

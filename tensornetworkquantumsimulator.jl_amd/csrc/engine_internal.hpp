@@ -8,6 +8,7 @@
 //   engine_gates.cpp  apply_gates, one- and two-site gate batches, truncate
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
+//   engine_loops.cpp  loop corrections: transfer matrices of simple cycles, ring products, traces (batched)
 //   sharding.cpp      exchange step (RCCL or host callback)
 // and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
@@ -17,7 +18,7 @@
 //                      V recovery, small-SVD prepare / finish            kernels_gate.hip   fused gauge + f64 Gram of the gate path
 //   kernels_chol.hip   Cholesky (square / packed), env prepare / finish  kernels_f64.hip    ComplexF64 on the f64 matrix cores
 //   kernels_theta.hip  per-gate small algebra: gate_eigs .. gate_finish  kernels_sample.hip sampling
-//   kernels_util.hip   diag, norm factor, scale, pack, permute, fills
+//   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, antiprojector, trace
 #pragma once
 #include "engine.hpp"
 #include "kernels.hpp"

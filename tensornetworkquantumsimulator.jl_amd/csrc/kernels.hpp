@@ -290,6 +290,22 @@ template <class T> void launch_site_prob_partial(hipStream_t s, const void* tabs
 void launch_site_draw(hipStream_t s, const double* d_partial, int nblocks, int d, double neg_tol, const double* d_uniform, unsigned long long seed,
                       unsigned long long sample, unsigned long long step, bool draw, double* d_p, int* d_x, double* d_px, int* d_status);
 template <class T> void launch_site_project(hipStream_t s, const void* psi, void* out, size_t nout, int d, const int* d_x, int x_host);
+// loop corrections (kernels_loop.hip).  Column-major matrices without padding between columns.
+// C (m x n) = A (m x k) op(B); opB = 0: B is k x n; opB = 1: B is n x k and op(B) = B^H.  The result goes through a four-index map: row i = i0 + I0 i1
+// and column j = j0 + J0 j1 are stored at element  i0 si0 + i1 si1 + j0 sj0 + j1 sj1  of C (a plain matrix: I0 = m, si0 = 1, J0 = n, sj0 = m).
+// With A = phi and B = psi viewed as [(b, a), rest] and opB = 1 this writes a loop vertex's transfer matrix straight into T[(b, b'), (a, a')].
+struct LoopGemmItem { const void* A; const void* B; void* C; int m, n, k, opB; int I0, J0; long long si0, si1, sj0, sj1;
+                      int tile_begin, ntm, ntn; };      // set by plan_loop_cgemm: first workgroup, 64 x 64 tiles along m / n
+int plan_loop_cgemm(LoopGemmItem* it, int n);           // returns the launch's workgroups
+template <class T> void launch_loop_cgemm(hipStream_t s, const LoopGemmItem* d_items, int nitems, int total_tiles);
+// T (nr x nc) <- T - f (b^T T): f, b vectors of nr elements, bilinear pairing (no conjugate)
+struct LoopProjItem { void* T; const void* f; const void* b; int nr, nc; int wg_begin; };
+int plan_loop_antiproject(LoopProjItem* it, int n);
+template <class T> void launch_loop_antiproject(hipStream_t s, const LoopProjItem* d_items, int nitems, int total_wgs);
+// out (one complex128) = sum_ij X[i,j] Y[j,i], X p x q, Y q x p, accumulated in f64; partial: 2 nwg doubles of scratch (nwg <= 64, set by the plan)
+struct LoopTraceItem { const void* X; const void* Y; int p, q; double* partial; double* out; int wg_begin, nwg; };
+int plan_loop_trace(LoopTraceItem* it, int n);
+template <class T> void launch_loop_trace(hipStream_t s, const LoopTraceItem* d_items, int nitems, int total_wgs);
 // one-site gates on d = 2, ComplexF32: streaming 2x2 apply, norm partials [item][nbx]
 void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int nbx, double* d_norm_partials);
 

@@ -364,3 +364,112 @@ def steiner_region(g: "NamedGraph", verts) -> Tuple[List[Vertex], List[int]]:
                 seen[b] = len(region); region.append(b); parent.append(q)
         q += 1
     return region, parent
+
+
+MAX_CONNECTED_CONFIGURATIONS = 200_000      # a guard against an enumeration nobody can wait for, not a tuned number
+
+
+def connected_edge_components(edges) -> List[Tuple[Tuple[Vertex, Vertex], ...]]:
+    """the connected components of the edge-induced subgraph of `edges`, each as a tuple of edges in the order given"""
+    comp: Dict[Vertex, Vertex] = {}
+
+    def find(x):
+        comp.setdefault(x, x)
+        while comp[x] != x:
+            comp[x] = comp[comp[x]]
+            x = comp[x]
+        return x
+    for (a, b) in edges:
+        comp[find(a)] = find(b)
+    out: Dict[Vertex, list] = {}
+    for e in edges:
+        out.setdefault(find(e[0]), []).append(e)
+    return [tuple(c) for c in out.values()]
+
+
+def leafless_edge_induced_subgraphs(g: NamedGraph, max_edges: int, connected_only: bool = False) -> List[Tuple[Tuple[Vertex, Vertex], ...]]:
+    """Role of NamedGraphs.leafless_edge_induced_subgraphs(g, max_edges) in src/MessagePassing/loopcorrection.jl:9: every non-empty set of at most
+    `max_edges` edges whose edge-induced subgraph has no vertex of degree 1, as a tuple of edges of `g.edges` in edge order.
+    Connected sets are grown inside the 2-core (no edge outside it lies in a leafless subgraph): starting from each edge e, only edges after e are
+    added, and only through the exclusive neighbourhood of the set so far, so every connected set is reached exactly once; a branch whose leaves
+    cannot all be closed within the budget (one more edge closes at most two) is cut.  What survives are the simple cycles up to `max_edges`, their
+    unions, and cycles joined by paths.  Disconnected sets (unless `connected_only`) are the vertex-disjoint unions of connected ones within the budget.
+    Order: by number of edges, then by edge positions.  Raises TnqsError when more than MAX_CONNECTED_CONFIGURATIONS connected sets are found."""
+    from ._lib import TnqsError
+    max_edges = int(max_edges)
+    edges = list(g.edges)
+    ne = len(edges)
+    # 2-core
+    alive = [True] * ne
+    deg = {v: 0 for v in g.vertices}
+    inc: Dict[Vertex, List[int]] = {v: [] for v in g.vertices}
+    for i, (a, b) in enumerate(edges):
+        deg[a] += 1; deg[b] += 1; inc[a].append(i); inc[b].append(i)
+    stack = [v for v in g.vertices if deg[v] == 1]
+    while stack:
+        v = stack.pop()
+        for i in inc[v]:
+            if alive[i]:
+                alive[i] = False
+                for w in edges[i]:
+                    deg[w] -= 1
+                    if deg[w] == 1:
+                        stack.append(w)
+    adj = [[] for _ in range(ne)]      # line graph of the 2-core
+    for v in g.vertices:
+        es = [i for i in inc[v] if alive[i]]
+        for i in es:
+            adj[i] += [j for j in es if j != i]
+    adj = [sorted(set(a)) for a in adj]
+    found: List[Tuple[int, ...]] = []
+    vdeg: Dict[Vertex, int] = {}
+
+    def add(i, sign):
+        for w in edges[i]:
+            vdeg[w] = vdeg.get(w, 0) + sign
+            if vdeg[w] == 0:
+                del vdeg[w]
+
+    def extend(sub, ext, closed, root):
+        leaves = sum(1 for d in vdeg.values() if d == 1)
+        if leaves == 0:
+            found.append(tuple(sorted(sub)))
+            if len(found) > MAX_CONNECTED_CONFIGURATIONS:
+                raise TnqsError(f"leafless_edge_induced_subgraphs: more than {MAX_CONNECTED_CONFIGURATIONS} connected configurations of at most "
+                                f"{max_edges} edges; lower max_configuration_size")
+        if len(sub) + max(1, (leaves + 1) // 2) > max_edges:
+            return
+        ext = list(ext)
+        while ext:
+            w = ext.pop()
+            new = [u for u in adj[w] if u > root and u not in closed]
+            sub.append(w); add(w, +1)
+            extend(sub, ext + new, closed | set(new), root)
+            sub.pop(); add(w, -1)
+
+    if max_edges >= 3:
+        for root in range(ne):
+            if not alive[root]:
+                continue
+            nb = [u for u in adj[root] if u > root]
+            add(root, +1)
+            extend([root], nb, {root} | set(nb), root)
+            add(root, -1)
+    found.sort(key=lambda c: (len(c), c))
+    out = list(found)
+    if not connected_only:
+        verts = [frozenset(w for i in c for w in edges[i]) for c in found]
+
+        def unions(start, sub, used, size):
+            for q in range(start, len(found)):
+                c = found[q]
+                if size + len(c) > max_edges:
+                    break                                # sorted by size: nothing further fits
+                if used & verts[q]:
+                    continue
+                if sub:
+                    out.append(tuple(sorted(sub + c)))
+                unions(q + 1, sub + c, used | verts[q], size + len(c))
+        unions(0, (), frozenset(), 0)
+        out = found + sorted(out[len(found):], key=lambda c: (len(c), c))
+    return [tuple(edges[i] for i in c) for c in out]
