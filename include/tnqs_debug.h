@@ -112,6 +112,31 @@ int tnqs_dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int*
 int tnqs_dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* T_inout, const void* f, const void* b);
 /* loop_trace_kernel<T> + its tail: out[i] (complex128) = sum_ab X_i[a,b] Y_i[b,a], X_i p[i] x q[i], Y_i q[i] x p[i] */
 int tnqs_dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out_re_im);
+/* ---- the kernels that post-process a BP cache and prepare a gate's environments (dtype 0 c64 = T float, 1 c128 = T double; column-major n x n matrices).  ONE launch
+ * over nitems items of different n, descriptors filled as the engine fills them; on the device every array of every item starts at a multiple of 256 bytes.  Input
+ * arrays hold the items' matrices one after the other (a slot for every item, read only where its `present` flag is not 0 -- 0 hands the kernel a null pointer, i.e.
+ * the identity).  Every OUTPUT array with a `guard` holds guard elements, item 0, guard elements, item 1, ..., guard elements: it goes to the device as the caller
+ * filled it and comes back whole, so the caller sees that nothing outside the items was written.  n > 256: TNQS_ERR_UNSUPPORTED as in the engine, nothing is written ----
+ * msg_rescale_kernel<T>: rescale_messages! of one edge per item; present[2 i], present[2 i + 1]: me_i, mer_i */
+int tnqs_dbg_msg_rescale(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, void* me_out, void* mer_out, int guard);
+/* edge_scalar_kernel<T>: out_re_im[2 i], [2 i + 1] = sum_ab me_i[a,b] mer_i[a,b]; the array goes up as filled and comes back */
+int tnqs_dbg_edge_scalar(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, double* out_re_im);
+/* env_prepare_kernel<T>: H_i = (M_i + M_i^dagger) / 2, V_i = identity, both complex128; present[i] */
+int tnqs_dbg_env_prepare(int dtype, int nitems, const int* n, const void* msg, const int* present, void* H_out, void* V_out, int guard);
+/* env_finish_kernel<T>: from the complex128 eigen factors (A_i = H_i V_i, V_i): msqrt_i = H^1/2 and proj_i = H^1/2 H^-1/2 over the eigenvalues kept under cutoff[i]
+ * (type T); flags_out[2 i] = all kept, flags_out[2 i + 1] = a negative eigenvalue beyond the cutoff (the array goes up as filled and comes back) */
+int tnqs_dbg_env_finish(int dtype, int nitems, const int* n, const void* A, const void* V, const double* cutoff, void* msqrt_out, void* proj_out, int* flags_out, int guard);
+/* symg_build_kernel<T>: from the complex128 eigen factors of both messages of an edge: rx, ry = conj((M + reg)^1/2), irx, iry = conj((M + reg)^-1/2) (complex128) and
+ * Ce = Ce0 = rx ry^T (type T); *flag_out = 1 when any regularised eigenvalue of any item is negative (one flag per launch, cleared first, as in the engine) */
+int tnqs_dbg_symg_build(int dtype, int nitems, const int* n, const void* AX, const void* VX, const void* AY, const void* VY, double reg, void* rx, void* ry, void* irx, void* iry,
+                        void* Ce, void* Ce0, int* flag_out, int guard);
+/* symg_finish_kernel<T>: from U Sigma and V (type T, singular triplets as columns in any order) and irx, iry (complex128): S_i (n[i] doubles, descending; guard counts
+ * doubles), Xs_i = irx U S^1/2, Xd_i = iry conj(V) S^1/2 (type T) */
+int tnqs_dbg_symg_finish(int dtype, int nitems, const int* n, const void* USigma, const void* Vsvd, const void* irx, const void* iry, void* Xs, void* Xd, double* S, int guard);
+/* diag_kernel<T>: out_i = diag(S_i) (S: chi[i] doubles per item) */
+int tnqs_dbg_diag(int dtype, int nitems, const int* chi, const double* S, void* out, int guard);
+/* cscale_kernel<T>: dst_i = src_i (re[i] + i im[i]), len[i] numbers per item (any length) */
+int tnqs_dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard);
 /* the pending real scale factor of the site tensor of v (a normalising gate only records 1/||psi_v||; the tensor the reference holds is the stored one times it): 1 when none is pending */
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor);
 #ifdef __cplusplus

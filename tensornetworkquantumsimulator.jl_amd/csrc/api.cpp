@@ -219,6 +219,15 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                  void dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int* n, const int* k, const void* A, const void* B, void* C, int guard);
                  void dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* T, const void* f, const void* b);
                  void dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out);
+                 void dbg_msg_rescale(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, void* me_out, void* mer_out, int guard);
+                 void dbg_edge_scalar(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, double* out);
+                 void dbg_env_prepare(int dtype, int nitems, const int* n, const void* msg, const int* present, void* H_out, void* V_out, int guard);
+                 void dbg_env_finish(int dtype, int nitems, const int* n, const void* A, const void* V, const double* cutoff, void* msqrt_out, void* proj_out, int* flags_out, int guard);
+                 void dbg_symg_build(int dtype, int nitems, const int* n, const void* AX, const void* VX, const void* AY, const void* VY, double reg, void* rx, void* ry, void* irx, void* iry,
+                                     void* Ce, void* Ce0, int* flag_out, int guard);
+                 void dbg_symg_finish(int dtype, int nitems, const int* n, const void* USigma, const void* Vsvd, const void* irx, const void* iry, void* Xs, void* Xd, double* S, int guard);
+                 void dbg_diag(int dtype, int nitems, const int* chi, const double* S, void* out, int guard);
+                 void dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard);
                  double dbg_pending_scale(State* s, int v); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
@@ -286,5 +295,28 @@ int tnqs_dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int*
 }
 int tnqs_dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* T, const void* f, const void* b) { return guard([&] { dbg_loop_antiproject(dtype, nitems, nr, nc, T, f, b); }); }
 int tnqs_dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out) { return guard([&] { dbg_loop_trace(dtype, nitems, p, q, X, Y, out); }); }
+int tnqs_dbg_msg_rescale(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, void* me_out, void* mer_out, int guard_elems) {
+    return guard([&] { dbg_msg_rescale(dtype, nitems, chi, me, mer, present, me_out, mer_out, guard_elems); });
+}
+int tnqs_dbg_edge_scalar(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, double* out_re_im) {
+    return guard([&] { dbg_edge_scalar(dtype, nitems, chi, me, mer, present, out_re_im); });
+}
+int tnqs_dbg_env_prepare(int dtype, int nitems, const int* n, const void* msg, const int* present, void* H_out, void* V_out, int guard_elems) {
+    return guard([&] { dbg_env_prepare(dtype, nitems, n, msg, present, H_out, V_out, guard_elems); });
+}
+int tnqs_dbg_env_finish(int dtype, int nitems, const int* n, const void* A, const void* V, const double* cutoff, void* msqrt_out, void* proj_out, int* flags_out, int guard_elems) {
+    return guard([&] { dbg_env_finish(dtype, nitems, n, A, V, cutoff, msqrt_out, proj_out, flags_out, guard_elems); });
+}
+int tnqs_dbg_symg_build(int dtype, int nitems, const int* n, const void* AX, const void* VX, const void* AY, const void* VY, double reg, void* rx, void* ry, void* irx, void* iry,
+                        void* Ce, void* Ce0, int* flag_out, int guard_elems) {
+    return guard([&] { dbg_symg_build(dtype, nitems, n, AX, VX, AY, VY, reg, rx, ry, irx, iry, Ce, Ce0, flag_out, guard_elems); });
+}
+int tnqs_dbg_symg_finish(int dtype, int nitems, const int* n, const void* USigma, const void* Vsvd, const void* irx, const void* iry, void* Xs, void* Xd, double* S, int guard_elems) {
+    return guard([&] { dbg_symg_finish(dtype, nitems, n, USigma, Vsvd, irx, iry, Xs, Xd, S, guard_elems); });
+}
+int tnqs_dbg_diag(int dtype, int nitems, const int* chi, const double* S, void* out, int guard_elems) { return guard([&] { dbg_diag(dtype, nitems, chi, S, out, guard_elems); }); }
+int tnqs_dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard_elems) {
+    return guard([&] { dbg_cscale(dtype, nitems, len, src, re, im, dst, guard_elems); });
+}
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor) { return guard([&] { if (!factor) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: null output"); *factor = dbg_pending_scale(S(h), v); }); }
 }

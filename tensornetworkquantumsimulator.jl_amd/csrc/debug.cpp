@@ -828,6 +828,202 @@ void dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const voi
     HIPCHK(hipDeviceSynchronize());
     dO.down(out, sizeof(double) * 2 * nitems);
 }
+// ---- the kernels that post-process a BP cache and prepare a gate's environments (kernels_bp.hip: msg_rescale, edge_scalar, symg_build, symg_finish; kernels_chol.hip:
+// env_prepare, env_finish; kernels_util.hip: diag, cscale): ONE launch over nitems items of different n, the descriptors filled as engine_obs.cpp / engine_gates.cpp
+// fill them.  Inputs: the items' arrays one after the other.  Outputs: `guard` caller-filled elements, item 0, `guard` elements, item 1, ..., `guard` elements ----
+namespace {
+// an output array as the caller hands it over.  On the device every item starts at a multiple of 256 bytes with the guard band that follows it right behind it (the
+// leading band right in front of item 0); the alignment gaps keep a 0xff filling that is checked after the launch.  The whole array goes up as the caller filled it
+// and comes back whole, so a write outside an item shows in a guard band or is reported here
+struct Guarded {
+    size_t gb, total; std::vector<size_t> off, len; std::vector<char> host; std::unique_ptr<DBuf> dev;
+    explicit Guarded(size_t guard_bytes) : gb(guard_bytes), total(round256(guard_bytes)) {}
+    void add(size_t bytes) { off.push_back(total); len.push_back(bytes); total += round256(bytes + gb); }
+    void alloc() { host.assign(total ? total : 1, (char)0xff); dev.reset(new DBuf(total)); }
+    char* at(size_t i) const { return (char*)dev->p + off[i]; }
+    void up(const void* src) {
+        const char* p = (const char*)src;
+        std::memcpy(host.data() + round256(gb) - gb, p, gb); p += gb;
+        for (size_t i = 0; i < off.size(); ++i) { std::memcpy(host.data() + off[i], p, len[i] + gb); p += len[i] + gb; }
+        dev->up(host.data(), total);
+    }
+    void down(void* dst, const char* what) {
+        dev->down(host.data(), total);
+        auto gap = [&](size_t b0, size_t b1) { for (size_t b = b0; b < b1; ++b) if (host[b] != (char)0xff)
+                                                   throw Err(TNQS_ERR_INVALID, std::string("dbg: a kernel wrote outside an item of ") + what); };
+        gap(0, round256(gb) - gb);
+        for (size_t i = 0; i < off.size(); ++i) gap(off[i] + len[i] + gb, off[i] + round256(len[i] + gb));
+        char* p = (char*)dst;
+        std::memcpy(p, host.data() + round256(gb) - gb, gb); p += gb;
+        for (size_t i = 0; i < off.size(); ++i) { std::memcpy(p, host.data() + off[i], len[i] + gb); p += len[i] + gb; }
+    }
+};
+// input arrays: the items one after the other on the host, 256-byte aligned slots on the device
+void put_all(Slots& s, const void* src) { const char* p = (const char*)src; for (size_t i = 0; i < s.off.size(); ++i) { s.put(i, p); p += s.len[i]; } }
+void post_check(const char* who, int dtype, int nitems, const int* n, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !n || guard < 0) throw Err(TNQS_ERR_INVALID, std::string(who) + ": bad arguments");
+    for (int i = 0; i < nitems; ++i) {
+        if (n[i] < 1) throw Err(TNQS_ERR_INVALID, std::string(who) + ": n >= 1");
+        if (n[i] > 256) throw Err(TNQS_ERR_UNSUPPORTED, std::string(who) + ": bond dimension > 256");
+    }
+}
+}
+void dbg_msg_rescale(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, void* me_out, void* mer_out, int guard) {
+    need_gpu();
+    post_check("dbg_msg_rescale", dtype, nitems, chi, guard);
+    if (!me || !mer || !present || !me_out || !mer_out) throw Err(TNQS_ERR_INVALID, "dbg_msg_rescale: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sA, sB; Guarded gA(guard * esz), gB(guard * esz);
+    for (int i = 0; i < nitems; ++i) { const size_t mb = (size_t)chi[i] * chi[i] * esz; sA.add(mb); sB.add(mb); gA.add(mb); gB.add(mb); }
+    sA.alloc(); sB.alloc(); gA.alloc(); gB.alloc();
+    put_all(sA, me); put_all(sB, mer);
+    std::vector<MsgRescaleItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) items[i] = MsgRescaleItem{present[2 * i] ? sA.at(i) : nullptr, present[2 * i + 1] ? sB.at(i) : nullptr, gA.at(i), gB.at(i), chi[i]};
+    DBuf dI(sizeof(MsgRescaleItem) * nitems);
+    sA.up(); sB.up(); gA.up(me_out); gB.up(mer_out); dI.up(items.data(), sizeof(MsgRescaleItem) * nitems);
+    if (dtype == TNQS_C64) launch_msg_rescale<float>(nullptr, (const MsgRescaleItem*)dI.p, nitems); else launch_msg_rescale<double>(nullptr, (const MsgRescaleItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gA.down(me_out, "me_out"); gB.down(mer_out, "mer_out");
+}
+void dbg_edge_scalar(int dtype, int nitems, const int* chi, const void* me, const void* mer, const int* present, double* out) {
+    need_gpu();
+    post_check("dbg_edge_scalar", dtype, nitems, chi, 0);
+    if (!me || !mer || !present || !out) throw Err(TNQS_ERR_INVALID, "dbg_edge_scalar: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sA, sB;
+    for (int i = 0; i < nitems; ++i) { const size_t mb = (size_t)chi[i] * chi[i] * esz; sA.add(mb); sB.add(mb); }
+    sA.alloc(); sB.alloc();
+    put_all(sA, me); put_all(sB, mer);
+    DBuf dO(16 * (size_t)nitems), dI(sizeof(EdgeScalarItem) * nitems);
+    std::vector<EdgeScalarItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) items[i] = EdgeScalarItem{present[2 * i] ? sA.at(i) : nullptr, present[2 * i + 1] ? sB.at(i) : nullptr, chi[i], (double*)dO.p + 2 * i};
+    sA.up(); sB.up(); dO.up(out, 16 * (size_t)nitems); dI.up(items.data(), sizeof(EdgeScalarItem) * nitems);
+    if (dtype == TNQS_C64) launch_edge_scalar<float>(nullptr, (const EdgeScalarItem*)dI.p, nitems); else launch_edge_scalar<double>(nullptr, (const EdgeScalarItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    dO.down(out, 16 * (size_t)nitems);
+}
+void dbg_env_prepare(int dtype, int nitems, const int* n, const void* msg, const int* present, void* H_out, void* V_out, int guard) {
+    need_gpu();
+    post_check("dbg_env_prepare", dtype, nitems, n, guard);
+    if (!msg || !present || !H_out || !V_out) throw Err(TNQS_ERR_INVALID, "dbg_env_prepare: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sM; Guarded gH((size_t)guard * 16), gV((size_t)guard * 16);
+    for (int i = 0; i < nitems; ++i) { const size_t nn = (size_t)n[i] * n[i]; sM.add(nn * esz); gH.add(nn * 16); gV.add(nn * 16); }
+    sM.alloc(); gH.alloc(); gV.alloc();
+    put_all(sM, msg);
+    std::vector<EnvItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) items[i] = EnvItem{present[i] ? sM.at(i) : nullptr, gH.at(i), gV.at(i), n[i]};
+    DBuf dI(sizeof(EnvItem) * nitems);
+    sM.up(); gH.up(H_out); gV.up(V_out); dI.up(items.data(), sizeof(EnvItem) * nitems);
+    if (dtype == TNQS_C64) launch_env_prepare<float>(nullptr, (const EnvItem*)dI.p, nitems); else launch_env_prepare<double>(nullptr, (const EnvItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gH.down(H_out, "H"); gV.down(V_out, "V");
+}
+void dbg_env_finish(int dtype, int nitems, const int* n, const void* A, const void* V, const double* cutoff, void* msqrt_out, void* proj_out, int* flags_out, int guard) {
+    need_gpu();
+    post_check("dbg_env_finish", dtype, nitems, n, guard);
+    if (!A || !V || !cutoff || !msqrt_out || !proj_out || !flags_out) throw Err(TNQS_ERR_INVALID, "dbg_env_finish: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sA, sV; Guarded gM(guard * esz), gP(guard * esz);
+    for (int i = 0; i < nitems; ++i) { const size_t nn = (size_t)n[i] * n[i]; sA.add(nn * 16); sV.add(nn * 16); gM.add(nn * esz); gP.add(nn * esz); }
+    sA.alloc(); sV.alloc(); gM.alloc(); gP.alloc();
+    put_all(sA, A); put_all(sV, V);
+    DBuf dF(sizeof(int) * 2 * nitems), dI(sizeof(EnvFinishItem) * nitems);
+    std::vector<EnvFinishItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) items[i] = EnvFinishItem{sA.at(i), sV.at(i), gM.at(i), gP.at(i), n[i], cutoff[i], (int*)dF.p + 2 * i};
+    sA.up(); sV.up(); gM.up(msqrt_out); gP.up(proj_out); dF.up(flags_out, sizeof(int) * 2 * nitems); dI.up(items.data(), sizeof(EnvFinishItem) * nitems);
+    if (dtype == TNQS_C64) launch_env_finish<float>(nullptr, (const EnvFinishItem*)dI.p, nitems); else launch_env_finish<double>(nullptr, (const EnvFinishItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gM.down(msqrt_out, "msqrt"); gP.down(proj_out, "proj"); dF.down(flags_out, sizeof(int) * 2 * nitems);
+}
+// (the pointers of a SymGaugeItem that the launched kernel does not use point at a scratch slot of the item's size)
+void dbg_symg_build(int dtype, int nitems, const int* n, const void* AX, const void* VX, const void* AY, const void* VY, double reg, void* rx, void* ry, void* irx, void* iry,
+                    void* Ce, void* Ce0, int* flag_out, int guard) {
+    need_gpu();
+    post_check("dbg_symg_build", dtype, nitems, n, guard);
+    if (!AX || !VX || !AY || !VY || !rx || !ry || !irx || !iry || !Ce || !Ce0 || !flag_out) throw Err(TNQS_ERR_INVALID, "dbg_symg_build: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sAX, sVX, sAY, sVY, scr; Guarded gRx((size_t)guard * 16), gRy((size_t)guard * 16), gIx((size_t)guard * 16), gIy((size_t)guard * 16), gC(guard * esz), gC0(guard * esz);
+    for (int i = 0; i < nitems; ++i) {
+        const size_t nn = (size_t)n[i] * n[i];
+        for (Slots* s : {&sAX, &sVX, &sAY, &sVY, &scr}) s->add(nn * 16);
+        for (Guarded* g : {&gRx, &gRy, &gIx, &gIy}) g->add(nn * 16);
+        gC.add(nn * esz); gC0.add(nn * esz);
+    }
+    for (Slots* s : {&sAX, &sVX, &sAY, &sVY, &scr}) s->alloc();
+    for (Guarded* g : {&gRx, &gRy, &gIx, &gIy, &gC, &gC0}) g->alloc();
+    put_all(sAX, AX); put_all(sVX, VX); put_all(sAY, AY); put_all(sVY, VY);
+    DBuf dFlag(sizeof(int)), dI(sizeof(SymGaugeItem) * nitems);
+    HIPCHK(hipMemset(dFlag.p, 0, sizeof(int)));          // one flag for the whole launch, cleared first (engine_obs.cpp)
+    std::vector<SymGaugeItem> items(nitems);
+    for (int i = 0; i < nitems; ++i)
+        items[i] = SymGaugeItem{sAX.at(i), sVX.at(i), sAY.at(i), sVY.at(i), gRx.at(i), gRy.at(i), gIx.at(i), gIy.at(i), gC.at(i), gC0.at(i), scr.at(i), scr.at(i), scr.at(i),
+                                (double*)scr.at(i), n[i], reg, (int*)dFlag.p};
+    sAX.up(); sVX.up(); sAY.up(); sVY.up(); scr.up();
+    gRx.up(rx); gRy.up(ry); gIx.up(irx); gIy.up(iry); gC.up(Ce); gC0.up(Ce0); dI.up(items.data(), sizeof(SymGaugeItem) * nitems);
+    if (dtype == TNQS_C64) launch_symg_build<float>(nullptr, (const SymGaugeItem*)dI.p, nitems); else launch_symg_build<double>(nullptr, (const SymGaugeItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gRx.down(rx, "rx"); gRy.down(ry, "ry"); gIx.down(irx, "irx"); gIy.down(iry, "iry"); gC.down(Ce, "Ce"); gC0.down(Ce0, "Ce0");
+    dFlag.down(flag_out, sizeof(int));
+}
+void dbg_symg_finish(int dtype, int nitems, const int* n, const void* USigma, const void* Vsvd, const void* irx, const void* iry, void* Xs, void* Xd, double* S, int guard) {
+    need_gpu();
+    post_check("dbg_symg_finish", dtype, nitems, n, guard);
+    if (!USigma || !Vsvd || !irx || !iry || !Xs || !Xd || !S) throw Err(TNQS_ERR_INVALID, "dbg_symg_finish: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sU, sV, sIx, sIy, scr; Guarded gXs(guard * esz), gXd(guard * esz), gS((size_t)guard * 8);
+    for (int i = 0; i < nitems; ++i) {
+        const size_t nn = (size_t)n[i] * n[i];
+        sU.add(nn * esz); sV.add(nn * esz); sIx.add(nn * 16); sIy.add(nn * 16); scr.add(nn * 16);
+        gXs.add(nn * esz); gXd.add(nn * esz); gS.add((size_t)n[i] * 8);
+    }
+    for (Slots* s : {&sU, &sV, &sIx, &sIy, &scr}) s->alloc();
+    gXs.alloc(); gXd.alloc(); gS.alloc();
+    put_all(sU, USigma); put_all(sV, Vsvd); put_all(sIx, irx); put_all(sIy, iry);
+    DBuf dFlag(sizeof(int)), dI(sizeof(SymGaugeItem) * nitems);
+    HIPCHK(hipMemset(dFlag.p, 0, sizeof(int)));
+    std::vector<SymGaugeItem> items(nitems);
+    for (int i = 0; i < nitems; ++i)
+        items[i] = SymGaugeItem{scr.at(i), scr.at(i), scr.at(i), scr.at(i), scr.at(i), scr.at(i), sIx.at(i), sIy.at(i), sU.at(i), scr.at(i), sV.at(i), gXs.at(i), gXd.at(i),
+                                (double*)gS.at(i), n[i], 0.0, (int*)dFlag.p};
+    sU.up(); sV.up(); sIx.up(); sIy.up(); scr.up(); gXs.up(Xs); gXd.up(Xd); gS.up(S); dI.up(items.data(), sizeof(SymGaugeItem) * nitems);
+    if (dtype == TNQS_C64) launch_symg_finish<float>(nullptr, (const SymGaugeItem*)dI.p, nitems); else launch_symg_finish<double>(nullptr, (const SymGaugeItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gXs.down(Xs, "Xs"); gXd.down(Xd, "Xd"); gS.down(S, "S");
+}
+void dbg_diag(int dtype, int nitems, const int* chi, const double* S, void* out, int guard) {
+    need_gpu();
+    post_check("dbg_diag", dtype, nitems, chi, guard);
+    if (!S || !out) throw Err(TNQS_ERR_INVALID, "dbg_diag: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sS; Guarded gO(guard * esz);
+    for (int i = 0; i < nitems; ++i) { sS.add((size_t)chi[i] * 8); gO.add((size_t)chi[i] * chi[i] * esz); }
+    sS.alloc(); gO.alloc();
+    put_all(sS, S);
+    std::vector<DiagItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) items[i] = DiagItem{gO.at(i), (const double*)sS.at(i), chi[i]};
+    DBuf dI(sizeof(DiagItem) * nitems);
+    sS.up(); gO.up(out); dI.up(items.data(), sizeof(DiagItem) * nitems);
+    if (dtype == TNQS_C64) launch_diag<float>(nullptr, (const DiagItem*)dI.p, nitems); else launch_diag<double>(nullptr, (const DiagItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gO.down(out, "out");
+}
+void dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard) {
+    need_gpu();
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !len || !src || !re || !im || !dst || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_cscale: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sS; Guarded gD(guard * esz);
+    for (int i = 0; i < nitems; ++i) { if (len[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_cscale: len >= 1"); sS.add((size_t)len[i] * esz); gD.add((size_t)len[i] * esz); }
+    sS.alloc(); gD.alloc();
+    put_all(sS, src);
+    std::vector<CScaleItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) items[i] = CScaleItem{sS.at(i), gD.at(i), (size_t)len[i], re[i], im[i]};
+    DBuf dI(sizeof(CScaleItem) * nitems);
+    sS.up(); gD.up(dst); dI.up(items.data(), sizeof(CScaleItem) * nitems);
+    if (dtype == TNQS_C64) launch_cscale<float>(nullptr, (const CScaleItem*)dI.p, nitems); else launch_cscale<double>(nullptr, (const CScaleItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gD.down(dst, "dst");
+}
 // the pending real scale factor of site v (State::sscale): 1 when none is pending
 double dbg_pending_scale(State* s, int v) {
     if (v < 0 || v >= s->g->nv) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: bad vertex");
