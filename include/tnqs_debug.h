@@ -45,8 +45,8 @@ int tnqs_dbg_bench_plane(int which, int nsites, int lx, int ly, int reps, double
  * *route_out (may be NULL) says which kernel ran: */
 #define TNQS_DBG_ROUTE_X3 1            /* bf16 x 3 matrix-core kernel (kernels_x3.hip: x3_rowgemm64_kernel, x3_gram64_kernel) */
 #define TNQS_DBG_ROUTE_F32 2           /* f32 matrix-core kernel (mfma_rowgemm_kernel<KB, NB, D>, mfma_gram64_kernel) */
-#define TNQS_DBG_ROUTE_F64 3           /* mfma_gram128_f64_kernel<true, false> */
-#define TNQS_DBG_ROUTE_F64_SHARED 4    /* mfma_gram128_f64_kernel<true, true> (every item has D K = 128) */
+#define TNQS_DBG_ROUTE_F64 3           /* mfma_gram128_f64_kernel<false> */
+#define TNQS_DBG_ROUTE_F64_SHARED 4    /* mfma_gram128_f64_kernel<true> (every item has D K = 128) */
 #define TNQS_DBG_ROUTE_HALF_LINES 5    /* mfma_pair16_kernel (planes that contain leg 0) */
 #define TNQS_DBG_ROUTE_WHOLE_LINES 6   /* mfma_pair16w_kernel */
 #define TNQS_DBG_ROUTE_SMALL_SCALAR 7  /* bp_small_site_kernel<1024>, scalar form */

@@ -5,7 +5,6 @@ set -e
 cd "$(dirname "$0")"
 OUT=../libtnqs_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result ${EXTRA_FLAGS:-}"
-[ "${EXPERIMENTS:-0}" = "1" ] && FLAGS="$FLAGS -DTNQS_EXPERIMENTS"      # kernel-experiment switches (engine_internal.hpp); never in the shipped build
 mkdir -p build
 # an object is stale when its source, any header here or the C ABI header is newer than it
 stale() { local d; [ -f "$2" ] || return 0; for d in "$1" *.hpp ../../include/tnqs.h; do [ "$d" -nt "$2" ] && return 0; done; return 1; }

@@ -1,5 +1,5 @@
 // device_common.hpp -- the device-side vocabulary shared by every kernel translation unit: the launch check, vector types, complex numbers,
-// wave / workgroup sums and the f64 matrix-core tile products.  (mfma_common.hpp adds the MFMA tile machinery on top of it.)
+// wave / workgroup sums, the item lookup of batched launches and the f64 matrix-core tile products.  (mfma_common.hpp adds the MFMA tile machinery on top of it.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -45,6 +45,13 @@ __device__ __forceinline__ double block_sum(double v, double* sh /* >= 17 double
     if (threadIdx.x == 0) { double t = 0; for (int i = 0; i < nw; ++i) t += sh[i]; sh[16] = t; }
     __syncthreads();
     return sh[16];
+}
+
+// the item of a batched launch that owns workgroup (tile, chunk, element) `id`: the last one whose `begin` is <= id
+template <class Item> __device__ __forceinline__ int find_item(const Item* __restrict__ items, int nitems, int Item::*begin, int id) {
+    int lo = 0, hi = nitems - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (items[mid].*begin <= id) lo = mid; else hi = mid - 1; }
+    return lo;
 }
 
 // one 16 x 16 complex f64 tile product on v_mfma_f64_16x16x4_f64: lane (l15, kq) supplies A[row i][k0 + kq] = fa(i, k) and B[k0 + kq][column j] = fb(k, j)

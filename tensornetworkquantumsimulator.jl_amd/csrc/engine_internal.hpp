@@ -68,8 +68,7 @@ TNQS_SWITCH(speculation_on, !envflag("TNQS_NO_SPECULATION"))     // apply_gates 
 // TNQS_JACOBI_GLOBAL=1: every Jacobi factorisation in the global-memory kernel (the route matrices beyond the LDS take);
 // tunables: TNQS_ARENA_KB (pinned staging arena; tests of its overflow path), TNQS_BP_WS_MB (workspace bound of a BP sub-batch), TNQS_BP_CACHE_MB, TNQS_RCCL_LIB (sharding.cpp),
 //           TNQS_FORCE_EXCHANGE (a one-rank RCCL handle takes the sharded path); diagnostics: TNQS_HOST_TIMING, TNQS_DEBUG_SWEEPS.
-// Kernel experiments are NOT in the shipped library: they only exist in a build with -DTNQS_EXPERIMENTS (csrc/build.sh EXPERIMENTS=1); the kernel-level entry points of
-// include/tnqs_debug.h (debug.cpp) read TNQS_DBG_* themselves and are not part of the hot path.
+// The kernel-level entry points of include/tnqs_debug.h (debug.cpp) read TNQS_DBG_* themselves and are not part of the hot path.
 // TNQS_BP_CACHE_MB: bound on the partial products kept across BP levels (MiB, default 49152)
 inline size_t bp_cache_budget() { static const size_t v = [] { const char* e = std::getenv("TNQS_BP_CACHE_MB"); return (e ? (size_t)std::atoll(e) : (size_t)49152) << 20; }(); return v; }
 inline size_t bp_ws_budget() { static const size_t v = [] { const char* e = std::getenv("TNQS_BP_WS_MB"); return (e ? (size_t)std::atoll(e) : (size_t)24576) << 20; }(); return v; }

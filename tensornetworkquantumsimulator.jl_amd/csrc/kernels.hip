@@ -22,9 +22,8 @@ __global__ __launch_bounds__(256) void fiber_gemm_kernel(const FiberItem* __rest
     cx<T>* tile = reinterpret_cast<cx<T>*>(smem);
     __shared__ double sh_red[17];
     const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
     const int gt = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].tile_begin <= gt) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &FiberItem::tile_begin, gt);
     const FiberItem it = items[lo];
     const int lt = gt - it.tile_begin;
     const int ta = lt % it.nta, tb = lt / it.nta;
@@ -93,9 +92,8 @@ template <class T, class Acc, int MAXB>
 __global__ __launch_bounds__(256) void gram_kernel(const GramItem* __restrict__ items, int nitems, int TR) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
@@ -223,8 +221,7 @@ template <class Acc, class Out>
 __global__ __launch_bounds__(256) void reduce_kernel(const ReduceItem* __restrict__ items, int nitems, int total) {
     int ge = blockIdx.x * 256 + threadIdx.x;
     if (ge >= total) return;
-    int lo = 0, hi = nitems - 1;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].elem_begin <= ge) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &ReduceItem::elem_begin, ge);
     const ReduceItem it = items[lo];
     int e = ge - it.elem_begin;
     const cx<Acc>* p = reinterpret_cast<const cx<Acc>*>(it.partial);

@@ -19,7 +19,6 @@ namespace tnqs {
 // Tiles of 64 fibers, LDS layout [kk][row] (rows contiguous = memory order); wave w takes 16 rows of every tile and the whole 64 x 64
 // output (four 32 x 32 accumulator pairs); the next tile's loads are in flight during the MFMA block.  32 flop/B when X != Y.
 // ------------------------------------------------------------------------------------------------------------
-template <bool M3>
 __global__ __launch_bounds__(256, 2) void mfma_gram64_kernel(const GramItem* __restrict__ items, int nitems) {
     constexpr int TR = 64, TRP = TR + 4, NU = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -28,9 +27,8 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_kernel(const GramItem* __r
     float* const Yr = Xi + 64 * TRP;
     float* const Yi = Yr + 64 * TRP;
     const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
@@ -45,7 +43,7 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_kernel(const GramItem* __r
     // wave w: output rows block a = w & 1 (i in [32 a, 32 a + 32)) x all 64 columns, tile rows 32 (w >> 1) .. + 32 -- 64 accumulator
     // registers per wave instead of 128, so that TWO workgroups fit a CU (one's barriers and LDS commits hide behind the other's MFMAs)
     const int a = w & 1, rh = w >> 1;
-    CAcc32<M3> C[2];                                             // M3: three-multiplication product (mfma_common.hpp)
+    CAcc32<true> C[2];                                           // three-multiplication product (mfma_common.hpp)
     C[0].zero(); C[1].zero();
     for (int e = tid; e < 64 * TRP; e += 256) { Xr[e] = 0.f; Xi[e] = 0.f; Yr[e] = 0.f; Yi[e] = 0.f; }
     const TileMap m = make_map(tid, D, TA, TB, PA, K);
@@ -178,7 +176,7 @@ bool launch_mfma_gram64(hipStream_t s, const GramItem* d_items, int nitems, int 
     if (total_chunks <= 0) return true;
     if (mfma_use_x3()) return launch_x3_gram64(s, d_items, nitems, total_chunks, KKmax);
     const size_t lds = (size_t)4 * 64 * 68 * sizeof(float);
-    set_max_dynamic_lds((const void*)mfma_gram64_kernel<true>, lds); hipLaunchKernelGGL(mfma_gram64_kernel<true>, dim3(total_chunks), dim3(256), lds, s, d_items, nitems);
+    set_max_dynamic_lds((const void*)mfma_gram64_kernel, lds); hipLaunchKernelGGL(mfma_gram64_kernel, dim3(total_chunks), dim3(256), lds, s, d_items, nitems);
     TNQS_CHECK_LAUNCH();
     return true;
 }
@@ -374,17 +372,18 @@ void launch_copy_items(hipStream_t s, const CopyItem* d_items, int nitems) {
 //     two site components of one n, one 16-byte store).
 // One wave per SIMD (accumulators + the two half-tile operand sets: up to 256 registers); the wave never waits on a workgroup barrier.
 // ------------------------------------------------------------------------------------------------------------
-template <int KB, int NB, int D, bool M3>
+template <int KB, int NB, int D>
 __global__ __launch_bounds__(256, (KB * NB <= 4 ? 2 : 1)) void mfma_rowgemm_kernel(const FiberItem* __restrict__ items, int nitems, double* __restrict__ norm_partials) {
     constexpr int KK = 32 * KB, NQ = KK / 2;                   // k-steps per tile
+    // three-multiplication product except for K = N = 128: its 16 blocks x 3 accumulators do not fit next to the operand registers (21 spills)
+    constexpr bool M3 = KB * NB <= 4;
     constexpr int NL = (D == 1) ? NQ : NQ / 2;                 // loads per lane and tile (8 bytes each for D = 1, 16 bytes for D = 2)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     v2f* const Xl = reinterpret_cast<v2f*>(smem);             // [q][nb][lane]
     __shared__ double sh_red[4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    int lo = 0, hi = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].tile_begin <= gw) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &FiberItem::tile_begin, gw);
     const FiberItem it = items[lo];
     const int K = it.K, No = it.No, NN = it.Do * No;
     const long long PA = it.PA;
@@ -433,7 +432,7 @@ __global__ __launch_bounds__(256, (KB * NB <= 4 ? 2 : 1)) void mfma_rowgemm_kern
     int t = t_begin + w;
     if (t < t_end) { issue_half(t, 0); issue_half(t, 1); }
     for (; t < t_end; t += 4) {
-        CAcc32<M3> C[NB];                                                        // three accumulators per block with the three-multiplication product
+        CAcc32<M3> C[NB];                                                        // M3: three accumulators per block
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
 #pragma unroll
@@ -510,15 +509,8 @@ int plan_rowgemm(FiberItem* it, int n, int cap, int* nwg, int tpw) {
 }
 template <int KB, int NB, int D> static void launch_rowgemm_t(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, double* d_norm_partials) {
     const size_t lds = (size_t)(16 * KB) * NB * 64 * sizeof(v2f);
-    // three-multiplication product except for K = N = 128: its 16 blocks x 3 accumulators do not fit next to the operand registers (21 spills)
-    constexpr bool fits3 = KB * NB <= 4;
-    if (fits3) {
-        set_max_dynamic_lds((const void*)mfma_rowgemm_kernel<KB, NB, D, fits3>, lds);
-        hipLaunchKernelGGL((mfma_rowgemm_kernel<KB, NB, D, fits3>), dim3(total_wgs), dim3(256), lds, s, d_items, nitems, d_norm_partials);
-    } else {
-        set_max_dynamic_lds((const void*)mfma_rowgemm_kernel<KB, NB, D, false>, lds);
-        hipLaunchKernelGGL((mfma_rowgemm_kernel<KB, NB, D, false>), dim3(total_wgs), dim3(256), lds, s, d_items, nitems, d_norm_partials);
-    }
+    set_max_dynamic_lds((const void*)mfma_rowgemm_kernel<KB, NB, D>, lds);
+    hipLaunchKernelGGL((mfma_rowgemm_kernel<KB, NB, D>), dim3(total_wgs), dim3(256), lds, s, d_items, nitems, d_norm_partials);
     TNQS_CHECK_LAUNCH();
 }
 // all items of one launch must share K and D (the caller groups them)
@@ -544,23 +536,22 @@ void launch_mfma_rowgemm(hipStream_t s, const FiberItem* d_items, int nitems, in
 //   wave w = 0, 1, 2:  {(w,w),(w,w+1),(w,w+2)},  {(w+3,w+3),(w+3,w+4),(w+3,w+5)},  {(w,w+3),(w,w+4),(w,w+5)}      (rows from one panel)
 //   wave 3          :  {(0,7),(1,7),(3,7)},  {(4,7),(6,7),(7,7)},  {(0,6),(3,6),(6,6)}                              (columns from one panel)
 // set s of a wave owns accumulator slots 3 s .. 3 s + 2
-template <bool ROW, int DIAGJ, bool M3>
+template <bool ROW, int DIAGJ>
 __device__ __forceinline__ void gram128_set(const float* __restrict__ Xr, const float* __restrict__ Xi, int TRP, int l15, int kq, int P, int q0, int q1, int q2,
                                             v4d& r0, v4d& r1, v4d& r2, v4d& i0, v4d& i1, v4d& i2, v4d& c0, v4d& c1, v4d& c2) {
     const int Q[3] = {q0, q1, q2};
     v4d r[3] = {r0, r1, r2}, i[3] = {i0, i1, i2}, c[3] = {c0, c1, c2};
-    gram_f64_shared<3, ROW, DIAGJ, M3>(Xr, Xi, TRP, l15, kq, P, Q, r, i, c);
+    gram_f64_shared<3, ROW, DIAGJ>(Xr, Xi, TRP, l15, kq, P, Q, r, i, c);
     r0 = r[0]; r1 = r[1]; r2 = r[2]; i0 = i[0]; i1 = i[1]; i2 = i[2]; c0 = c[0]; c1 = c[1]; c2 = c[2];
 }
-template <bool M3, bool SHARED>
+template <bool SHARED>
 __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* __restrict__ items, int nitems) {
     constexpr int TR = 64, TRP = TR + 4, NU = 16, KKP = 128, NBW = 9;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* const Xbuf = reinterpret_cast<float*>(smem);          // [buf][re|im][KKP * TRP]
     const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
@@ -587,7 +578,7 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
             else { bI[q] = rI[q]; bJ[q] = rJ[q]; }
         }
     }
-    v4d Cr[NBW], Ci[NBW], Cc[NBW];                             // M3: sum (ar+ai) br,  sum ai (br-bi),  sum ar (bi+br)  (CAcc32::mac_conj in f64)
+    v4d Cr[NBW], Ci[NBW], Cc[NBW];                             // sum (ar+ai) br,  sum ai (br-bi),  sum ar (bi+br)  (three multiplications: CAcc32::mac_conj in f64)
 #pragma unroll
     for (int q = 0; q < NBW; ++q)
 #pragma unroll
@@ -657,7 +648,7 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
         if (t + 1 < t_end) { if (fast) { commit_loads(cur ^ 1); if (t + 2 < t_end) issue_loads(t + 2); } else fill_slow(t + 1, cur ^ 1); }
         const float* Xr = Xbuf + cur * (2 * KKP * TRP); const float* Xi = Xr + KKP * TRP;
         if (SHARED) {
-#define TNQS_SET(ROW, DJ, S, P, A, B, C) gram128_set<ROW, DJ, M3>(Xr, Xi, TRP, l15, kq, P, A, B, C, Cr[3 * S], Cr[3 * S + 1], Cr[3 * S + 2], \
+#define TNQS_SET(ROW, DJ, S, P, A, B, C) gram128_set<ROW, DJ>(Xr, Xi, TRP, l15, kq, P, A, B, C, Cr[3 * S], Cr[3 * S + 1], Cr[3 * S + 2], \
                                                                   Ci[3 * S], Ci[3 * S + 1], Ci[3 * S + 2], Cc[3 * S], Cc[3 * S + 1], Cc[3 * S + 2])
             if (w < 3) {
                 TNQS_SET(true, 0, 0, w, w, w + 1, w + 2);
@@ -684,16 +675,9 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const double ar = (double)t0[c], ai = (double)t1[c], br = (double)u0[c], bi = (double)u1[c];
-                        if (M3) {                                                                      // out[i][j] += x[i] conj(x[j])
-                            Cr[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar + ai, br, Cr[q], 0, 0, 0);
-                            Ci[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br - bi, Ci[q], 0, 0, 0);
-                            Cc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi + br, Cc[q], 0, 0, 0);
-                        } else {
-                            Cr[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, Cr[q], 0, 0, 0);
-                            Ci[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, Ci[q], 0, 0, 0);
-                            Cr[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bi, Cr[q], 0, 0, 0);
-                            Ci[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ar, bi, Ci[q], 0, 0, 0);
-                        }
+                        Cr[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar + ai, br, Cr[q], 0, 0, 0);       // out[i][j] += x[i] conj(x[j])
+                        Ci[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br - bi, Ci[q], 0, 0, 0);
+                        Cc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi + br, Cc[q], 0, 0, 0);
                     }
                 }
             }
@@ -708,7 +692,7 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * bI[q] + kq + 4 * r, j = 16 * bJ[q] + l15;
             if (i < KK && j < KK) {
-                cx<double> v; v.re = M3 ? Cr[q][r] - Ci[q][r] : Cr[q][r]; v.im = M3 ? Cr[q][r] - Cc[q][r] : Ci[q][r]; part[i + (size_t)KK * j] = v;
+                cx<double> v; v.re = Cr[q][r] - Ci[q][r]; v.im = Cr[q][r] - Cc[q][r]; part[i + (size_t)KK * j] = v;
                 if (bI[q] != bJ[q]) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }
             }
         }
@@ -718,8 +702,8 @@ bool launch_mfma_gram128_f64(hipStream_t s, const GramItem* d_items, int nitems,
     if (KKmax > 128) return false;
     if (total_chunks <= 0) return true;
     const size_t lds = (size_t)4 * 128 * 68 * sizeof(float);
-#define TNQS_G128(M3, SH) { set_max_dynamic_lds((const void*)mfma_gram128_f64_kernel<M3, SH>, lds); hipLaunchKernelGGL((mfma_gram128_f64_kernel<M3, SH>), dim3(total_chunks), dim3(256), lds, s, d_items, nitems); }
-    if (all_kk128) TNQS_G128(true, true) else TNQS_G128(true, false)
+#define TNQS_G128(SH) { set_max_dynamic_lds((const void*)mfma_gram128_f64_kernel<SH>, lds); hipLaunchKernelGGL(mfma_gram128_f64_kernel<SH>, dim3(total_chunks), dim3(256), lds, s, d_items, nitems); }
+    if (all_kk128) TNQS_G128(true) else TNQS_G128(false)
 #undef TNQS_G128
     TNQS_CHECK_LAUNCH();
     return true;

@@ -41,9 +41,8 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_f64_kernel(const FiberIte
     __shared__ double sh_red[17];
     zc* const XT = reinterpret_cast<zc*>(smem);                 // X^T[nn][kk] at nn * KP + kk
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, kq = lane >> 4;
-    int lo = 0, hi = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].tile_begin <= gw) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &FiberItem::tile_begin, gw);
     const FiberItem it = items[lo];
     const int D = GEN ? it.D : 1, Do = GEN ? it.Do : 1, K = it.K, No = it.No, KK = D * K, NN = Do * No;
     const int KP = ((KK + 3) & ~3) + 1;                          // row pitch: whole k-steps + 1 (odd: the 16 rows of a b128 read fall into different banks)
@@ -160,9 +159,8 @@ __global__ __launch_bounds__(256) void mfma_gram_f64in_kernel(const GramItem* __
     extern __shared__ __attribute__((aligned(16))) char smem[];
     zc* const Lb = reinterpret_cast<zc*>(smem);                  // [buf 2][tensor 2][MAXC * TFP]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, kq = lane >> 4;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;

@@ -23,7 +23,7 @@ namespace tnqs {
 //              v_mfma_f32_32x32x2_f32 with Gauss' three products; A operand 16 consecutive floats per lane (k-step t <-> r = t + 16 h),
 //              B operand = A^T staged once per workgroup; the result is written over the wave's own rows;
 //   Gram       the ten upper 16 x 16 blocks of G on v_mfma_f64_16x16x4_f64 in panel-sharing sets, 3M in f64 (gram_f64_shared), dealt to
-//              the waves exactly as in mfma_gram64_f64_kernel<true, true> (same partial layout: 2 per chunk, one per tile parity).
+//              the waves exactly as in mfma_gram64_f64_kernel<true> (same partial layout: 2 per chunk, one per tile parity).
 // Pipeline: iteration t commits and transforms tile t + 1 in the other buffer, issues the loads of tile t + 2, then multiplies tile t;
 // ONE workgroup barrier per tile.
 // X3 (round 5, default): the transform on the bf16 matrix cores -- the tile rows split exactly into three bf16 pieces on the fly, the matrix A split once per
@@ -37,9 +37,8 @@ __global__ __launch_bounds__(256, 2) void mfma_gauge_gram64_kernel(const GramIte
     float* const Mr = Xbuf + 4 * PLANE;                          // A[r][r'] at r * 32 + r' (re), then (im)
     float* const Mi = Mr + 1024;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, kq = lane >> 4;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int TA = it.TA, TB = it.TB;
@@ -161,20 +160,20 @@ __global__ __launch_bounds__(256, 2) void mfma_gauge_gram64_kernel(const GramIte
         const float* Xr = Xbuf + cur * (2 * PLANE); const float* Xi = Xr + PLANE;
         if (((t - t_begin) & 1) == parA) {                         // wave-uniform
             const int q3[3] = {0, 1, 2};
-            if (w & 1) gram_f64_shared<3, false, -1, true>(Xr, Xi, TRP, l15, kq, 3, q3, CAr, CAi, CAc);
-            else       gram_f64_shared<3, true, 0, true>(Xr, Xi, TRP, l15, kq, 0, q3, CAr, CAi, CAc);
+            if (w & 1) gram_f64_shared<3, false, -1>(Xr, Xi, TRP, l15, kq, 3, q3, CAr, CAi, CAc);
+            else       gram_f64_shared<3, true, 0>(Xr, Xi, TRP, l15, kq, 0, q3, CAr, CAi, CAc);
         } else if (w & 1) {
             const int q2[1] = {2}, q3b[1] = {3};
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 v4d r1[1] = {CBr[b]}, i1[1] = {CBi[b]}, c1[1] = {CBc[b]};
-                if (b == 0) gram_f64_shared<1, true, 0, true>(Xr, Xi, TRP, l15, kq, 2, q2, r1, i1, c1);
-                else        gram_f64_shared<1, true, 0, true>(Xr, Xi, TRP, l15, kq, 3, q3b, r1, i1, c1);
+                if (b == 0) gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 2, q2, r1, i1, c1);
+                else        gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 3, q3b, r1, i1, c1);
                 CBr[b] = r1[0]; CBi[b] = i1[0]; CBc[b] = c1[0];
             }
         } else {
             const int q12[2] = {1, 2};
-            gram_f64_shared<2, true, 0, true>(Xr, Xi, TRP, l15, kq, 1, q12, CBr, CBi, CBc);
+            gram_f64_shared<2, true, 0>(Xr, Xi, TRP, l15, kq, 1, q12, CBr, CBi, CBc);
         }
         lds_barrier();                                              // tile t consumed by everybody, tile t+1 transformed by everybody
     }
@@ -241,9 +240,8 @@ __global__ __launch_bounds__(256, 3) void mfma_gauge_gram32_kernel(const GramIte
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, kq = lane >> 4;
     float* const Xr = reinterpret_cast<float*>(smem) + w * SLAB; float* const Xi = Xr + PL;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const long long PA = it.PA;

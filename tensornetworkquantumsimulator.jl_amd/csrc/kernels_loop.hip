@@ -34,9 +34,8 @@ template <class T> __global__ __launch_bounds__(256) void loop_cgemm_kernel(cons
     __shared__ __attribute__((aligned(16))) cx<T> As[KT * P];
     __shared__ __attribute__((aligned(16))) cx<T> Bs[KT * P];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, wr = w & 1, wc = w >> 1;
-    int lo = 0, hi = nitems - 1;
     const int gt = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].tile_begin <= gt) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &LoopGemmItem::tile_begin, gt);
     const LoopGemmItem it = items[lo];
     const int lt = gt - it.tile_begin;
     if (lt >= it.ntm * it.ntn) return;
@@ -167,9 +166,8 @@ template void launch_loop_cgemm<double>(hipStream_t, const LoopGemmItem*, int, i
 
 // ---- antiprojector: T <- T - f (b^T T), bilinear (no conjugate).  One wave per column: w = sum_i b[i] T[i, c], then T[i, c] -= f[i] w ------
 template <class T> __global__ __launch_bounds__(256) void loop_antiproject_kernel(const LoopProjItem* __restrict__ items, int nitems) {
-    int lo = 0, hi = nitems - 1;
     const int gt = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].wg_begin <= gt) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &LoopProjItem::wg_begin, gt);
     const LoopProjItem it = items[lo];
     const int c = 4 * (gt - it.wg_begin) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= it.nc) return;
@@ -196,9 +194,8 @@ template void launch_loop_antiproject<double>(hipStream_t, const LoopProjItem*, 
 // of X and leaves one complex128 partial; the tail kernel (one workgroup per item) sums an item's partials ---------------------------------------------
 template <class T> __global__ __launch_bounds__(256) void loop_trace_kernel(const LoopTraceItem* __restrict__ items, int nitems) {
     __shared__ double sh[17];
-    int lo = 0, hi = nitems - 1;
     const int gt = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].wg_begin <= gt) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &LoopTraceItem::wg_begin, gt);
     const LoopTraceItem it = items[lo];
     const int lw = gt - it.wg_begin;
     if (lw >= it.nwg) return;

@@ -6,7 +6,6 @@
 //      A[i = ln][k = h]   B[k = h][j = ln]   C[row = (r&3) + 8*(r>>2) + 4*h][col = ln],  r = 0..15
 // Because the k index only has to be consistent between A and B, k-step t of a 32-deep block is mapped to
 // k = t + 16*h, so every lane reads 16 CONSECUTIVE floats of its operand row from LDS (4 x ds_read_b128).
-#include <cstdlib>
 #include "kernels.hpp"
 #include "mfma_common.hpp"
 #include <type_traits>
@@ -16,182 +15,11 @@ namespace tnqs {
 
 // ------------------------------------------------------------------------------------------------------------
 // fiber GEMM:  out[(s',n),(a,b)] = sum_{(s,k)} in[(s,k),(a,b)] X[(s,k),(s',n)]   with D*K <= 32*KB, Do*No <= 32*NB.
-// One workgroup stages X^T once and walks `tpw` consecutive tiles of TR fibers; the next tile's global loads are
-// issued before the MFMA block of the current one.  Zero padding in LDS makes any K, N legal.
-// ------------------------------------------------------------------------------------------------------------
-template <int KB, int NB, int TR>
-__global__ __launch_bounds__(256) void mfma_fiber_gemm_kernel(const FiberItem* __restrict__ items, int nitems,
-                                                              double* __restrict__ norm_partials) {
-    constexpr int KKP = 32 * KB, NNP = 32 * NB;
-    constexpr int CP = (KKP > NNP ? KKP : NNP);
-    constexpr int PT = CP + 1;         // odd pitch: conflict-free row-strided writes and ds_read_b32 operand reads
-    constexpr int PX = KKP + 1;
-    constexpr int RB = TR / 32;
-    constexpr int NU = 8;              // max units per thread per tile
-    static_assert(RB * NB == 4, "one (row block, column block) unit per wave");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* At_re = reinterpret_cast<float*>(smem);
-    float* At_im = At_re + TR * PT;
-    float* Xt_re = At_im + TR * PT;
-    float* Xt_im = Xt_re + NNP * PX;
-    __shared__ double sh_red[4];
-    const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
-    const int gw = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].tile_begin <= gw) lo = mid; else hi = mid - 1; }
-    const FiberItem it = items[lo];
-    const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
-    const int Do = it.Do, No = it.No, NN = Do * No;
-    const long long PA = it.PA;
-    const int ntiles = it.nta * it.ntb;
-    const int t_begin = (gw - it.tile_begin) * it.tpw;
-    const int t_end = min(ntiles, t_begin + it.tpw);
-    const cf* __restrict__ in = reinterpret_cast<const cf*>(it.in);
-    const cf* __restrict__ X = reinterpret_cast<const cf*>(it.X);
-    cf* __restrict__ out = reinterpret_cast<cf*>(it.out);
-    // ---- stage X^T (zero padded) once ---------------------------------------------------------------------------
-    for (int e = tid; e < NNP * KKP; e += 256) {
-        int kk = e & (KKP - 1), nn = e / KKP;
-        cf v; v.re = 0.f; v.im = 0.f;
-        if (kk < KK && nn < NN) v = X[kk + (size_t)KK * nn];
-        Xt_re[nn * PX + kk] = v.re; Xt_im[nn * PX + kk] = v.im;
-    }
-    // zero the whole A tile once (padding columns / rows stay zero: tiles only overwrite valid cells)
-    for (int e = tid; e < TR * PT; e += 256) { At_re[e] = 0.f; At_im[e] = 0.f; }
-    const TileMap mi = make_map(tid, D, TA, TB, PA, K);
-    const TileMap mo = make_map(tid, Do, TA, TB, PA, No);
-    const long long kstride_in = (long long)D * PA, kstride_out = (long long)Do * PA;
-    const bool fast = mi.U <= 256 && mo.U <= 256 && (K + mi.KP - 1) / mi.KP <= NU;
-    const int lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    const int rb = w % RB, cb = w / RB;
-    v4f pre[NU];
-    auto tile_origin = [&](int t, int& a0, int& b0, int& na, int& nb) {
-        int ta = t % it.nta, tb = t / it.nta;
-        a0 = ta * TA; b0 = tb * TB; na = min(TA, it.PA - a0); nb = min(TB, it.PB - b0);
-    };
-    auto issue_loads = [&](int t) {
-        int a0, b0, na, nb; tile_origin(t, a0, b0, na, nb);
-        const long long org = (long long)D * (a0 + PA * (long long)K * b0);
-        const bool v0 = mi.active && mi.al < na && mi.bl < nb, v1 = v0 && mi.al1 < na;
-#pragma unroll
-        for (int j = 0; j < NU; ++j) {
-            int k = mi.kp + mi.KP * j;
-            v4f v; v[0] = v[1] = v[2] = v[3] = 0.f;
-            if (k < K && v0) {
-                const cf* p = in + org + mi.off + kstride_in * k;
-                if (mi.vec == 2 && v1) v = ldg4(p);
-                else { cf x = ldgc(p); v[0] = x.re; v[1] = x.im; }
-            }
-            pre[j] = v;
-        }
-    };
-    auto commit_loads = [&]() {
-        if (!mi.active) return;
-#pragma unroll
-        for (int j = 0; j < NU; ++j) {
-            int k = mi.kp + mi.KP * j;
-            if (k < K) {
-                int kk0 = mi.c0 + D * k;
-                At_re[mi.row0 * PT + kk0] = pre[j][0]; At_im[mi.row0 * PT + kk0] = pre[j][1];
-                if (mi.vec == 2) { int kk1 = mi.c1 + D * k; At_re[mi.row1 * PT + kk1] = pre[j][2]; At_im[mi.row1 * PT + kk1] = pre[j][3]; }
-            }
-        }
-    };
-    double nrm = 0;
-    if (fast && t_begin < t_end) issue_loads(t_begin);
-    for (int t = t_begin; t < t_end; ++t) {
-        int a0, b0, na, nb; tile_origin(t, a0, b0, na, nb);
-        lds_barrier();                       // previous tile's output has left the LDS tile
-        if (fast) commit_loads();
-        else {
-            const int ntile_el = D * TA * K * TB;
-            for (int e = tid; e < ntile_el; e += 256) {
-                int s = e % D; int r1 = e / D; int al = r1 % TA; int r2 = r1 / TA; int k = r2 % K; int bl = r2 / K;
-                cf v; v.re = 0.f; v.im = 0.f;
-                if (al < na && bl < nb) v = in[s + D * ((long long)(a0 + al) + PA * ((long long)k + (long long)K * (b0 + bl)))];
-                int row = al + TA * bl;
-                At_re[row * PT + s + D * k] = v.re; At_im[row * PT + s + D * k] = v.im;
-            }
-        }
-        lds_barrier();
-        if (fast && t + 1 < t_end) issue_loads(t + 1);       // in flight while the matrix cores work
-        v16f Cr, Ci;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { Cr[r] = 0.f; Ci[r] = 0.f; }
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-            float ar[16], ai[16], br[16], bi[16];
-            const float* pa_r = At_re + (32 * rb + ln) * PT + 32 * kb + 16 * h;
-            const float* pa_i = At_im + (32 * rb + ln) * PT + 32 * kb + 16 * h;
-            const float* pb_r = Xt_re + (32 * cb + ln) * PX + 32 * kb + 16 * h;
-            const float* pb_i = Xt_im + (32 * cb + ln) * PX + 32 * kb + 16 * h;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) { ar[q] = pa_r[q]; ai[q] = pa_i[q]; br[q] = pb_r[q]; bi[q] = pb_i[q]; }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                Cr = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[q], br[q], Cr, 0, 0, 0);
-                Cr = __builtin_amdgcn_mfma_f32_32x32x2f32(-ai[q], bi[q], Cr, 0, 0, 0);
-                Ci = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[q], bi[q], Ci, 0, 0, 0);
-                Ci = __builtin_amdgcn_mfma_f32_32x32x2f32(ai[q], br[q], Ci, 0, 0, 0);
-            }
-        }
-        lds_barrier();       // every wave has read its operands: the tile rows can now take the results
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            int row = 32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h;
-            At_re[row * PT + 32 * cb + ln] = Cr[r];
-            At_im[row * PT + 32 * cb + ln] = Ci[r];
-        }
-        lds_barrier();
-        // ---- coalesced store of the output tile ---------------------------------------------------------------
-        if (fast) {
-            const long long org = (long long)Do * (a0 + PA * (long long)No * b0);
-            const bool v0 = mo.active && mo.al < na && mo.bl < nb, v1 = v0 && mo.al1 < na;
-            if (v0) {
-                for (int n = mo.kp; n < No; n += mo.KP) {
-                    int nn0 = mo.c0 + Do * n;
-                    v4f v;
-                    v[0] = At_re[mo.row0 * PT + nn0]; v[1] = At_im[mo.row0 * PT + nn0];
-                    cf* p = out + org + mo.off + kstride_out * n;
-                    nrm += (double)v[0] * v[0] + (double)v[1] * v[1];
-                    if (mo.vec == 2 && v1) {
-                        int nn1 = mo.c1 + Do * n;
-                        v[2] = At_re[mo.row1 * PT + nn1]; v[3] = At_im[mo.row1 * PT + nn1];
-                        nrm += (double)v[2] * v[2] + (double)v[3] * v[3];
-                        stg4(p, v);
-                    } else { cf x; x.re = v[0]; x.im = v[1]; stgc(p, x); }
-                }
-            }
-        } else {
-            const int nout_el = Do * TA * No * TB;
-            for (int e = tid; e < nout_el; e += 256) {
-                int sp = e % Do; int r1 = e / Do; int al = r1 % TA; int r2 = r1 / TA; int n = r2 % No; int bl = r2 / No;
-                if (al < na && bl < nb) {
-                    int row = al + TA * bl, nn = sp + Do * n;
-                    cf v; v.re = At_re[row * PT + nn]; v.im = At_im[row * PT + nn];
-                    out[sp + Do * ((long long)(a0 + al) + PA * ((long long)n + (long long)No * (b0 + bl)))] = v;
-                    nrm += (double)v.re * v.re + (double)v.im * v.im;
-                }
-            }
-        }
-        // the result cells written beyond the valid KK columns must be cleared again for the next tile's operands
-        if (NN > KK || KK < KKP) {
-            lds_barrier();
-            for (int e = tid; e < TR * (CP - KK); e += 256) { int row = e / (CP - KK), c = KK + e % (CP - KK); At_re[row * PT + c] = 0.f; At_im[row * PT + c] = 0.f; }
-        }
-    }
-    if (it.want_norm) {
-        nrm = wave_sum(nrm);
-        if (lane == 0) sh_red[w] = nrm;
-        __syncthreads();
-        if (tid == 0) norm_partials[gw] = sh_red[0] + sh_red[1] + sh_red[2] + sh_red[3];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// wave-private variant: every wave owns tiles of 32 fibers and its own LDS slab, so there is NO workgroup barrier in
-// the tile loop -- the 3-4 waves resident on a SIMD drift apart and one wave's MFMA block overlaps the others'
-// global / LDS phases.  This is the production kernel; the workgroup-tile kernel above is kept for A/B.
+// One workgroup stages X^T once and walks `tpw` consecutive tiles.  Every wave owns tiles of 32 fibers and its own LDS
+// slab, so there is NO workgroup barrier in the tile loop -- the 3-4 waves resident on a SIMD drift apart and one wave's
+// MFMA block overlaps the others' global / LDS phases; a wave's next tile's global loads are issued before the MFMA
+// block of its current one.  Zero padding in LDS makes any K, N legal.  Odd pitches (PT, PX): conflict-free row-strided
+// writes and ds_read_b32 operand reads.  NU: max units per thread per tile.
 // ------------------------------------------------------------------------------------------------------------
 template <int KB, int NB, int NU>
 __global__ __launch_bounds__(256) void mfma_fiber_gemm_w_kernel(const FiberItem* __restrict__ items, int nitems,
@@ -206,9 +34,8 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_w_kernel(const FiberItem*
     float* At_re = Xt_im + NNP * PX + w * (2 * 32 * PT);
     float* At_im = At_re + 32 * PT;
     __shared__ double sh_red[4];
-    int lo = 0, hi = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].tile_begin <= gw) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &FiberItem::tile_begin, gw);
     const FiberItem it = items[lo];
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
     const int Do = it.Do, No = it.No, NN = Do * No;
@@ -364,53 +191,25 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_w_kernel(const FiberItem*
     }
 }
 
-template <int KB, int NB, int TR> static size_t fiber_lds() {
+// X^T and the four waves' slabs (two planes of 32 rows each)
+template <int KB, int NB> static size_t fiber_lds() {
     constexpr int KKP = 32 * KB, NNP = 32 * NB; constexpr int CP = (KKP > NNP ? KKP : NNP);
-    return (size_t)(2 * TR * (CP + 1) + 2 * NNP * (KKP + 1)) * sizeof(float);
+    return (size_t)(4 * 2 * 32 * (CP + 1) + 2 * NNP * (KKP + 1)) * sizeof(float);
 }
-static int g_wave_private = -1;
-static bool wave_private() {
-    if (g_wave_private < 0) {
-        g_wave_private = 1;
-#ifdef TNQS_EXPERIMENTS
-        const char* e = getenv("TNQS_MFMA_WG_TILES"); if (e && e[0] == '1') g_wave_private = 0;
-#endif
-    }
-    return g_wave_private == 1;
-}
-int mfma_fiber_tile_rows(int KK, int NN) {
-    if (wave_private()) return (KK <= 64 && NN <= 64) ? 32 : 0;
-    if (KK <= 32 && NN <= 32) return 128;
-    if (KK <= 64 && NN <= 64) return 64;
-    return 0;
-}
+int mfma_fiber_tile_rows(int KK, int NN) { return (KK <= 64 && NN <= 64) ? 32 : 0; }
 // returns false if the shape is not covered (caller falls back to the generic kernel)
 bool launch_mfma_fiber_gemm(hipStream_t s, const FiberItem* d_items, int nitems, int total_tiles, int KKmax, int NNmax,
                             double* d_norm_partials) {
     if (total_tiles <= 0) return true;
-    if (wave_private()) {
-        if (KKmax <= 32 && NNmax <= 32) {
-            const size_t lds = fiber_lds<1, 1, 128>();
-            hipLaunchKernelGGL((mfma_fiber_gemm_w_kernel<1, 1, 8>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
-            return true;
-        }
-        if (KKmax <= 64 && NNmax <= 64) {
-            const size_t lds = fiber_lds<2, 2, 128>();
-            set_max_dynamic_lds((const void*)mfma_fiber_gemm_w_kernel<2, 2, 16>, (size_t)lds);
-            hipLaunchKernelGGL((mfma_fiber_gemm_w_kernel<2, 2, 16>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
-            return true;
-        }
-        return false;
-    }
     if (KKmax <= 32 && NNmax <= 32) {
-        const size_t lds = fiber_lds<1, 1, 128>();
-        hipLaunchKernelGGL((mfma_fiber_gemm_kernel<1, 1, 128>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
+        const size_t lds = fiber_lds<1, 1>();
+        hipLaunchKernelGGL((mfma_fiber_gemm_w_kernel<1, 1, 8>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
         return true;
     }
     if (KKmax <= 64 && NNmax <= 64) {
-        const size_t lds = fiber_lds<2, 2, 64>();
-        set_max_dynamic_lds((const void*)mfma_fiber_gemm_kernel<2, 2, 64>, (size_t)lds);
-        hipLaunchKernelGGL((mfma_fiber_gemm_kernel<2, 2, 64>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
+        const size_t lds = fiber_lds<2, 2>();
+        set_max_dynamic_lds((const void*)mfma_fiber_gemm_w_kernel<2, 2, 16>, (size_t)lds);
+        hipLaunchKernelGGL((mfma_fiber_gemm_w_kernel<2, 2, 16>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
         return true;
     }
     return false;
@@ -428,9 +227,8 @@ __global__ __launch_bounds__(256) void mfma_gram32_kernel(const GramItem* __rest
     __shared__ __attribute__((aligned(16))) float Yr[32 * TRP];
     __shared__ __attribute__((aligned(16))) float Yi[32 * TRP];
     const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
@@ -543,9 +341,8 @@ __global__ __launch_bounds__(256) void mfma_gram32_fused_kernel(const GramItem* 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
     float* Lr = reinterpret_cast<float*>(smem) + w * (2 * 32 * PITCH);
     float* Li = Lr + 32 * PITCH;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int K = it.K, TA = it.TA, TB = it.TB;            // D == 1, TA*TB == 64, K <= 32
@@ -654,18 +451,10 @@ void launch_mfma_gram32_fused(hipStream_t s, const GramItem* d_items, int nitems
 // loads of the phase after it arrive (one every six MFMAs of step 1) and are committed over the locations the same thread just stored
 // from -- so one barrier per phase orders everything.
 // ------------------------------------------------------------------------------------------------------------
-// XCD-aware workgroup order: consecutive workgroup ids go round-robin over the 8 XCDs, so XCD x sees ids x, x+8, ...  Remapping id ->
-// (id % 8) * (n/8) + id / 8 gives every XCD one contiguous range of the work list (neighbouring slices share DRAM pages and L2 sets).
-__device__ __forceinline__ int xcd_remap(int id, int n, int mode) {
-    if (!mode) return id;
-    const int n8 = (n >> 3) << 3;
-    return id < n8 ? (id & 7) * (n8 >> 3) + (id >> 3) : id;
-}
 __device__ __forceinline__ long long pair_slice_base(const PairGeom& g, int sl) {
     int a0 = sl % g.n0; int r1 = sl / g.n0; int a1 = r1 % g.n1; int a2 = r1 / g.n1;
     return (long long)a0 * g.t0 + (long long)a1 * g.t1 + (long long)a2 * g.t2;
 }
-template <bool M3>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void mfma_pair_kernel(const PairItem* __restrict__ items, int nitems) {
     constexpr int PS = 32 * 33 + 4;            // plane stride in complex elements, pitch 33 (rows and columns both conflict-free)
     constexpr int BUF = 8 * PS;
@@ -673,9 +462,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     extern __shared__ __attribute__((aligned(16))) char smem[];
     v2f* L = reinterpret_cast<v2f*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    int lo = 0, hi_ = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].slice_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int lo = find_item(items, nitems, &PairItem::slice_begin, gw);
     const PairItem it = items[lo];
     const PairGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2;
@@ -733,7 +521,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < 4; ++i) xc[i] = P[ln * 33 + i + 16 * h];            // A[i = iy = ln][k = ix]
         // ---- step 1 ---------------------------------------------------------------------------------------------------------------
-        CAcc32<M3> Y;
+        CAcc32<true> Y;
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4) {
             if (c4 < 3) {
@@ -745,20 +533,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int i = 0; i < 4; ++i) {
                 const int q = 4 * c4 + i;
                 const float br = mxr[q], bi = mxi[q];
-                if (q == 0) Y.template mac_bpre<true>(xc[i][0], xc[i][1], br, M3 ? bi - br : bi, M3 ? br + bi : -bi);
-                else Y.template mac_bpre<false>(xc[i][0], xc[i][1], br, M3 ? bi - br : bi, M3 ? br + bi : -bi);
+                if (q == 0) Y.template mac_bpre<true>(xc[i][0], xc[i][1], br, bi - br, br + bi);
+                else Y.template mac_bpre<false>(xc[i][0], xc[i][1], br, bi - br, br + bi);
                 if ((q & 1) == 0) { pre[q >> 1] = ldg4(in + nb + tstr * (q >> 1)); TNQS_PIN(); }      // next phase's loads, one every two updates
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) xc[i] = xn[i];
         }
         // ---- step 2 (and the previous phase's plane on its way out) -----------------------------------------------------------------
-        CAcc32<M3> S;
+        CAcc32<true> S;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float br = myr[r], bi = myi[r];
-            if (r == 0) S.template mac_bpre<true>(Y.re(r), Y.im(r), br, M3 ? bi - br : bi, M3 ? br + bi : -bi);
-            else S.template mac_bpre<false>(Y.re(r), Y.im(r), br, M3 ? bi - br : bi, M3 ? br + bi : -bi);
+            if (r == 0) S.template mac_bpre<true>(Y.re(r), Y.im(r), br, bi - br, br + bi);
+            else S.template mac_bpre<false>(Y.re(r), Y.im(r), br, bi - br, br + bi);
             if ((r & 1) == 0) { if (prev) store1(buf ^ 1, ob, r >> 1); TNQS_PIN(); }
         }
         S.finish();
@@ -782,10 +570,6 @@ static int pair_slices(const PairGeom& g) { return g.n0 * g.n1 * g.n2; }
 int plan_pair(PairItem* it, int n, int spw) {
     if (spw <= 0) {
         double tot = 0; for (int i = 0; i < n; ++i) tot += pair_slices(it[i].g); spw = 16; while (spw > 1 && 2.0 * tot / spw < 1024.0) spw >>= 1;
-#ifdef TNQS_EXPERIMENTS
-        static const int forced = [] { const char* e = std::getenv("TNQS_PAIR_SPW"); return e ? std::atoi(e) : 0; }();
-        if (forced > 0) spw = forced;
-#endif
     }
     return lay_out(it, n, &PairItem::slice_begin, nullptr, [&](PairItem& p) { p.spw = spw; const int np = (pair_slices(p.g) + spw - 1) / spw; return 16 * ((np + 7) / 8); });
 }
@@ -793,7 +577,7 @@ void launch_mfma_pair(hipStream_t s, const PairItem* d_items, int nitems, int to
     if (total_wgs <= 0) return;
     if (mfma_use_x3()) { launch_x3_pair(s, d_items, nitems, total_wgs); return; }
     const size_t lds = (size_t)16 * (32 * 33 + 4) * 2 * sizeof(float);
-    set_max_dynamic_lds((const void*)mfma_pair_kernel<true>, lds); hipLaunchKernelGGL(mfma_pair_kernel<true>, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
+    set_max_dynamic_lds((const void*)mfma_pair_kernel, lds); hipLaunchKernelGGL(mfma_pair_kernel, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
     TNQS_CHECK_LAUNCH();
 }
 
@@ -806,14 +590,13 @@ void launch_mfma_pair(hipStream_t s, const PairItem* d_items, int nitems, int to
 //   step 2  out[b][b'] += sum_jx C1[jx][b] conj Y[jx][b']    (A = C1's accumulator registers as they are, B = Y plane)
 // Each wave owns two planes and one 32 x 32 accumulator; it writes one partial per workgroup and wave.
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void mfma_pair_gram_kernel(const PairGramItem* __restrict__ items, int nitems, int xcd) {
+__global__ __launch_bounds__(512) void mfma_pair_gram_kernel(const PairGramItem* __restrict__ items, int nitems) {
     constexpr int PS = 32 * 33 + 1;            // plane stride in complex elements ((re, im) pairs, ds_*_b64 accesses)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     v2f* L = reinterpret_cast<v2f*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    int lo = 0, hi_ = nitems - 1;
-    const int gw = xcd_remap(blockIdx.x, gridDim.x, xcd);
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].wg_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int gw = blockIdx.x;
+    const int lo = find_item(items, nitems, &PairGramItem::wg_begin, gw);
     const PairGramItem it = items[lo];
     const PairGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2;
@@ -918,14 +701,7 @@ void launch_mfma_pair_gram(hipStream_t s, const PairGramItem* d_items, int nitem
     if (total_wgs <= 0) return;
     const size_t lds = (size_t)16 * (32 * 33 + 1) * 2 * sizeof(float);
     set_max_dynamic_lds((const void*)mfma_pair_gram_kernel, lds);
-    static int xcd = -1;
-    if (xcd < 0) {
-        xcd = 0;
-#ifdef TNQS_EXPERIMENTS
-        if (const char* e = std::getenv("TNQS_XCD_REMAP")) xcd = std::atoi(e);
-#endif
-    }
-    hipLaunchKernelGGL(mfma_pair_gram_kernel, dim3(total_wgs), dim3(512), lds, s, d_items, nitems, xcd); TNQS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mfma_pair_gram_kernel, dim3(total_wgs), dim3(512), lds, s, d_items, nitems); TNQS_CHECK_LAUNCH();
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -946,9 +722,7 @@ void launch_mfma_pair_gram(hipStream_t s, const PairGramItem* d_items, int nitem
 // phase, one every six MFMAs (a burst of eight 32-lines-per-instruction loads at the phase start stalled the issue: 129 -> 143 TFLOP/s).
 // Measured on 100 device-resident sites (profiles/plane_bench.py): 147 TFLOP/s algorithmic (8 flop per complex multiply-add), against
 // 129 for the same kernel with LDS-resident matrices and compiler-scheduled reads and 114 for the round-2 half-slice kernel it replaces.
-// M3 = false (TNQS_NO_3M=1): the same schedule with the four-multiplication product.
 // ------------------------------------------------------------------------------------------------------------
-template <bool M3>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void mfma_pair_gram2_kernel(const PairGram2Item* __restrict__ items, int nitems) {
     constexpr int PS = 32 * 33 + 8;            // plane stride in complex elements
     constexpr int BUF = 8 * PS;                // one phase: X planes of companions 0..3, then their Y planes
@@ -957,9 +731,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     extern __shared__ __attribute__((aligned(16))) char smem[];
     v2f* L = reinterpret_cast<v2f*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    int lo = 0, hi_ = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].wg_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int lo = find_item(items, nitems, &PairGram2Item::wg_begin, gw);
     const PairGram2Item it = items[lo];
     const PairGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2;
@@ -976,7 +749,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int q = 0; q < 16; q += 2) { const v4f v = ldg4(M + q); mr[q] = v[0]; mi[q] = v[1]; mr[q + 1] = v[2]; mi[q + 1] = v[3]; }
 #pragma unroll
-        for (int q = 0; q < 16; ++q) m0[q] = M3 ? mr[q] + mi[q] : -mi[q];
+        for (int q = 0; q < 16; ++q) m0[q] = mr[q] + mi[q];
     }
     // mover: thread -> (companion pair f2 = 0..1 of the quarter, first segment sg0 = 0..255); segment j: ix = sg0 & 31, iy = (sg0 >> 5) + 8 j
     const int f2 = tid & 1, sg0 = tid >> 1;
@@ -994,7 +767,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             p0[4 * PS] = c; p0[5 * PS] = d;
         }
     };
-    CAcc32<M3> O; O.zero();
+    CAcc32<true> O; O.zero();
     if (s_begin < s_end) {
         const long long b = pair_slice_base(g, s_begin) + toff;
 #pragma unroll
@@ -1017,7 +790,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < 4; ++i) xc[i] = xat(i + 16 * h);
         // ---- step 1: C[j'][kept] = sum_k M[k][j'] X[k][kept] ---------------------------------------------------------------
-        CAcc32<M3> C;
+        CAcc32<true> C;
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4) {
 #pragma unroll
@@ -1096,8 +869,8 @@ void launch_mfma_pair_gram2(hipStream_t s, const PairGram2Item* d_items, int nit
     if (total_wgs <= 0) return;
     if (mfma_use_x3()) { launch_x3_pair_gram2(s, d_items, nitems, total_wgs); return; }
     const size_t lds = (size_t)16 * (32 * 33 + 8) * 2 * sizeof(float);
-    set_max_dynamic_lds((const void*)mfma_pair_gram2_kernel<true>, lds);
-    hipLaunchKernelGGL(mfma_pair_gram2_kernel<true>, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
+    set_max_dynamic_lds((const void*)mfma_pair_gram2_kernel, lds);
+    hipLaunchKernelGGL(mfma_pair_gram2_kernel, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
     TNQS_CHECK_LAUNCH();
 }
 
@@ -1164,16 +937,15 @@ void launch_recover_v_mfma(hipStream_t s, const RecoverItem* d_items, int nitems
 // tiles and backwards on odd tiles, so every wave (= SIMD) does 5 blocks per two tiles instead of 8; the two tile parities
 // accumulate into separate partials (2 per chunk) because a block changes wave with the parity.
 // ------------------------------------------------------------------------------------------------------------
-template <bool M3, bool SHARED>         // SHARED: every item of the launch has KK = 64 (four panels): blocks dealt in panel-sharing sets
-__global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem* __restrict__ items, int nitems, int dbg_skip) {
+template <bool SHARED>         // SHARED: every item of the launch has KK = 64 (four panels): blocks dealt in panel-sharing sets
+__global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem* __restrict__ items, int nitems) {
     constexpr int TR = 64, TRP = TR + 4, NU = 8;
     // two tile buffers (re, im planes each): the next tile is committed while other waves still multiply the current one
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* const Xbuf = reinterpret_cast<float*>(smem);          // [buf][re|im][64 * TRP]
     const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
@@ -1203,7 +975,7 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem*
         bOn[0] = bOn[1] = true;
         bI[0] = (w & 1) ? 2 : 1; bJ[0] = (w & 1) ? 2 : 1; bI[1] = (w & 1) ? 3 : 1; bJ[1] = (w & 1) ? 3 : 2;
     }
-    // M3: Gauss' three-multiplication product in f64 (mfma_common.hpp, CAcc32::mac_conj): per block  sum (ar+ai) br,  sum ai (br-bi),  sum ar (bi+br)
+    // Gauss' three-multiplication product in f64 (mfma_common.hpp, CAcc32::mac_conj): per block  sum (ar+ai) br,  sum ai (br-bi),  sum ar (bi+br)
     v4d CAr[3], CAi[3], CBr[2], CBi[2], CAc[3], CBc[2];
 #pragma unroll
     for (int j = 0; j < 3; ++j)
@@ -1296,39 +1068,32 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem*
                     for (int c = 0; c < 4; ++c) {
                         const double ar = (double)t0[c], ai = (double)t1[c], br = (double)u0[c], bi = (double)u1[c];
                         // out[i][j] += x[i] * conj(x[j])
-                        if (M3) {
-                            cr = __builtin_amdgcn_mfma_f64_16x16x4f64(ar + ai, br, cr, 0, 0, 0);
-                            ci = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br - bi, ci, 0, 0, 0);
-                            cc = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi + br, cc, 0, 0, 0);
-                        } else {
-                            cr = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, cr, 0, 0, 0);
-                            ci = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, ci, 0, 0, 0);
-                            cr = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bi, cr, 0, 0, 0);
-                            ci = __builtin_amdgcn_mfma_f64_16x16x4f64(-ar, bi, ci, 0, 0, 0);
-                        }
+                        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(ar + ai, br, cr, 0, 0, 0);
+                        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br - bi, ci, 0, 0, 0);
+                        cc = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi + br, cc, 0, 0, 0);
                     }
                 }
             }
         };
-        if (dbg_skip != 1 && shared_sets) {
+        if (shared_sets) {
             if (((t - t_begin) & 1) == parA) {                    // wave-uniform
                 const int q3[3] = {0, 1, 2};
-                if (w & 1) gram_f64_shared<3, false, -1, M3>(Xr, Xi, TRP, l15, kq, 3, q3, CAr, CAi, CAc);
-                else       gram_f64_shared<3, true, 0, M3>(Xr, Xi, TRP, l15, kq, 0, q3, CAr, CAi, CAc);
+                if (w & 1) gram_f64_shared<3, false, -1>(Xr, Xi, TRP, l15, kq, 3, q3, CAr, CAi, CAc);
+                else       gram_f64_shared<3, true, 0>(Xr, Xi, TRP, l15, kq, 0, q3, CAr, CAi, CAc);
             } else if (w & 1) {
                 const int q2[1] = {2}, q3b[1] = {3};
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {                      // two diagonal blocks, each on its own panel (register copies, no address taken)
                     v4d r1[1] = {CBr[b]}, i1[1] = {CBi[b]}, c1[1] = {CBc[b]};
-                    if (b == 0) gram_f64_shared<1, true, 0, M3>(Xr, Xi, TRP, l15, kq, 2, q2, r1, i1, c1);
-                    else        gram_f64_shared<1, true, 0, M3>(Xr, Xi, TRP, l15, kq, 3, q3b, r1, i1, c1);
+                    if (b == 0) gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 2, q2, r1, i1, c1);
+                    else        gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 3, q3b, r1, i1, c1);
                     CBr[b] = r1[0]; CBi[b] = i1[0]; CBc[b] = c1[0];
                 }
             } else {
                 const int q12[2] = {1, 2};
-                gram_f64_shared<2, true, 0, M3>(Xr, Xi, TRP, l15, kq, 1, q12, CBr, CBi, CBc);
+                gram_f64_shared<2, true, 0>(Xr, Xi, TRP, l15, kq, 1, q12, CBr, CBi, CBc);
             }
-        } else if (dbg_skip != 1) {
+        } else {
             if (((t - t_begin) & 1) == parA) {                    // wave-uniform
 #pragma unroll
                 for (int q = 0; q < 3; ++q) if (aOn[q]) block_pass(aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
@@ -1344,7 +1109,7 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem*
         for (int r = 0; r < 4; ++r) {
             int i = 16 * I + kq + 4 * r, j = 16 * J + l15;
             if (i < KK && j < KK) {
-                cx<double> v; v.re = M3 ? cr[r] - ci[r] : cr[r]; v.im = M3 ? cr[r] - cc[r] : ci[r]; part[i + (size_t)KK * j] = v;
+                cx<double> v; v.re = cr[r] - ci[r]; v.im = cr[r] - cc[r]; part[i + (size_t)KK * j] = v;
                 if (I != J) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }     // G[j][i] = conj(G[i][j])
             }
         }
@@ -1361,15 +1126,8 @@ bool launch_mfma_gram64_f64(hipStream_t s, const GramItem* d_items, int nitems, 
     if (KKmax > 64) return false;
     if (total_chunks <= 0) return true;
     const size_t lds = (size_t)4 * 64 * 68 * sizeof(float);
-    static int skip = -1;
-    if (skip < 0) {
-        skip = 0;
-#ifdef TNQS_EXPERIMENTS
-        if (const char* e = std::getenv("TNQS_DBG_GRAM_SKIP")) skip = std::atoi(e);
-#endif
-    }
-#define TNQS_G64(M3, SH) { set_max_dynamic_lds((const void*)mfma_gram64_f64_kernel<M3, SH>, lds); hipLaunchKernelGGL((mfma_gram64_f64_kernel<M3, SH>), dim3(total_chunks), dim3(256), lds, s, d_items, nitems, skip); }
-    if (all_kk64) TNQS_G64(true, true) else TNQS_G64(true, false)
+#define TNQS_G64(SH) { set_max_dynamic_lds((const void*)mfma_gram64_f64_kernel<SH>, lds); hipLaunchKernelGGL(mfma_gram64_f64_kernel<SH>, dim3(total_chunks), dim3(256), lds, s, d_items, nitems); }
+    if (all_kk64) TNQS_G64(true) else TNQS_G64(false)
 #undef TNQS_G64
     TNQS_CHECK_LAUNCH();
     return true;

@@ -17,7 +17,6 @@
 // k only has to be consistent between A and B: k-step t of group g is mapped to index 4 g + t, so a lane reads FOUR CONSECUTIVE complex
 // numbers of its operand row from LDS (2 x ds_read_b128).  Chaining as in the chi = 32 kernels: accumulator register r of a product
 // holds row 4 g + r, which is exactly the k index instruction r of the next product consumes -- the intermediate never leaves registers.
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -44,14 +43,13 @@ constexpr int P16 = 18, PS16 = 16 * P16 + 4;
 // Wave w of a workgroup takes half (w & 1) of slices s0 + (w >> 1), s0 + (w >> 1) + 4, ...; the next unit's 16 KiB are prefetched into
 // registers before the matrix work of the current one.
 // ------------------------------------------------------------------------------------------------------------
-template <bool M3>          // M3: Gauss' three-multiplication complex product (mfma_common.hpp), 24 instead of 32 matrix instructions per plane
+// Gauss' three-multiplication complex product (mfma_common.hpp): 24 instead of 32 matrix instructions per plane
 __global__ __launch_bounds__(512) void mfma_pair16_kernel(const Pair16Item* __restrict__ items, int nitems) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c16 = lane & 15, g4 = lane >> 4;
     v2f* const L = reinterpret_cast<v2f*>(smem) + w * (8 * PS16);
-    int lo = 0, hi_ = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].wg_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int lo = find_item(items, nitems, &Pair16Item::wg_begin, gw);
     const Pair16Item it = items[lo];
     const PlaneGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2 * g.n3;
@@ -61,12 +59,12 @@ __global__ __launch_bounds__(512) void mfma_pair16_kernel(const Pair16Item* __re
     const cf* __restrict__ Mx = reinterpret_cast<const cf*>(it.Mx);
     const cf* __restrict__ My = reinterpret_cast<const cf*>(it.My);
     // B operands: Mx[k = 4 g + t][j = c] (step 1), My[k = 4 g + r][j = c] (step 2); element (i, j) at i + 16 j
-    // M3: (mxi, myi) hold bi - br and (mxs, mys) br + bi
+    // (mxi, myi) hold bi - br and (mxs, mys) br + bi
     float mxr[4], mxi[4], myr[4], myi[4], mxs[4], mys[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        cf a = Mx[(4 * g4 + t) + 16 * c16]; mxr[t] = a.re; mxi[t] = M3 ? a.im - a.re : a.im; mxs[t] = a.re + a.im;
-        cf b = My[(4 * g4 + t) + 16 * c16]; myr[t] = b.re; myi[t] = M3 ? b.im - b.re : b.im; mys[t] = b.re + b.im;
+        cf a = Mx[(4 * g4 + t) + 16 * c16]; mxr[t] = a.re; mxi[t] = a.im - a.re; mxs[t] = a.re + a.im;
+        cf b = My[(4 * g4 + t) + 16 * c16]; myr[t] = b.re; myi[t] = b.im - b.re; mys[t] = b.re + b.im;
     }
     // mover: lane -> (companion pair f = lane & 3: 16 bytes, ix = lane >> 2); load j covers iy = j
     const int f = lane & 3, ix0 = lane >> 2, half = w & 1;
@@ -99,39 +97,22 @@ __global__ __launch_bounds__(512) void mfma_pair16_kernel(const Pair16Item* __re
             const float ar[4] = {a01[0], a01[2], a23[0], a23[2]}, ai[4] = {a01[1], a01[3], a23[1], a23[3]};
             v4f Yr = {0.f, 0.f, 0.f, 0.f}, Yi = {0.f, 0.f, 0.f, 0.f};
             v4f Sr = {0.f, 0.f, 0.f, 0.f}, Si = {0.f, 0.f, 0.f, 0.f};
-            if (M3) {
-                v4f k1 = Yr, k2 = Yr, k3 = Yr;
+            v4f k1 = Yr, k2 = Yr, k3 = Yr;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    k1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t] + ai[t], mxr[t], k1, 0, 0, 0);
-                    k2 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxi[t], k2, 0, 0, 0);
-                    k3 = __builtin_amdgcn_mfma_f32_16x16x4f32(ai[t], mxs[t], k3, 0, 0, 0);
-                }
-                Yr = k1 - k3; Yi = k1 + k2;
-                v4f q1 = Sr, q2 = Sr, q3 = Sr;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {                                                 // Y reg r: row iy = 4 g + r, col jx = c16
-                    q1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r] + Yi[r], myr[r], q1, 0, 0, 0);
-                    q2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myi[r], q2, 0, 0, 0);
-                    q3 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yi[r], mys[r], q3, 0, 0, 0);
-                }
-                Sr = q1 - q3; Si = q1 + q2;
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    Yr = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxr[t], Yr, 0, 0, 0);
-                    Yi = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxi[t], Yi, 0, 0, 0);
-                    Yr = __builtin_amdgcn_mfma_f32_16x16x4f32(-ai[t], mxi[t], Yr, 0, 0, 0);
-                    Yi = __builtin_amdgcn_mfma_f32_16x16x4f32(ai[t], mxr[t], Yi, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {                                                 // Y reg r: row iy = 4 g + r, col jx = c16
-                    Sr = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myr[r], Sr, 0, 0, 0);
-                    Si = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myi[r], Si, 0, 0, 0);
-                    Sr = __builtin_amdgcn_mfma_f32_16x16x4f32(-Yi[r], myi[r], Sr, 0, 0, 0);
-                    Si = __builtin_amdgcn_mfma_f32_16x16x4f32(Yi[r], myr[r], Si, 0, 0, 0);
-                }
+            for (int t = 0; t < 4; ++t) {
+                k1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t] + ai[t], mxr[t], k1, 0, 0, 0);
+                k2 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxi[t], k2, 0, 0, 0);
+                k3 = __builtin_amdgcn_mfma_f32_16x16x4f32(ai[t], mxs[t], k3, 0, 0, 0);
             }
+            Yr = k1 - k3; Yi = k1 + k2;
+            v4f q1 = Sr, q2 = Sr, q3 = Sr;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {                                                 // Y reg r: row iy = 4 g + r, col jx = c16
+                q1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r] + Yi[r], myr[r], q1, 0, 0, 0);
+                q2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myi[r], q2, 0, 0, 0);
+                q3 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yi[r], mys[r], q3, 0, 0, 0);
+            }
+            Sr = q1 - q3; Si = q1 + q2;
             // S'[jx = 4 g + r][jy = c16] -> LDS [jy][jx]: four consecutive complex numbers
             v4f o01 = {Sr[0], Si[0], Sr[1], Si[1]}, o23 = {Sr[2], Si[2], Sr[3], Si[3]};
             *reinterpret_cast<v4f*>(P + c16 * P16 + 4 * g4) = o01;
@@ -158,14 +139,12 @@ __global__ __launch_bounds__(512) void mfma_pair16_kernel(const Pair16Item* __re
 // (36.5 KiB; four waves per workgroup, one per SIMD), the same matrix work per plane.  The kernel is far from matrix-core bound (27 ms
 // against 50 ms of memory time on the 3 x 3 x 3 torus), so one wave per SIMD is enough to cover the compute phase with the prefetch.
 // ------------------------------------------------------------------------------------------------------------
-template <bool M3>
 __global__ __launch_bounds__(256) void mfma_pair16w_kernel(const Pair16Item* __restrict__ items, int nitems) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c16 = lane & 15, g4 = lane >> 4;
     v2f* const L = reinterpret_cast<v2f*>(smem) + w * (16 * PS16);
-    int lo = 0, hi_ = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].wg_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int lo = find_item(items, nitems, &Pair16Item::wg_begin, gw);
     const Pair16Item it = items[lo];
     const PlaneGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2 * g.n3;
@@ -177,8 +156,8 @@ __global__ __launch_bounds__(256) void mfma_pair16w_kernel(const Pair16Item* __r
     float mxr[4], mxi[4], myr[4], myi[4], mxs[4], mys[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        cf a = Mx[(4 * g4 + t) + 16 * c16]; mxr[t] = a.re; mxi[t] = M3 ? a.im - a.re : a.im; mxs[t] = a.re + a.im;
-        cf b = My[(4 * g4 + t) + 16 * c16]; myr[t] = b.re; myi[t] = M3 ? b.im - b.re : b.im; mys[t] = b.re + b.im;
+        cf a = Mx[(4 * g4 + t) + 16 * c16]; mxr[t] = a.re; mxi[t] = a.im - a.re; mxs[t] = a.re + a.im;
+        cf b = My[(4 * g4 + t) + 16 * c16]; myr[t] = b.re; myi[t] = b.im - b.re; mys[t] = b.re + b.im;
     }
     // mover: lane -> (companion pair f = lane & 7: 16 bytes, 8 lanes = one line; ix = (lane >> 3) + 8 h); load (h, j) covers iy = j
     const int f = lane & 7, ix0 = lane >> 3;
@@ -215,39 +194,22 @@ __global__ __launch_bounds__(256) void mfma_pair16w_kernel(const Pair16Item* __r
             const v4f a23 = *reinterpret_cast<const v4f*>(P + c16 * P16 + 4 * g4 + 2);
             const float ar[4] = {a01[0], a01[2], a23[0], a23[2]}, ai[4] = {a01[1], a01[3], a23[1], a23[3]};
             v4f Yr = {0.f, 0.f, 0.f, 0.f}, Yi = Yr, Sr = Yr, Si = Yr;
-            if (M3) {
-                v4f k1 = Yr, k2 = Yr, k3 = Yr;
+            v4f k1 = Yr, k2 = Yr, k3 = Yr;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    k1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t] + ai[t], mxr[t], k1, 0, 0, 0);
-                    k2 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxi[t], k2, 0, 0, 0);
-                    k3 = __builtin_amdgcn_mfma_f32_16x16x4f32(ai[t], mxs[t], k3, 0, 0, 0);
-                }
-                Yr = k1 - k3; Yi = k1 + k2;
-                v4f q1 = Sr, q2 = Sr, q3 = Sr;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    q1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r] + Yi[r], myr[r], q1, 0, 0, 0);
-                    q2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myi[r], q2, 0, 0, 0);
-                    q3 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yi[r], mys[r], q3, 0, 0, 0);
-                }
-                Sr = q1 - q3; Si = q1 + q2;
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    Yr = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxr[t], Yr, 0, 0, 0);
-                    Yi = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxi[t], Yi, 0, 0, 0);
-                    Yr = __builtin_amdgcn_mfma_f32_16x16x4f32(-ai[t], mxi[t], Yr, 0, 0, 0);
-                    Yi = __builtin_amdgcn_mfma_f32_16x16x4f32(ai[t], mxr[t], Yi, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    Sr = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myr[r], Sr, 0, 0, 0);
-                    Si = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myi[r], Si, 0, 0, 0);
-                    Sr = __builtin_amdgcn_mfma_f32_16x16x4f32(-Yi[r], myi[r], Sr, 0, 0, 0);
-                    Si = __builtin_amdgcn_mfma_f32_16x16x4f32(Yi[r], myr[r], Si, 0, 0, 0);
-                }
+            for (int t = 0; t < 4; ++t) {
+                k1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t] + ai[t], mxr[t], k1, 0, 0, 0);
+                k2 = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[t], mxi[t], k2, 0, 0, 0);
+                k3 = __builtin_amdgcn_mfma_f32_16x16x4f32(ai[t], mxs[t], k3, 0, 0, 0);
             }
+            Yr = k1 - k3; Yi = k1 + k2;
+            v4f q1 = Sr, q2 = Sr, q3 = Sr;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                q1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r] + Yi[r], myr[r], q1, 0, 0, 0);
+                q2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yr[r], myi[r], q2, 0, 0, 0);
+                q3 = __builtin_amdgcn_mfma_f32_16x16x4f32(Yi[r], mys[r], q3, 0, 0, 0);
+            }
+            Sr = q1 - q3; Si = q1 + q2;
             v4f o01 = {Sr[0], Si[0], Sr[1], Si[1]}, o23 = {Sr[2], Si[2], Sr[3], Si[3]};      // S'[jx = 4 g + r][jy = c16] -> LDS [jy][jx]
             *reinterpret_cast<v4f*>(P + c16 * P16 + 4 * g4) = o01;
             *reinterpret_cast<v4f*>(P + c16 * P16 + 4 * g4 + 2) = o23;
@@ -267,14 +229,8 @@ __global__ __launch_bounds__(256) void mfma_pair16w_kernel(const Pair16Item* __r
         __builtin_amdgcn_wave_barrier();
     }
 }
-// whole_lines: every item has its 16 companions in one 128-byte line (PlaneGeom::cstr == 2) and TNQS_PAIR16_HALF is not set: see pair16_whole_lines()
-bool pair16_whole_lines(const PlaneGeom& g) {
-#ifdef TNQS_EXPERIMENTS
-    static const bool off = [] { const char* e = std::getenv("TNQS_PAIR16_HALF"); return e && e[0] == '1'; }();
-    if (off) return false;
-#endif
-    return g.cstr == 2;
-}
+// whole_lines: the item has its 16 companions in one 128-byte line
+bool pair16_whole_lines(const PlaneGeom& g) { return g.cstr == 2; }
 // spw: 4 (4 slices at a time, as 8 waves x half slices or 4 waves x whole slices), doubled up to 64 while the batch keeps >= 2048 workgroups of
 // 2 spw slices (at least ~8 per CU); ceil(slices / spw) workgroups per item
 void plan_pair16(Pair16Item* it, int n, int wgs[2], int spw) {
@@ -285,13 +241,13 @@ void plan_pair16(Pair16Item* it, int n, int wgs[2], int spw) {
 void launch_mfma_pair16(hipStream_t s, const Pair16Item* d_items, int nitems, int total_wgs, bool whole_lines) {
     if (total_wgs > 0 && whole_lines) {
         const size_t lds = (size_t)4 * 16 * PS16 * sizeof(v2f);
-        set_max_dynamic_lds((const void*)mfma_pair16w_kernel<true>, lds); hipLaunchKernelGGL(mfma_pair16w_kernel<true>, dim3(total_wgs), dim3(256), lds, s, d_items, nitems);
+        set_max_dynamic_lds((const void*)mfma_pair16w_kernel, lds); hipLaunchKernelGGL(mfma_pair16w_kernel, dim3(total_wgs), dim3(256), lds, s, d_items, nitems);
         TNQS_CHECK_LAUNCH();
         return;
     }
     if (total_wgs <= 0) return;
     const size_t lds = (size_t)8 * 8 * PS16 * sizeof(v2f);
-    set_max_dynamic_lds((const void*)mfma_pair16_kernel<true>, lds); hipLaunchKernelGGL(mfma_pair16_kernel<true>, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
+    set_max_dynamic_lds((const void*)mfma_pair16_kernel, lds); hipLaunchKernelGGL(mfma_pair16_kernel, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
     TNQS_CHECK_LAUNCH();
 }
 
@@ -306,15 +262,14 @@ void launch_mfma_pair16(hipStream_t s, const Pair16Item* d_items, int nitems, in
 // half slice -> matrix work.  The matrix phase of one wave runs under the memory phases of the other wave of its SIMD: 1.61 - 1.87 ms per
 // 12 sites against 1.97 - 2.15 with four waves of 8 resident companions (one per SIMD), which was matrix-core bound in practice: 1.78 ms
 // even without its global loads.
-template <bool M3>          // M3: three-multiplication complex products, 48 instead of 64 matrix instructions per companion (both messages)
+// three-multiplication complex products: 48 instead of 64 matrix instructions per companion (both messages)
 __global__ __launch_bounds__(512) void mfma_pair_gram2x16_kernel(const PairGram2x16Item* __restrict__ items, int nitems) {
     constexpr int NW = 8, NC = 4;                                        // waves per workgroup, companions resident per wave
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c16 = lane & 15, g4 = lane >> 4;
     v2f* const L = reinterpret_cast<v2f*>(smem) + w * (2 * NC * PS16);   // planes 0..NC-1: X of the resident companions, planes NC..2NC-1: Y
-    int lo = 0, hi_ = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].wg_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int lo = find_item(items, nitems, &PairGram2x16Item::wg_begin, gw);
     const PairGram2x16Item it = items[lo];
     const PlaneGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2 * g.n3;
@@ -323,7 +278,7 @@ __global__ __launch_bounds__(512) void mfma_pair_gram2x16_kernel(const PairGram2
     const cf* __restrict__ Xg = reinterpret_cast<const cf*>(it.X);
     const cf* __restrict__ Yg = reinterpret_cast<const cf*>(it.Y);
     // A operands of the first steps: Mx^T / My^T, lane (i = c16, g): k-step t -> M[4 g + t][c16]
-    float mxr[4], mxi[4], myr[4], myi[4], mxs[4], mys[4];      // M3: (mxs, mys) = re + im, the A-side sum of Gauss' product
+    float mxr[4], mxi[4], myr[4], myi[4], mxs[4], mys[4];      // (mxs, mys) = re + im, the A-side sum of Gauss' product
     {
         const cf* __restrict__ Mx = reinterpret_cast<const cf*>(it.Mx); const cf* __restrict__ My = reinterpret_cast<const cf*>(it.My);
 #pragma unroll
@@ -333,7 +288,7 @@ __global__ __launch_bounds__(512) void mfma_pair_gram2x16_kernel(const PairGram2
         }
     }
     const bool both = it.My != nullptr;                 // My == null: only the message through ly is wanted (a site that sends one message in this level)
-    // M3: (O?r, O?i, O?c) accumulate sum (ar + ai) br, sum ai (br - bi), sum ar (bi + br) of out += C conj(Y): re = r - i, im = r - c
+    // (O?r, O?i, O?c) accumulate sum (ar + ai) br, sum ai (br - bi), sum ar (bi + br) of out += C conj(Y): re = r - i, im = r - c
     v4f O1r = {0.f, 0.f, 0.f, 0.f}, O1i = O1r, O2r = O1r, O2i = O1r, O1c = O1r, O2c = O1r;
     const int f = lane & 3, ix0 = lane >> 2, half = w & 1;
     const long long toff = (long long)(4 * half + f) * g.cstr + g.sx * ix0;
@@ -383,58 +338,29 @@ __global__ __launch_bounds__(512) void mfma_pair_gram2x16_kernel(const PairGram2
             const v4f z4 = {0.f, 0.f, 0.f, 0.f};
             // ---- first products: C1[jx = 4 g + r][b = c16] = Mx^T X (message through ly), C2[jy = 4 g + r][d = c16] = My^T X^T (through lx)
             v4f C1r = z4, C1i = z4, C2r = z4, C2i = z4;
-            if (M3) {
-                v4f k1 = z4, k2 = z4, k3 = z4, q1 = z4, q2 = z4, q3 = z4;
+            v4f k1 = z4, k2 = z4, k3 = z4, q1 = z4, q2 = z4, q3 = z4;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    k1 = __builtin_amdgcn_mfma_f32_16x16x4f32(mxs[t], xr[t], k1, 0, 0, 0);
-                    k2 = __builtin_amdgcn_mfma_f32_16x16x4f32(mxr[t], xi[t] - xr[t], k2, 0, 0, 0);
-                    k3 = __builtin_amdgcn_mfma_f32_16x16x4f32(mxi[t], xr[t] + xi[t], k3, 0, 0, 0);
-                    if constexpr (BOTH) {
-                        q1 = __builtin_amdgcn_mfma_f32_16x16x4f32(mys[t], o.xt[t][0], q1, 0, 0, 0);
-                        q2 = __builtin_amdgcn_mfma_f32_16x16x4f32(myr[t], o.xt[t][1] - o.xt[t][0], q2, 0, 0, 0);
-                        q3 = __builtin_amdgcn_mfma_f32_16x16x4f32(myi[t], o.xt[t][0] + o.xt[t][1], q3, 0, 0, 0);
-                    }
-                }
-                C1r = k1 - k3; C1i = k1 + k2; C2r = q1 - q3; C2i = q1 + q2;
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    C1r = __builtin_amdgcn_mfma_f32_16x16x4f32(mxr[t], xr[t], C1r, 0, 0, 0);
-                    C1i = __builtin_amdgcn_mfma_f32_16x16x4f32(mxr[t], xi[t], C1i, 0, 0, 0);
-                    C1r = __builtin_amdgcn_mfma_f32_16x16x4f32(-mxi[t], xi[t], C1r, 0, 0, 0);
-                    C1i = __builtin_amdgcn_mfma_f32_16x16x4f32(mxi[t], xr[t], C1i, 0, 0, 0);
-                    if constexpr (BOTH) {
-                        C2r = __builtin_amdgcn_mfma_f32_16x16x4f32(myr[t], o.xt[t][0], C2r, 0, 0, 0);
-                        C2i = __builtin_amdgcn_mfma_f32_16x16x4f32(myr[t], o.xt[t][1], C2i, 0, 0, 0);
-                        C2r = __builtin_amdgcn_mfma_f32_16x16x4f32(-myi[t], o.xt[t][1], C2r, 0, 0, 0);
-                        C2i = __builtin_amdgcn_mfma_f32_16x16x4f32(myi[t], o.xt[t][0], C2i, 0, 0, 0);
-                    }
+            for (int t = 0; t < 4; ++t) {
+                k1 = __builtin_amdgcn_mfma_f32_16x16x4f32(mxs[t], xr[t], k1, 0, 0, 0);
+                k2 = __builtin_amdgcn_mfma_f32_16x16x4f32(mxr[t], xi[t] - xr[t], k2, 0, 0, 0);
+                k3 = __builtin_amdgcn_mfma_f32_16x16x4f32(mxi[t], xr[t] + xi[t], k3, 0, 0, 0);
+                if constexpr (BOTH) {
+                    q1 = __builtin_amdgcn_mfma_f32_16x16x4f32(mys[t], o.xt[t][0], q1, 0, 0, 0);
+                    q2 = __builtin_amdgcn_mfma_f32_16x16x4f32(myr[t], o.xt[t][1] - o.xt[t][0], q2, 0, 0, 0);
+                    q3 = __builtin_amdgcn_mfma_f32_16x16x4f32(myi[t], o.xt[t][0] + o.xt[t][1], q3, 0, 0, 0);
                 }
             }
+            C1r = k1 - k3; C1i = k1 + k2; C2r = q1 - q3; C2i = q1 + q2;
             // ---- second products: out1[b][b'] += C1[jx][b] conj Y[jx][b'],  out2[d][d'] += C2[jy][d] conj Y^T[jy][d'] ------------------
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (M3) {
-                    O1r = __builtin_amdgcn_mfma_f32_16x16x4f32(C1r[r] + C1i[r], yr[r], O1r, 0, 0, 0);
-                    O1c = __builtin_amdgcn_mfma_f32_16x16x4f32(C1r[r], yi[r] + yr[r], O1c, 0, 0, 0);
-                    O1i = __builtin_amdgcn_mfma_f32_16x16x4f32(C1i[r], yr[r] - yi[r], O1i, 0, 0, 0);
-                    if constexpr (BOTH) {
-                        O2r = __builtin_amdgcn_mfma_f32_16x16x4f32(C2r[r] + C2i[r], o.yt[r][0], O2r, 0, 0, 0);
-                        O2c = __builtin_amdgcn_mfma_f32_16x16x4f32(C2r[r], o.yt[r][1] + o.yt[r][0], O2c, 0, 0, 0);
-                        O2i = __builtin_amdgcn_mfma_f32_16x16x4f32(C2i[r], o.yt[r][0] - o.yt[r][1], O2i, 0, 0, 0);
-                    }
-                } else {
-                    O1r = __builtin_amdgcn_mfma_f32_16x16x4f32(C1r[r], yr[r], O1r, 0, 0, 0);
-                    O1i = __builtin_amdgcn_mfma_f32_16x16x4f32(C1i[r], yr[r], O1i, 0, 0, 0);
-                    O1r = __builtin_amdgcn_mfma_f32_16x16x4f32(C1i[r], yi[r], O1r, 0, 0, 0);
-                    O1i = __builtin_amdgcn_mfma_f32_16x16x4f32(-C1r[r], yi[r], O1i, 0, 0, 0);
-                    if constexpr (BOTH) {
-                        O2r = __builtin_amdgcn_mfma_f32_16x16x4f32(C2r[r], o.yt[r][0], O2r, 0, 0, 0);
-                        O2i = __builtin_amdgcn_mfma_f32_16x16x4f32(C2i[r], o.yt[r][0], O2i, 0, 0, 0);
-                        O2r = __builtin_amdgcn_mfma_f32_16x16x4f32(C2i[r], o.yt[r][1], O2r, 0, 0, 0);
-                        O2i = __builtin_amdgcn_mfma_f32_16x16x4f32(-C2r[r], o.yt[r][1], O2i, 0, 0, 0);
-                    }
+                O1r = __builtin_amdgcn_mfma_f32_16x16x4f32(C1r[r] + C1i[r], yr[r], O1r, 0, 0, 0);
+                O1c = __builtin_amdgcn_mfma_f32_16x16x4f32(C1r[r], yi[r] + yr[r], O1c, 0, 0, 0);
+                O1i = __builtin_amdgcn_mfma_f32_16x16x4f32(C1i[r], yr[r] - yi[r], O1i, 0, 0, 0);
+                if constexpr (BOTH) {
+                    O2r = __builtin_amdgcn_mfma_f32_16x16x4f32(C2r[r] + C2i[r], o.yt[r][0], O2r, 0, 0, 0);
+                    O2c = __builtin_amdgcn_mfma_f32_16x16x4f32(C2r[r], o.yt[r][1] + o.yt[r][0], O2c, 0, 0, 0);
+                    O2i = __builtin_amdgcn_mfma_f32_16x16x4f32(C2i[r], o.yt[r][0] - o.yt[r][1], O2i, 0, 0, 0);
                 }
             }
         };
@@ -462,7 +388,7 @@ __global__ __launch_bounds__(512) void mfma_pair_gram2x16_kernel(const PairGram2
     // one partial per workgroup and message: the four waves' accumulators are summed through LDS, in wave order
     cf* __restrict__ p1 = reinterpret_cast<cf*>(it.partial_y) + (size_t)lw * 256;
     cf* __restrict__ p2 = reinterpret_cast<cf*>(it.partial_x) + (size_t)lw * 256;
-    if (M3) { const v4f a1 = O1r, a2 = O2r; O1r = a1 - O1i; O1i = a1 - O1c; O2r = a2 - O2i; O2i = a2 - O2c; }
+    { const v4f a1 = O1r, a2 = O2r; O1r = a1 - O1i; O1i = a1 - O1c; O2r = a2 - O2i; O2i = a2 - O2c; }
     __syncthreads();                                     // every wave is done with its slab
     v2f* const R = reinterpret_cast<v2f*>(smem);        // [message 2][wave NW][16 x 17]
 #pragma unroll
@@ -491,7 +417,7 @@ int plan_pair_gram2x16(PairGram2x16Item* it, int n, int* nwg, int spw) {
 void launch_mfma_pair_gram2x16(hipStream_t s, const PairGram2x16Item* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
     const size_t lds = (size_t)8 * 8 * PS16 * sizeof(v2f);
-    set_max_dynamic_lds((const void*)mfma_pair_gram2x16_kernel<true>, lds); hipLaunchKernelGGL(mfma_pair_gram2x16_kernel<true>, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
+    set_max_dynamic_lds((const void*)mfma_pair_gram2x16_kernel, lds); hipLaunchKernelGGL(mfma_pair_gram2x16_kernel, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
     TNQS_CHECK_LAUNCH();
 }
 

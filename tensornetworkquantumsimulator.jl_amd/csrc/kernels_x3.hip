@@ -14,7 +14,6 @@
 // instructions per f32 value (and, subtract, and, subtract, 1.5 byte-permutes to pack pairs), on the VALU next to the matrix pipe.
 // The kernels keep the data movement of the f32 kernels they replace (kernels_mfma.hip); with the matrix time halved they are bound by HBM.
 // TNQS_NO_BF16X3=1 selects the f32 kernels.
-#include <cstdlib>
 #include <type_traits>
 #include "kernels.hpp"
 #include "mfma_common.hpp"
@@ -43,7 +42,7 @@ __device__ __forceinline__ long long x3_slice_base(const PairGeom& g, int sl) {
 // eight consecutive elements are four aligned 16-byte reads (message 0; message 1 reads the same planes transposed, 8-byte reads along the lanes).
 // ------------------------------------------------------------------------------------------------------------
 // SINGLE: one message per item (partial_y only; My, partial_x unused) -- the eight waves take the eight companions of a phase, one each
-template <int MODE, bool SINGLE = false>
+template <bool SINGLE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void x3_pair_gram2_kernel(const PairGram2Item* __restrict__ items, int nitems) {
     constexpr int P = 34;                      // row pitch in complex elements
     constexpr int PS = 32 * P + 2;             // plane stride: X planes of companions 0..7, then their Y planes
@@ -53,9 +52,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     extern __shared__ __attribute__((aligned(16))) char smem[];
     v2f* L = reinterpret_cast<v2f*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    int lo = 0, hi_ = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].wg_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int lo = find_item(items, nitems, &PairGram2Item::wg_begin, gw);
     const PairGram2Item it = items[lo];
     const PairGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2;
@@ -74,7 +72,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             float xr[8], xi[8];
 #pragma unroll
             for (int e = 0; e < 8; e += 2) { const v4f v = ldg4(M + 16 * n + e); xr[e] = v[0]; xi[e] = v[1]; xr[e + 1] = v[2]; xi[e + 1] = v[3]; }
-            Mr[n] = split8<MODE>(xr); Mi[n] = split8<MODE>(xi);
+            Mr[n] = split8(xr); Mi[n] = split8(xi);
         }
     }
     // mover: thread -> (companion pair f4 = 0..3 of the half, first segment sg0 = 0..127); segment j: ix = sg0 & 31, iy = (sg0 >> 5) + 4 j
@@ -84,7 +82,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     v2f* const lbase = L + (2 * f4) * PS + iy0 * P + ix0;                // element (ix, iy) at [iy][ix]
     v4f px[8], py[8];
     auto commit = [&]() {
-        if (MODE == 3 || MODE == 4) return;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             v2f* p0 = lbase + 4 * P * j;                                 // iy advances by 4 per j
@@ -108,11 +105,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int MSG = decltype(msg_c)::value;
     // eight plane elements (index i0 .. i0 + 3 and i1 .. i1 + 3 along the contracted direction) of the kept index ln: message 0 reads rows, message 1 columns
     auto read8 = [&](const v2f* PL, int i0, int i1, float (&re)[8], float (&im)[8]) {
-        if (MODE == 4) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { re[e] = __int_as_float(i0 + e + ln); im[e] = __int_as_float(i1 + e); }
-            return;
-        }
         if (MSG == 0) {
             const v4f* a = reinterpret_cast<const v4f*>(PL + ln * P + i0); const v4f* b = reinterpret_cast<const v4f*>(PL + ln * P + i1);
             const v4f a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
@@ -128,40 +120,36 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const long long nb = x3_slice_base(g, more ? sl + 1 : sl) + toff;          // (the last phase re-reads its own slice: no branch in the stream)
         float ar[8], ai[8], br[8], bi[8];
         read8(L + comp * PS, 8 * h, 8 * h + 4, ar, ai);
-        if (MODE == 5) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { px[j] = ldg4(Xg + nb + tstr * j); py[j] = ldg4(Yg + nb + tstr * j); }
-        }
 #pragma unroll
         for (int t = 0; t < (SINGLE ? 1 : 2); ++t) {
             const v2f* PX = L + (comp + 4 * t) * PS; const v2f* PY = PX + 8 * PS;
             // ---- step 1: C[j'][kept] = sum_k M[k][j'] X[k][kept] -------------------------------------------------------------------------
             v16f Cr, Ci;
             read8(PX, 16 + 8 * h, 16 + 8 * h + 4, br, bi);
-            if (t == 0 && (MODE < 3)) {
+            if (t == 0) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) { px[j] = ldg4(Xg + nb + tstr * j); py[j] = ldg4(Yg + nb + tstr * j); }
             }
             TNQS_PIN();
             {
-                const P3 xr = split8<MODE>(ar), xi = split8<MODE>(ai);
-                mac6x2<true, MODE>(Cr, Mr[0], xr, Ci, Mr[0], xi);
-                mac6x2<false, MODE>(Cr, Mi[0], neg(xi), Ci, Mi[0], xr);
+                const P3 xr = split8(ar), xi = split8(ai);
+                mac6x2<true>(Cr, Mr[0], xr, Ci, Mr[0], xi);
+                mac6x2<false>(Cr, Mi[0], neg(xi), Ci, Mi[0], xr);
             }
             read8(PY, 4 * h, 4 * h + 8, ar, ai);                                         // first operands of step 2
-            if (t == 0 && (MODE < 3)) {
+            if (t == 0) {
 #pragma unroll
                 for (int j = 2; j < 4; ++j) { px[j] = ldg4(Xg + nb + tstr * j); py[j] = ldg4(Yg + nb + tstr * j); }
             }
             TNQS_PIN();
             {
-                const P3 xr = split8<MODE>(br), xi = split8<MODE>(bi);
-                mac6x2<false, MODE>(Cr, Mr[1], xr, Ci, Mr[1], xi);
-                mac6x2<false, MODE>(Cr, Mi[1], neg(xi), Ci, Mi[1], xr);
+                const P3 xr = split8(br), xi = split8(bi);
+                mac6x2<false>(Cr, Mr[1], xr, Ci, Mr[1], xi);
+                mac6x2<false>(Cr, Mi[1], neg(xi), Ci, Mi[1], xr);
             }
             // ---- step 2: O[kept][kept'] += sum_j' C[j'][kept] conj Y[j'][kept'] ----------------------------------------------------------
             read8(PY, 16 + 4 * h, 16 + 4 * h + 8, br, bi);
-            if (t == 0 && (MODE < 3)) {
+            if (t == 0) {
 #pragma unroll
                 for (int j = 4; j < 6; ++j) { px[j] = ldg4(Xg + nb + tstr * j); py[j] = ldg4(Yg + nb + tstr * j); }
             }
@@ -170,11 +158,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 float cr[8], ci[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { cr[e] = Cr[e]; ci[e] = Ci[e]; }
-                const P3 pcr = split8<MODE>(cr), pci = split8<MODE>(ci), yr = split8<MODE>(ar), yi = split8<MODE>(ai);
-                mac6x2<false, MODE>(Or, pcr, yr, Oi, pci, yr);
-                mac6x2<false, MODE>(Or, pci, yi, Oi, neg(pcr), yi);
+                const P3 pcr = split8(cr), pci = split8(ci), yr = split8(ar), yi = split8(ai);
+                mac6x2<false>(Or, pcr, yr, Oi, pci, yr);
+                mac6x2<false>(Or, pci, yi, Oi, neg(pcr), yi);
             }
-            if (t == 0 && (MODE < 3)) {
+            if (t == 0) {
 #pragma unroll
                 for (int j = 6; j < 8; ++j) { px[j] = ldg4(Xg + nb + tstr * j); py[j] = ldg4(Yg + nb + tstr * j); }
             }
@@ -184,9 +172,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 float cr[8], ci[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { cr[e] = Cr[8 + e]; ci[e] = Ci[8 + e]; }
-                const P3 pcr = split8<MODE>(cr), pci = split8<MODE>(ci), yr = split8<MODE>(br), yi = split8<MODE>(bi);
-                mac6x2<false, MODE>(Or, pcr, yr, Oi, pci, yr);
-                mac6x2<false, MODE>(Or, pci, yi, Oi, neg(pcr), yi);
+                const P3 pcr = split8(cr), pci = split8(ci), yr = split8(br), yi = split8(bi);
+                mac6x2<false>(Or, pcr, yr, Oi, pci, yr);
+                mac6x2<false>(Or, pci, yi, Oi, neg(pcr), yi);
             }
         }
         TNQS_PIN();
@@ -237,23 +225,15 @@ int plan_x3_pair_gram1(PairGram2Item* it, int n, int* nwg, int spw) {
 void launch_x3_pair_gram1(hipStream_t s, const PairGram2Item* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
     const size_t lds = (size_t)16 * (32 * 34 + 2) * 2 * sizeof(float);
-    set_max_dynamic_lds((const void*)x3_pair_gram2_kernel<0, true>, lds);
-    hipLaunchKernelGGL((x3_pair_gram2_kernel<0, true>), dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
+    set_max_dynamic_lds((const void*)x3_pair_gram2_kernel<true>, lds);
+    hipLaunchKernelGGL((x3_pair_gram2_kernel<true>), dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
     TNQS_CHECK_LAUNCH();
 }
 void launch_x3_pair_gram2(hipStream_t s, const PairGram2Item* d_items, int nitems, int total_wgs) {
     if (total_wgs <= 0) return;
     const size_t lds = (size_t)16 * (32 * 34 + 2) * 2 * sizeof(float);
-#ifdef TNQS_EXPERIMENTS
-    // timing experiments (never in the shipped build): 1 no splitting, 2 no matrix instructions, 3 no global loads / commits, 4 no LDS reads either, 5 all loads at the phase start
-    static const int mode = [] { const char* e = std::getenv("TNQS_X3_MODE"); return e ? std::atoi(e) : 0; }();
-    #define TNQS_X3_LAUNCH(M) { set_max_dynamic_lds((const void*)x3_pair_gram2_kernel<M>, lds); hipLaunchKernelGGL(x3_pair_gram2_kernel<M>, dim3(total_wgs), dim3(512), lds, s, d_items, nitems); }
-    if (mode == 1) TNQS_X3_LAUNCH(1) else if (mode == 2) TNQS_X3_LAUNCH(2) else if (mode == 3) TNQS_X3_LAUNCH(3) else if (mode == 4) TNQS_X3_LAUNCH(4) else if (mode == 5) TNQS_X3_LAUNCH(5) else TNQS_X3_LAUNCH(0)
-    #undef TNQS_X3_LAUNCH
-#else
-    set_max_dynamic_lds((const void*)x3_pair_gram2_kernel<0>, lds);
-    hipLaunchKernelGGL(x3_pair_gram2_kernel<0>, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
-#endif
+    set_max_dynamic_lds((const void*)x3_pair_gram2_kernel<false>, lds);
+    hipLaunchKernelGGL(x3_pair_gram2_kernel<false>, dim3(total_wgs), dim3(512), lds, s, d_items, nitems);
     TNQS_CHECK_LAUNCH();
 }
 
@@ -271,9 +251,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     extern __shared__ __attribute__((aligned(16))) char smem[];
     v2f* L = reinterpret_cast<v2f*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    int lo = 0, hi_ = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi_) { int mid = (lo + hi_ + 1) >> 1; if (items[mid].slice_begin <= gw) lo = mid; else hi_ = mid - 1; }
+    const int lo = find_item(items, nitems, &PairItem::slice_begin, gw);
     const PairItem it = items[lo];
     const PairGeom g = it.g;
     const int nslices = g.n0 * g.n1 * g.n2;
@@ -415,9 +394,8 @@ __global__ __launch_bounds__(256, 2) void x3_rowgemm64_kernel(const FiberItem* _
     u4* const Xl = reinterpret_cast<u4*>(smem);              // [(n, nb)][re h m l, im h m l][lane]
     __shared__ double sh_red[4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    int lo = 0, hi = nitems - 1;
     const int gw = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].tile_begin <= gw) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &FiberItem::tile_begin, gw);
     const FiberItem it = items[lo];
     const int K = it.K, No = it.No, NN = it.Do * No;
     const long long PA = it.PA;
@@ -547,9 +525,8 @@ __global__ __launch_bounds__(256, 2) void x3_gram64_kernel(const GramItem* __res
     float* const Yr = Xi + 64 * TRP;
     float* const Yi = Yr + 64 * TRP;
     const int tid = threadIdx.x;
-    int lo = 0, hi = nitems - 1;
     const int gc = blockIdx.x;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (items[mid].chunk_begin <= gc) lo = mid; else hi = mid - 1; }
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
     const GramItem it = items[lo];
     const int lc = gc - it.chunk_begin;
     const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;

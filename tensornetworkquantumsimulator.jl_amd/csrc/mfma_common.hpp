@@ -33,7 +33,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //               is two VALU instructions per accumulator register, once per tile.  Error: |delta| <= c u (|a_r| + |a_i|)(|b_r| + |b_i|) per
 //               term, i.e. the same NORMWISE bound as the four-multiplication product; the componentwise bound of the imaginary part is
 //               lost (a tiny imaginary part next to a large real one carries the large one's rounding), which the BP messages and site
-//               tensors -- compared and used normwise everywhere -- do not rely on.  TNQS_NO_3M=1 selects M3 = false everywhere.
+//               tensors -- compared and used normwise everywhere -- do not rely on.
 // ------------------------------------------------------------------------------------------------------------
 template <bool M3> struct CAcc32 {
     v16f a, b, c;
@@ -120,10 +120,10 @@ template <bool M3> struct CAcc32 {
 // l15 of a 16-column panel, tile rows 16 kq .. 16 kq + 15).  A set of upper-triangle blocks that share one panel P: ROW = P supplies the rows
 // (A operand) of every block and Q[j] the columns, !ROW = P supplies the columns (B operand) and Q[j] the rows; DIAGJ >= 0: block DIAGJ is (P, P).
 // The shared panel's values are read from LDS, converted to f64 and combined ONCE per four k-steps for all N blocks (a block on its own
-// converts four values and forms three sums per k-step).  out[i][j] += x[i] conj(x[j]); M3: (cr, ci, cc) accumulate
+// converts four values and forms three sums per k-step).  out[i][j] += x[i] conj(x[j]) as three multiplications: (cr, ci, cc) accumulate
 // sum (ar+ai) br, sum ai (br-bi), sum ar (bi+br), i.e. re = cr - ci, im = cr - cc.
 // ------------------------------------------------------------------------------------------------------------
-template <int N, bool ROW, int DIAGJ, bool M3>
+template <int N, bool ROW, int DIAGJ>
 __device__ __forceinline__ void gram_f64_shared(const float* __restrict__ Xr, const float* __restrict__ Xi, int TRP, int l15, int kq, int P,
                                                 const int (&Q)[N], v4d (&cr)[N], v4d (&ci)[N], v4d (&cc)[N]) {
 #pragma unroll 1
@@ -141,22 +141,14 @@ __device__ __forceinline__ void gram_f64_shared(const float* __restrict__ Xr, co
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const double qr = dg ? pr[c] : (double)o0[c], qi = dg ? pi[c] : (double)o1[c];
-                if (M3) {
-                    if (ROW) {                                       // a = p, b = q
-                        cr[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ps[c], qr, cr[j], 0, 0, 0);
-                        ci[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(pi[c], qr - qi, ci[j], 0, 0, 0);
-                        cc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(pr[c], qi + qr, cc[j], 0, 0, 0);
-                    } else {                                         // a = q, b = p
-                        cr[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(qr + qi, pr[c], cr[j], 0, 0, 0);
-                        ci[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(qi, pd[c], ci[j], 0, 0, 0);
-                        cc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(qr, ps[c], cc[j], 0, 0, 0);
-                    }
-                } else {
-                    const double ar = ROW ? pr[c] : qr, ai = ROW ? pi[c] : qi, br = ROW ? qr : pr[c], bi = ROW ? qi : pi[c];
-                    cr[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, cr[j], 0, 0, 0);
-                    ci[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, ci[j], 0, 0, 0);
-                    cr[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bi, cr[j], 0, 0, 0);
-                    ci[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ar, bi, ci[j], 0, 0, 0);
+                if (ROW) {                                           // a = p, b = q
+                    cr[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ps[c], qr, cr[j], 0, 0, 0);
+                    ci[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(pi[c], qr - qi, ci[j], 0, 0, 0);
+                    cc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(pr[c], qi + qr, cc[j], 0, 0, 0);
+                } else {                                             // a = q, b = p
+                    cr[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(qr + qi, pr[c], cr[j], 0, 0, 0);
+                    ci[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(qi, pd[c], ci[j], 0, 0, 0);
+                    cc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(qr, ps[c], cc[j], 0, 0, 0);
                 }
             }
         }

@@ -706,6 +706,7 @@ def test_gram_mfma64(launch, same, nchunks):
 
 
 GRAM128_LAUNCHES = {"kk72": ([(2, 5, 36, 41)], ROUTE_F64), "kk72b": ([(1, 3, 72, 50)], ROUTE_F64), "kk128": ([(2, 64, 64, 3), (1, 7, 128, 30)], ROUTE_F64_SHARED),
+                    "kk128x3": ([(2, 64, 64, 3), (1, 7, 128, 30), (2, 5, 64, 13)], ROUTE_F64_SHARED),      # three items of different sizes on the shared-panel kernel
                     "mixed96_128": ([(2, 5, 48, 29), (2, 3, 64, 50), (1, 2, 96, 33)], ROUTE_F64)}
 
 
@@ -713,7 +714,7 @@ GRAM128_LAUNCHES = {"kk72": ([(2, 5, 36, 41)], ROUTE_F64), "kk72b": ([(1, 3, 72,
 @pytest.mark.parametrize("nchunks", [0, 2])
 def test_gram_mfma128_f64(launch, nchunks):
     """the gate-path Gram at chi = 64 (launch_mfma_gram128_f64): f32 operands, products exact in f64, f64 accumulation -- 1e-12 of the largest entry.  Both
-    instantiations: <true, true> when every item has D K = 128 (the engine's all_kk128), <true, false> otherwise (KK = 72, a 96 + 128 launch)"""
+    instantiations: <true> when every item has D K = 128 (the engine's all_kk128), <false> otherwise (KK = 72, a 96 + 128 launch)"""
     items, want = GRAM128_LAUNCHES[launch]
     res, route = gram_mfma(items, True, nchunks)
     assert route == want
