@@ -103,6 +103,14 @@ int tnqs_dbg_default_sequence_graph(int nv, int ne, const int32_t* esrc, const i
  * (TNQS_ERR_INVALID), adjacency is not.  HOST ONLY: no device is touched (tests/test_gate_schedule.py) */
 int tnqs_dbg_gate_schedule(int nv, int ne, const int32_t* esrc, const int32_t* edst, int ngates, const int32_t* nverts, const int32_t* verts, int update_cache,
                            int* step_of_gate, int* step_is_bp, int cap, int* nsteps_out);
+/* the launches of one fiber GEMM pass (out = in x_(s,leg) X) as the engine plans them, from the items' shapes alone (csrc/fiber_plan.cpp plan_fiber_pass).
+ * use: 0 single-leg stage of a mode-product chain, 1 gate epilogue, 2 generic whatever the shape (one-site gate, second factorisation pass, region operator);
+ * dtype 0 c64, 1 c128; use_mfma / use_chi64: the two switches (TNQS_NO_MFMA / TNQS_NO_CHI64 unset = 1); shape: (D, PA, K, PB, Do, No) per item.
+ * launches_out (the first cap launches, in stream order), 10 ints each: route (0 generic tiled, 1 f32 matrix-core tiles, 2 register-direct, 3 f64 matrix cores),
+ * D and K of a register-direct launch (else 0), fibers per tile TR, tiles per workgroup, KKmax, NNmax, workgroups, items, 1 = general form of the f64 kernel.
+ * items_out, 7 ints per item in the caller's order: its launch, its first workgroup, its workgroups (= norm partials), TA, TB, nta, ntb.
+ * A site too large for the generic kernel: TNQS_ERR_UNSUPPORTED.  HOST ONLY: no device is touched (tests/test_fiber_plan.py) */
+int tnqs_dbg_fiber_plan(int use, int dtype, int use_mfma, int use_chi64, int nitems, const int* shape, int* launches_out, int cap, int* nlaunches_out, int* items_out);
 /* ---- loop corrections (csrc/kernels_loop.hip; dtype 0 c64, 1 c128; column-major matrices, the items' matrices one after the other in every array) ----
  * loop_cgemm_kernel<T>, ONE launch: C_i (m[i] x n[i]) = A_i (m[i] x k[i]) op(B_i); opB = 0: B_i is k[i] x n[i]; opB = 1: B_i is n[i] x k[i], op = conjugate transpose.
  * C holds `guard` elements, then C_0, `guard` elements, C_1, ..., `guard` elements: the whole array goes to the device as the caller filled it and comes back,

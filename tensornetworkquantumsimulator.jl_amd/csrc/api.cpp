@@ -247,6 +247,18 @@ int tnqs_dbg_gate_schedule(int nv, int ne, const int32_t* esrc, const int32_t* e
                        auto g = dbg_make_graph(nv, ne, esrc, edst); const GateSchedule steps = build_gate_schedule(*g, ngates, nverts, verts, update_cache != 0); *nsteps_out = (int)steps.size();
                        for (int k = 0; k < (int)steps.size(); ++k) { if (step_is_bp && k < cap) step_is_bp[k] = steps[k].is_bp ? 1 : 0; if (step_of_gate) for (int i = steps[k].begin; i < steps[k].end; ++i) step_of_gate[i] = k; } });
 }
+int tnqs_dbg_fiber_plan(int use, int dtype, int use_mfma, int use_chi64, int nitems, const int* shape, int* launches, int cap, int* nlaunches_out, int* items_out) {
+    return guard([&] { if (use < 0 || use > 2 || (dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 0 || (nitems > 0 && !shape) || !nlaunches_out) throw Err(TNQS_ERR_INVALID, "tnqs_dbg_fiber_plan: bad arguments");
+                       std::vector<FiberItem> items(nitems);
+                       for (int i = 0; i < nitems; ++i) { const int* q = shape + 6 * i; for (int k = 0; k < 6; ++k) if (q[k] < 1) throw Err(TNQS_ERR_INVALID, "tnqs_dbg_fiber_plan: bad shape");
+                                                          FiberItem& it = items[i]; it.D = q[0]; it.PA = q[1]; it.K = q[2]; it.PB = q[3]; it.Do = q[4]; it.No = q[5]; }
+                       const std::vector<FiberLaunch> plan = plan_fiber_pass(items.data(), nitems, fiber_rules(use == 0 ? FiberUse::Chain : use == 1 ? FiberUse::Epilogue : FiberUse::Plain, dtype == TNQS_C64, use_mfma != 0, use_chi64 != 0),
+                                                                            dtype == TNQS_C64 ? 8 : 16);
+                       *nlaunches_out = (int)plan.size();
+                       for (int l = 0; l < (int)plan.size(); ++l) { const FiberLaunch& L = plan[l];
+                           if (launches && l < cap) { const int v[10] = {(int)L.route, L.D, L.K, L.TR, L.tpw, L.KKmax, L.NNmax, L.wgs, (int)L.items.size(), L.general ? 1 : 0}; std::copy(v, v + 10, launches + 10 * l); }
+                           if (items_out) for (size_t k = 0; k < L.items.size(); ++k) { const FiberItem& it = L.items[k]; const int v[7] = {l, it.tile_begin, L.nwg[k], it.TA, it.TB, it.nta, it.ntb}; std::copy(v, v + 7, items_out + 7 * L.index[k]); } } });
+}
 int tnqs_dbg_jacobi(int dtype, int m, int n, void* A, void* V, int* sweeps) { return guard([&] { dbg_jacobi(dtype, m, n, A, V, sweeps); }); }
 int tnqs_dbg_theta_svd_pre(int m, int n, int nq, void* A, const void* Q, void* V, int* sweeps, int copies, int reps, double* ms, double* phase_us, int cap) { return guard([&] { dbg_theta_svd_pre(m, n, nq, A, Q, V, sweeps, copies, reps, ms, phase_us, cap); }); }
 int tnqs_dbg_time_jacobi_f32(int m, int n, const void* A, int copies, int reps, double* ms, int* sweeps) { return guard([&] { dbg_time_jacobi_f32(m, n, A, copies, reps, ms, sweeps); }); }

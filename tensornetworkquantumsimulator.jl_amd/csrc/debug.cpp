@@ -136,18 +136,16 @@ void dbg_fiber_gemm(int dtype, int D, int PA, int K, int PB, int Do, int No, con
     dIn.up(in, nin * esz); dX.up(X, nx * esz);
     HIPCHK(hipMemset(dOut.p, 0xff, nout * esz));
     FiberItem it{}; it.in = dIn.p; it.out = dOut.p; it.X = dX.p; it.D = D; it.PA = PA; it.K = K; it.PB = PB; it.Do = Do; it.No = No;
-    int TR = pick_TR((size_t)D * K, esz, 1);
-    bool mf = use_mfma && dtype == TNQS_C64 && mfma_fiber_tile_rows(D * K, Do * No) > 0;
-    if (mf) TR = mfma_fiber_tile_rows(D * K, Do * No);
     it.want_norm = 1;
-    const bool mf64 = use_mfma && dtype == TNQS_C128 && fiber_gemm_f64_covers(it);       // kernels_f64.hip (general form: D, Do, norm partial)
-    const int tiles = mf64 ? plan_fiber_gemm_f64(&it, 1, nullptr, 12) : plan_fiber_gemm(&it, 1, TR, mf ? 5 : 1);
+    // laid out by the engine's planner under this entry point's own rules: the epilogue's (general f64 kernel) without RowGemm and without the lower bound of
+    // the f32 matrix-core route, tiles per workgroup forced to values that do not divide the tile counts of the tests
+    FiberRules r = fiber_rules(FiberUse::Epilogue, dtype == TNQS_C64, use_mfma != 0, true); r.rg_D = 0; r.kk_min = 1; r.mfma_tpw = 5; r.f64_tpw = 12;
+    const std::vector<FiberLaunch> plan = plan_fiber_pass(&it, 1, r, esz);
+    const FiberLaunch& L = plan[0]; const int tiles = L.wgs;
     DBuf dN((size_t)tiles * 8);
-    dI.up(&it, sizeof(it));
-    if (mf64) launch_mfma_fiber_gemm_f64(nullptr, (const FiberItem*)dI.p, 1, tiles, D * K, Do * No, (double*)dN.p, true);
-    else if (mf) launch_mfma_fiber_gemm(nullptr, (const FiberItem*)dI.p, 1, tiles, D * K, Do * No, (double*)dN.p);
-    else if (dtype == TNQS_C64) launch_fiber_gemm<float>(nullptr, (const FiberItem*)dI.p, 1, tiles, TR, D * K, (double*)dN.p);
-    else launch_fiber_gemm<double>(nullptr, (const FiberItem*)dI.p, 1, tiles, TR, D * K, (double*)dN.p);
+    dI.up(L.items.data(), sizeof(FiberItem));
+    if (dtype == TNQS_C64) launch_fiber_route<float>(nullptr, L, (const FiberItem*)dI.p, (double*)dN.p);
+    else launch_fiber_route<double>(nullptr, L, (const FiberItem*)dI.p, (double*)dN.p);
     HIPCHK(hipDeviceSynchronize());
     dOut.down(out, nout * esz);
     if (norm2) { std::vector<double> np(tiles); dN.down(np.data(), (size_t)tiles * 8); double t = 0; for (double v : np) t += v; *norm2 = t; }
@@ -446,7 +444,7 @@ void dbg_gauge_gram(int z, const int* chi, int bleg, const void* X, const void* 
 }
 
 // ---- entry points that reach exactly the kernels of one engine launch: several items per launch, set up as the engine sets them up
-// (engine_batch.cpp run_chains / run_grams / svd_batch, engine_gates.cpp plan_rowgemm, engine_bp.cpp), a shape the named kernel does not
+// (fiber_plan.cpp, engine_batch.cpp run_chains / run_grams / svd_batch, engine_bp.cpp), a shape the named kernel does not
 // take is refused (TNQS_ERR_UNSUPPORTED) and *route says which kernel ran (TNQS_DBG_ROUTE_*, include/tnqs_debug.h) ----
 namespace {
 template <class F> void cat_offsets(int n, std::vector<size_t>& off, F&& size_of) { off.assign(n + 1, 0); for (int i = 0; i < n; ++i) off[i + 1] = off[i] + size_of(i); }
@@ -462,7 +460,7 @@ void dbg_rowgemm(int D, int K, int nitems, const int* PA, const int* PB, const i
     for (int i = 0; i < nitems; ++i) {
         FiberItem& it = items[i]; it.D = D; it.PA = PA[i]; it.K = K; it.PB = PB[i]; it.Do = D; it.No = No[i];
         if (PA[i] < 1 || PB[i] < 1 || !rowgemm_covers(it)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_rowgemm: item not covered by the register-direct kernels");
-        rowgemm_tiles(it); it.want_norm = 1;
+        it.want_norm = 1;
     }
     std::vector<size_t> oi, ox, oo;
     cat_offsets(nitems, oi, [&](int i) { return (size_t)D * PA[i] * K * PB[i]; });
@@ -475,16 +473,19 @@ void dbg_rowgemm(int D, int K, int nitems, const int* PA, const int* PB, const i
         FiberItem& it = items[i];
         it.in = (char*)dIn.p + oi[i] * 8; it.X = (char*)dX.p + ox[i] * 8; it.out = (char*)dOut.p + oo[i] * 8;
     }
-    const int wgs = plan_rowgemm(items.data(), nitems, D == 2 ? 32 : 64, nullptr, tpw);
+    // the engine's plan of the pass (D = 2: gate epilogue, D = 1: mode product), tpw forced when given: one RowGemm launch over all items
+    FiberRules r = fiber_rules(D == 2 ? FiberUse::Epilogue : FiberUse::Chain, true, true, true); r.rg_tpw = tpw;
+    const std::vector<FiberLaunch> plan = plan_fiber_pass(items.data(), nitems, r, 8);
+    const FiberLaunch& L = plan[0]; const int wgs = L.wgs;
+    if (L.route != FiberRoute::RowGemm || (int)L.items.size() != nitems) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_rowgemm: item not covered by the register-direct kernels");
     DBuf dN((size_t)wgs * 8);
-    dI.up(items.data(), sizeof(FiberItem) * nitems);
-    launch_mfma_rowgemm(nullptr, (const FiberItem*)dI.p, nitems, wgs, D, K, (double*)dN.p);
+    dI.up(L.items.data(), sizeof(FiberItem) * nitems);
+    launch_fiber_route<float>(nullptr, L, (const FiberItem*)dI.p, (double*)dN.p);
     HIPCHK(hipDeviceSynchronize());
     dOut.down(out, oo[nitems] * 8);
     std::vector<double> np(wgs); dN.down(np.data(), (size_t)wgs * 8);
     for (int i = 0; i < nitems; ++i) {
-        const int end = i + 1 < nitems ? items[i + 1].tile_begin : wgs;
-        double t = 0; for (int w = items[i].tile_begin; w < end; ++w) t += np[w];
+        double t = 0; for (int w = 0; w < L.nwg[i]; ++w) t += np[L.items[i].tile_begin + w];
         if (norm2) norm2[i] = t;
     }
     if (route) *route = (D * K == 64 && mfma_use_x3()) ? TNQS_DBG_ROUTE_X3 : TNQS_DBG_ROUTE_F32;

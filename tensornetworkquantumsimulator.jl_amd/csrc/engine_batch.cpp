@@ -7,11 +7,33 @@ namespace tnqs {
 // ---------------------------------------------------------------------------------------------------------------
 // batched building blocks
 // ---------------------------------------------------------------------------------------------------------------
+void FiberPass::prepare(State* s, size_t k, bool norms) {
+    if (norms) np[k] = dalloc(s, (size_t)std::max(1, plan[k].wgs) * sizeof(double));
+    d_items[k] = upload(s, plan[k].items);
+}
+template <class T> void FiberPass::launch(State* s, size_t k, int cls, bool book) const {
+    const FiberLaunch& L = plan[k];
+    if (L.items.empty()) return;
+    double* const partials = np[k] ? reinterpret_cast<double*>(np[k]->p) : nullptr;
+    if (cls < 0) { launch_fiber_route<T>(s->stream, L, d_items[k], partials); return; }
+    double bytes = 0, flops = 0;
+    const bool rg = L.route == FiberRoute::RowGemm;
+    if (book && !(rg && k > 0))      // RowGemm launches come first in a plan: launch 0 books them all
+        for (size_t q = k; q < plan.size() && (q == k || (rg && plan[q].route == FiberRoute::RowGemm)); ++q)
+            for (const FiberItem& it : plan[q].items) {
+                const double fibers = (double)it.PA * it.PB, nin = fibers * it.D * it.K;
+                bytes += (nin + fibers * it.Do * it.No) * s->esz(); flops += 8.0 * nin * it.Do * it.No;
+            }
+    ProfScope ps(s, cls, bytes, flops);
+    launch_fiber_route<T>(s->stream, L, d_items[k], partials);
+}
+template void FiberPass::launch<float>(State*, size_t, int, bool) const;
+template void FiberPass::launch<double>(State*, size_t, int, bool) const;
+
 template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls, int cls_pair) {
     if (cls_pair < 0) cls_pair = cls;
     const size_t esz = s->esz();
     std::vector<int> nt(chains.size(), 0);          // temporaries written so far (ping-pong index)
-    std::vector<size_t> done(chains.size(), 0);     // steps consumed from the FRONT of c.steps after the pair stage
     for (auto& c : chains) c.result = c.src;
     // ---- stage 0: two legs per pass over the tensor -- 32-dimensional legs: mfma_pair_kernel (once), 16-dimensional legs:
     // mfma_pair16_kernel, repeated while a chain still has two of them (a degree-6 site absorbs its legs in 3 passes instead of 5) ---
@@ -100,64 +122,24 @@ template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls
     }
     size_t maxsteps = 0;
     for (auto& c : chains) maxsteps = std::max(maxsteps, c.steps.size());
+    const FiberRules rules = fiber_rules_of(s, FiberUse::Chain);
+    std::vector<FiberItem> items;
     for (size_t o = 0; o < maxsteps; ++o) {
-        std::vector<FiberItem> items; size_t KKmax = 1; double bytes = 0, flops = 0;
-        for (auto& c : chains) if (c.steps.size() > o) KKmax = std::max<size_t>(KKmax, c.sd.chi[c.steps[o].first]);
-        int TR = pick_TR(KKmax, esz, 1);
-        bool mf = false;
-        if (std::is_same<T, float>::value && use_mfma() && KKmax >= 8) { int t = mfma_fiber_tile_rows((int)KKmax, (int)KKmax); if (t > 0) { TR = t; mf = true; } }
-        int tpw = 1;
-        if (mf) { double tot = 0; for (auto& c : chains) if (c.steps.size() > o) tot += (double)c.sd.n / c.sd.chi[c.steps[o].first] / TR; tpw = (int)std::max(1.0, std::min(TR == 32 ? 32.0 : 8.0, tot / 4096.0)); if (TR == 32 && tpw >= 4) tpw &= ~3; }
-        std::vector<FiberItem> rg_items, rg32_items; double rg_bytes = 0, rg_flops = 0;      // chi = 64 (32) legs: register-direct MFMA kernel
+        items.clear();
         for (size_t ci = 0; ci < chains.size(); ++ci) {
             Chain& c = chains[ci];
             if (c.steps.size() <= o) continue;
-            int j = c.steps[o].first;
+            const int j = c.steps[o].first;
             c.trail.push_back({j});
-            FiberItem it{};
             Buf& dst = c.tmp[nt[ci] & 1];
             if (!dst) dst = dalloc(s, c.sd.n * esz);
+            FiberItem it = site_fiber_item(c.sd, j, false, c.sd.chi[j], false);
             it.in = c.result; it.out = dst->p; it.X = c.steps[o].second;
-            it.D = 1; it.PA = (int)c.sd.pre(j); it.K = c.sd.chi[j]; it.PB = (int)c.sd.post(j); it.Do = 1; it.No = it.K;
-            if (std::is_same<T, float>::value && use_mfma() && rowgemm_covers(it) && (it.K != 64 || use_chi64())) {
-                rowgemm_tiles(it); it.want_norm = 0;
-                (it.K == 64 ? rg_items : rg32_items).push_back(it);
-                c.result = dst->p; nt[ci]++;
-                rg_bytes += 2.0 * c.sd.n * esz; rg_flops += 8.0 * c.sd.n * it.K;
-                continue;
-            }
-            it.want_norm = 0;
             items.push_back(it);
             c.result = dst->p; nt[ci]++;
-            bytes += 2.0 * c.sd.n * esz; flops += 8.0 * c.sd.n * it.K;
         }
-        bool booked = false;
-        for (int pass = 0; pass < 2; ++pass) {
-            std::vector<FiberItem>& ri = pass ? rg32_items : rg_items;
-            if (ri.empty()) continue;
-            const int wgs = plan_rowgemm(ri.data(), (int)ri.size(), 64);
-            const FiberItem* d = upload(s, ri);
-            ProfScope ps(s, cls, booked ? 0.0 : rg_bytes, booked ? 0.0 : rg_flops); booked = true;      // bytes / flops of both groups are booked on the first scope
-            launch_mfma_rowgemm(s->stream, d, (int)ri.size(), wgs, 1, pass ? 32 : 64, nullptr);
-        }
-        if (items.empty()) continue;
-        // ComplexF64: the f64 matrix cores (kernels_f64.hip) when every product of the pass is one the kernel takes
-        bool f64mf = std::is_same<T, double>::value && use_mfma();
-        for (auto& it : items) f64mf = f64mf && fiber_gemm_f64_covers(it);
-        if (f64mf) {
-            const int wgs = plan_fiber_gemm_f64(items.data(), (int)items.size());
-            const FiberItem* d = upload(s, items);
-            ProfScope ps(s, cls, bytes, flops);
-            launch_mfma_fiber_gemm_f64(s->stream, d, (int)items.size(), wgs, (int)KKmax, (int)KKmax, nullptr, false);
-            continue;
-        }
-        const int tiles = plan_fiber_gemm(items.data(), (int)items.size(), TR, mf ? tpw : 1);
-        const FiberItem* d = upload(s, items);
-        ProfScope ps(s, cls, bytes, flops);
-        if (mf) launch_mfma_fiber_gemm(s->stream, d, (int)items.size(), tiles, (int)KKmax, (int)KKmax, nullptr);
-        else launch_fiber_gemm<T>(s->stream, d, (int)items.size(), tiles, TR, (int)KKmax, nullptr);
+        FiberPass(items, rules, esz).run<T>(s, cls, /*norms=*/false);
     }
-    (void)done;
 }
 
 // the tall route of svd_batch (ComplexF32, no V): Cholesky-QR preprocessing, Jacobi on R, A <- A J, polishing sweeps where the pivot collapsed.

@@ -73,6 +73,14 @@ template <class T> static void norm_and_replace(State* s, const std::vector<int>
     }
 }
 
+// the same for launch k of a fiber GEMM pass: vert_of[i] = the vertex of the pass's item i, whose output is P.outs[i]
+template <class T> static void norm_and_replace(State* s, const FiberPass& P, size_t k, const std::vector<int>& vert_of, bool normalize) {
+    const FiberLaunch& L = P.plan[k];
+    std::vector<int> verts, tb; std::vector<Buf> outs;
+    for (size_t i = 0; i < L.items.size(); ++i) { verts.push_back(vert_of[L.index[i]]); outs.push_back(P.outs[L.index[i]]); tb.push_back(L.items[i].tile_begin); }
+    norm_and_replace<T>(s, verts, outs, P.np[k], tb, L.nwg, normalize);
+}
+
 // d x d complex matrices, column-major [s' + d s] as (re, im) pairs
 static bool is_unitary(const double* m, int d, double tol) {
     for (int a = 0; a < d; ++a) for (int b = 0; b < d; ++b) {
@@ -143,42 +151,23 @@ template <class T> static void apply_one_site_batch(State* s, const std::vector<
             return;
         }
     }
-    std::vector<FiberItem> items; std::vector<int> verts, tb, nt; std::vector<Buf> outs;
-    size_t KKmax = 1; double bytes = 0, flops = 0;
-    for (auto& g1 : gates) KKmax = std::max<size_t>(KKmax, s->d[g1.v]);
-    const int TR = pick_TR(KKmax, esz, 1);
-    std::vector<T> hx;       // X[kk + d*nn] = G[nn, kk]  (out[s'] = sum_s G[s', s] psi[s], simple_update.jl:27)
-    std::vector<size_t> xoff;
-    for (auto& g1 : gates) {
-        int d = s->d[g1.v]; xoff.push_back(hx.size());
-        for (int nn = 0; nn < d; ++nn) for (int kk = 0; kk < d; ++kk) { hx.push_back((T)g1.mat[2 * (nn + d * kk)]); hx.push_back((T)g1.mat[2 * (nn + d * kk) + 1]); }
-    }
-    // note: column-major X means index kk + d*nn; the loop above emits nn-major order, i.e. X[kk + d*nn] at position nn*d + kk
-    const char* dxp;
-    {
-        std::vector<char> raw(reinterpret_cast<char*>(hx.data()), reinterpret_cast<char*>(hx.data()) + hx.size() * sizeof(T));
-        dxp = upload(s, raw);
-    }
-    size_t gi = 0;
-    for (auto& g1 : gates) {
-        if (!s->owns(g1.v)) { ++gi; continue; }
-        SD sd = site_dims(s, g1.v);
-        FiberItem it{}; Buf out = dalloc(s, sd.n * esz);
-        it.in = s->site[g1.v]->p; it.out = out->p; it.X = dxp + xoff[gi] * sizeof(T);
-        it.D = sd.d; it.PA = (int)(sd.n / sd.d); it.K = 1; it.PB = 1; it.Do = sd.d; it.No = 1; it.want_norm = normalize ? 1 : 0;
-        verts.push_back(g1.v); outs.push_back(out); items.push_back(it);
-        bytes += 2.0 * sd.n * esz; flops += 8.0 * sd.n * sd.d;
-        ++gi;
+    std::vector<FiberItem> items; std::vector<int> verts; std::vector<Buf> outs;
+    FiberRules rules = fiber_rules_of(s, FiberUse::Plain);
+    SiteOps<T> ops;
+    for (auto& g1 : gates) { rules.kk_floor = std::max(rules.kk_floor, s->d[g1.v]); ops.add(g1.mat, s->d[g1.v]); }
+    ops.send(s);
+    for (size_t gi = 0; gi < gates.size(); ++gi) {
+        const int v = gates[gi].v;
+        if (!s->owns(v)) continue;
+        SD sd = site_dims(s, v);
+        Buf out = dalloc(s, sd.n * esz);
+        items.push_back(ops.item(gi, sd, s->site[v]->p, out->p, normalize));
+        verts.push_back(v); outs.push_back(out);
     }
     if (items.empty()) return;
-    nt.resize(items.size());
-    const int tiles = plan_fiber_gemm(items.data(), (int)items.size(), TR, 1, nt.data());
-    for (auto& it : items) tb.push_back(it.tile_begin);
-    Buf np = dalloc(s, std::max(1, tiles) * sizeof(double));
-    const FiberItem* d = upload(s, items);
-    { ProfScope ps(s, TNQS_PROF_GATE_APPLY, bytes, flops);
-      launch_fiber_gemm<T>(s->stream, d, (int)items.size(), tiles, TR, (int)KKmax, reinterpret_cast<double*>(np->p)); }
-    norm_and_replace<T>(s, verts, outs, np, tb, nt, normalize);
+    FiberPass P(items, rules, esz); P.outs = std::move(outs);
+    P.run<T>(s, TNQS_PROF_GATE_APPLY, /*norms=*/true);
+    norm_and_replace<T>(s, P, 0, verts, normalize);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -282,8 +271,6 @@ template <class T> struct TwoSiteBatch {
     struct EnvRec { int de; int n; void *H, *V, *msq, *prj; };      // views into one arena (env_arena): thousands of 16 KiB pool allocations per batch
                                                                     // were a third of the host time between a BP update and the first kernel of a batch
     struct GateWS { Buf lam1, lam2, idx1, idx2, theta, thetaV, theta0, X1, X2, S, lowA, lowB, lowG, lowL, lowW, lowQ, lowB1, lowG2, lowL2, lowLc; int n1, n2, chi, cap; };
-    struct RgGroup { int kk = 0; std::vector<FiberItem> sub; std::vector<int> sv, stb, snt; std::vector<Buf> so; int wgs = 0; Buf npr; const FiberItem* d = nullptr; };
-    struct RgPlan { bool valid = false; std::vector<RgGroup> groups; std::vector<char> via; double rby = 0, rfl = 0; };
 
     State* s; const Graph& g; const tnqs_apply_opts& ao; double* errs;
     const size_t esz; const bool sharded;
@@ -304,7 +291,7 @@ template <class T> struct TwoSiteBatch {
     std::vector<GateWS> ws; std::vector<int> pg; int npg = 0;                  // pg: gates this rank takes part in
     std::vector<GateItem> gitems; const GateItem* d_gitems = nullptr; bool lowrank_on_batch = false; int cap_max = 1; size_t x2_max = 0;
     ReadRoute route = ReadRoute::two_trips;
-    RgPlan spec_plan;
+    FiberPass spec_plan;                                        // the epilogue pass planned before the read-back (plan_epilogue)
     std::vector<const double*> Sptr; Buf S_keep;
     std::vector<Chain> pch;                                     // the projector passes of step 5
 
@@ -771,27 +758,25 @@ template <class T> struct TwoSiteBatch {
         if (!sharded && rs.empty()) return;
         const size_t m = rs.size();
         std::vector<Buf> X1(m), Q1(m), G2(m), V2(m), GVn(m), GWn(m); Buf d_rk = dalloc(s, std::max<size_t>(1, m) * sizeof(int));
-        std::vector<Qr2RinvItem> ri; std::vector<FiberItem> fi; std::vector<GramJob> gj; std::vector<size_t> own_k; size_t KKmax = 1;
+        std::vector<Qr2RinvItem> ri; std::vector<FiberItem> fi; std::vector<GramJob> gj; std::vector<size_t> own_k;
         for (size_t k = 0; k < m; ++k) {
             const size_t i = rs[k]; const int q = rq[k]; const bool second = (i & 1) != 0; const int n = nof(i); const size_t nn = (size_t)n * n;
             X1[k] = dalloc(s, nn * 16); V2[k] = dalloc(s, nn * 16); GVn[k] = dalloc(s, nn * 16); GWn[k] = dalloc(s, nn * 16);
             ri.push_back(Qr2RinvItem{GW[i]->p, second ? gitems[q].lam2 : gitems[q].lam1, second ? gitems[q].idx2 : gitems[q].idx1, gitems[q].info + (second ? 1 : 0), n, X1[k]->p});
-            if (sj[i].owned) { own_k.push_back(k); KKmax = std::max<size_t>(KKmax, (size_t)n); Q1[k] = dalloc(s, sj[i].sd.n * esz); }
+            if (sj[i].owned) { own_k.push_back(k); Q1[k] = dalloc(s, sj[i].sd.n * esz); }
         }
-        const int TR = pick_TR(KKmax, esz, 1);
         for (size_t k : own_k) {
-            const size_t i = rs[k]; const SiteJob& j = sj[i]; const int chi = j.sd.chi[j.bleg];
-            FiberItem it{}; it.in = gauged_of[i]; it.out = Q1[k]->p; it.X = X1[k]->p;
-            it.D = j.sd.d; it.PA = (int)(j.sd.pre(j.bleg) / j.sd.d); it.K = chi; it.PB = (int)j.sd.post(j.bleg); it.Do = j.sd.d; it.No = chi;
+            const size_t i = rs[k]; const SiteJob& j = sj[i];
+            FiberItem it = site_fiber_item(j.sd, j.bleg, true, j.sd.chi[j.bleg], false); it.in = gauged_of[i]; it.out = Q1[k]->p; it.X = X1[k]->p;
             fi.push_back(it);
             GramJob g2{}; g2.X = Q1[k]->p; g2.Y = Q1[k]->p; g2.sd = j.sd; g2.leg = j.bleg; g2.keep_site = true; gj.push_back(g2);
         }
         if (m) { const Qr2RinvItem* d = upload(s, ri); ProfScope ps(s, TNQS_PROF_SMALL, 0, 0); launch_qr2_rinv(s->stream, d, (int)m); }
         if (!fi.empty()) {
-            const int tiles = plan_fiber_gemm(fi.data(), (int)fi.size(), TR, 1);
-            Buf np = dalloc(s, std::max(1, tiles) * sizeof(double)); const FiberItem* d = upload(s, fi);
-            { ProfScope ps(s, TNQS_PROF_GATE_APPLY, 0, 0); launch_fiber_gemm<T>(s->stream, d, (int)fi.size(), tiles, TR, (int)KKmax, reinterpret_cast<double*>(np->p)); }
-            s->keepalive.push_back(np);
+            // (Plain: these ComplexF64 sites stay on the generic kernel, whatever the f64 matrix-core kernel would take)
+            FiberPass Q(fi, fiber_rules_of(s, FiberUse::Plain), esz);
+            Q.prepare(s, 0, /*norms=*/true); Q.launch<T>(s, 0, TNQS_PROF_GATE_APPLY, /*book=*/false);
+            s->keepalive.push_back(Q.np[0]);
             run_grams<T, double>(s, gj, TNQS_PROF_GATE_GRAM);
             std::vector<ReduceItem> rd; int elems = 0;
             for (size_t t = 0; t < own_k.size(); ++t) {
@@ -874,7 +859,7 @@ template <class T> struct TwoSiteBatch {
         route = stage ? ReadRoute::deferred : one_trip ? ReadRoute::one_trip : ReadRoute::two_trips;
         auto run_ahead = [&]() {        // the whole chain, sized from upper bounds, and the epilogue plan for new bond dimensions at their caps
             svd_and_finish(nullptr);
-            if (!sharded && ao.maxdim > 0) spec_plan = plan_epilogue([&](int gi) { return ws[gi].cap; }, [&](size_t q) { return (const void*)s->site[sj[own_idx[q]].v]->p; }, nullptr);
+            if (!sharded && ao.maxdim > 0) spec_plan = plan_epilogue([&](int gi) { return ws[gi].cap; }, [&](size_t q) { return (const void*)s->site[sj[own_idx[q]].v]->p; });
             ht_a.stop(); ht_s4.stop();
         };
         switch (route) {
@@ -961,39 +946,28 @@ template <class T> struct TwoSiteBatch {
         }
     }
 
-    // ---- epilogue plan (step 5) for the register-direct MFMA kernel: items, output buffers, uploaded descriptors.  Built twice at most: speculatively
-    // BEFORE the read-back of the batch -- assuming every new bond dimension equals its cap and no projector pass is needed, which is the steady state of a
-    // saturated evolution -- so that after the synchronisation the epilogue is launched at once instead of after 0.25 ms of host preparation with an idle
-    // chip (20x20: 380 items and output buffers); and again after the read-back when the assumption did not hold --------------------------------------
-    template <class ChiOf, class InOf> RgPlan plan_epilogue(ChiOf chi_of, InOf in_of, std::vector<char>* skip) {
-        RgPlan P; P.via.assign(own_idx.size(), 0);
-        std::vector<FiberItem> rg; std::vector<int> rverts; std::vector<Buf> routs;
-        if (F32 && use_mfma())
-            for (size_t q = 0; q < own_idx.size(); ++q) {
-                if (skip && (*skip)[q]) continue;
-                size_t i = own_idx[q]; int gi = (int)i / 2; int chin = chi_of(gi); const SiteJob& j = sj[i];
-                FiberItem it{};
-                it.D = j.sd.d; it.PA = (int)(j.sd.pre(j.bleg) / j.sd.d); it.K = j.sd.chi[j.bleg]; it.PB = (int)j.sd.post(j.bleg); it.Do = j.sd.d; it.No = chin;
-                if (!rowgemm_covers(it) || it.D != 2 || (it.K == 64 && !use_chi64())) continue;
-                const size_t nout = j.sd.n / it.K * chin;
-                Buf out = dalloc(s, nout * esz);
-                it.in = in_of(q); it.out = out->p; it.X = (i & 1) ? ws[gi].X2->p : ws[gi].X1->p;
-                rowgemm_tiles(it); it.want_norm = ao.normalize_tensors ? 1 : 0;
-                rg.push_back(it); rverts.push_back(j.v); routs.push_back(out);
-                P.rby += (double)(j.sd.n + nout) * esz; P.rfl += 8.0 * j.sd.n * j.sd.d * chin; P.via[q] = 1; if (skip) (*skip)[q] = 1;
-            }
-        for (int kk : {64, 32}) {
-            RgGroup G; G.kk = kk;
-            for (size_t q = 0; q < rg.size(); ++q) if (rg[q].K == kk) { G.sub.push_back(rg[q]); G.sv.push_back(rverts[q]); G.so.push_back(routs[q]); }
-            if (G.sub.empty()) continue;
-            G.snt.resize(G.sub.size());
-            G.wgs = tnqs::plan_rowgemm(G.sub.data(), (int)G.sub.size(), 32, G.snt.data());
-            for (auto& it : G.sub) G.stb.push_back(it.tile_begin);
-            G.npr = dalloc(s, (size_t)G.wgs * sizeof(double));
-            G.d = upload(s, G.sub);
-            P.groups.push_back(std::move(G));
+    // ---- epilogue pass (step 5): the fiber GEMM psi' = psi~ x_(s,b) X of every owned site, planned for the new bond dimensions chi_of(gate), with its
+    // register-direct launches PREPARED -- output buffers, norm partials, uploaded descriptors.  Built twice at most: speculatively BEFORE the read-back of the
+    // batch -- assuming every new bond dimension equals its cap and no projector pass is needed, which is the steady state of a saturated evolution -- so that
+    // after the synchronisation the epilogue is launched at once instead of after 0.25 ms of host preparation with an idle chip (20x20: 380 items and output
+    // buffers); and again after the read-back when the assumption did not hold ----------------------------------------------------------------------------
+    // output buffers of the pass's RowGemm launches (rowgemm) or of its other launch, in site order
+    void alloc_outs(FiberPass& P, bool rowgemm) {
+        std::vector<FiberItem*> at(own_idx.size(), nullptr);
+        for (auto& L : P.plan) if ((L.route == FiberRoute::RowGemm) == rowgemm) for (size_t k = 0; k < L.items.size(); ++k) at[L.index[k]] = &L.items[k];
+        for (size_t q = 0; q < at.size(); ++q) if (at[q]) { P.outs[q] = dalloc(s, (size_t)at[q]->Do * at[q]->PA * at[q]->No * at[q]->PB * esz); at[q]->out = P.outs[q]->p; }
+    }
+    template <class ChiOf, class InOf> FiberPass plan_epilogue(ChiOf chi_of, InOf in_of) {
+        std::vector<FiberItem> items;
+        for (size_t q = 0; q < own_idx.size(); ++q) {
+            const size_t i = own_idx[q]; const int gi = (int)i / 2;
+            FiberItem it = site_fiber_item(sj[i].sd, sj[i].bleg, true, chi_of(gi), ao.normalize_tensors != 0);
+            it.in = in_of(q); it.X = (i & 1) ? ws[gi].X2->p : ws[gi].X1->p;
+            items.push_back(it);
         }
-        P.valid = true;
+        FiberPass P(items, fiber_rules_of(s, FiberUse::Epilogue), esz); P.outs.resize(items.size());
+        alloc_outs(P, true);
+        for (size_t k = 0; k < P.plan.size(); ++k) if (P.plan[k].route == FiberRoute::RowGemm) P.prepare(s, k, /*norms=*/true);
         return P;
     }
 
@@ -1008,62 +982,21 @@ template <class T> struct TwoSiteBatch {
         }
         run_chains<T>(s, pch, TNQS_PROF_GATE_MODEPROD);
         if (own_idx.empty()) return;
-        std::vector<FiberItem> items; std::vector<int> verts, tb, nt; std::vector<Buf> outs;
-        size_t KKmax = 1, NNmax = 1; double bytes = 0, flops = 0;
-        for (size_t q = 0; q < own_idx.size(); ++q) {
-            size_t i = own_idx[q];
-            KKmax = std::max<size_t>(KKmax, (size_t)sj[i].sd.d * sj[i].sd.chi[sj[i].bleg]);
-            NNmax = std::max<size_t>(NNmax, (size_t)sj[i].sd.d * info[8 * (i / 2) + 2]);
+        // the speculative pass built before the read-back when it came true, a fresh one otherwise
+        bool spec_ok = spec_plan.valid;
+        for (size_t q = 0; q < own_idx.size() && spec_ok; ++q) { const int gi = (int)own_idx[q] / 2; spec_ok = info[8 * gi + 2] == ws[gi].cap && pch[q].steps.empty() && pch[q].result == s->site[sj[own_idx[q]].v]->p; }
+        FiberPass fresh_plan;
+        if (!spec_ok) {
+            spec_plan = FiberPass{};              // (its output buffers go back to the pool)
+            fresh_plan = plan_epilogue([&](int gi) { return info[8 * gi + 2]; }, [&](size_t q) { return pch[q].result; });
         }
-        int TR = pick_TR(KKmax, esz, 1);
-        bool mf = false;
-        if (F32 && use_mfma() && KKmax >= 8) { int t = mfma_fiber_tile_rows((int)KKmax, (int)NNmax); if (t > 0) { TR = t; mf = true; } }
-        const bool f64mf = !F32 && use_mfma() && KKmax >= 4 && KKmax <= 64 && NNmax <= 64;      // kernels_f64.hip
-        std::vector<char> via64(own_idx.size(), 0);      // sites served by the register-direct matrix-core kernel
-        {   // chi = 64 sites (K = (s, b) = 128 -> N = (s', b') <= 128) and chi = 32 sites on the register-direct MFMA kernel: the speculative plan built
-            // before the read-back when it came true, a fresh one otherwise
-            bool spec_ok = spec_plan.valid;
-            for (size_t q = 0; q < own_idx.size() && spec_ok; ++q) { const int gi = (int)own_idx[q] / 2; spec_ok = info[8 * gi + 2] == ws[gi].cap && pch[q].steps.empty() && pch[q].result == s->site[sj[own_idx[q]].v]->p; }
-            RgPlan fresh_plan;
-            if (!spec_ok) {
-                spec_plan = RgPlan{};              // (its output buffers go back to the pool)
-                fresh_plan = plan_epilogue([&](int gi) { return info[8 * gi + 2]; }, [&](size_t q) { return pch[q].result; }, &via64);
-            } else for (size_t q = 0; q < own_idx.size(); ++q) via64[q] = via64[q] || spec_plan.via[q];
-            RgPlan& P = spec_ok ? spec_plan : fresh_plan;
-            bool booked = false;
-            for (auto& G : P.groups) {          // one launch per contracted dimension
-                { ProfScope ps(s, TNQS_PROF_GATE_APPLY, booked ? 0.0 : P.rby, booked ? 0.0 : P.rfl); booked = true; launch_mfma_rowgemm(s->stream, G.d, (int)G.sub.size(), G.wgs, 2, G.kk, reinterpret_cast<double*>(G.npr->p)); }
-                norm_and_replace<T>(s, G.sv, G.so, G.npr, G.stb, G.snt, ao.normalize_tensors != 0);
-            }
-        }
-        for (size_t q = 0; q < own_idx.size(); ++q) {
-            if (via64[q]) continue;
-            size_t i = own_idx[q];
-            int gi = (int)i / 2; int chin = info[8 * gi + 2];
-            const SiteJob& j = sj[i];
-            size_t pre = j.sd.pre(j.bleg), post = j.sd.post(j.bleg);
-            int chi = j.sd.chi[j.bleg];
-            size_t nout = j.sd.n / chi * chin;
-            FiberItem it{}; Buf out = dalloc(s, nout * esz);
-            it.in = pch[q].result; it.out = out->p; it.X = (i & 1) ? ws[gi].X2->p : ws[gi].X1->p;
-            it.D = j.sd.d; it.PA = (int)(pre / j.sd.d); it.K = chi; it.PB = (int)post; it.Do = j.sd.d; it.No = chin;
-            it.want_norm = ao.normalize_tensors ? 1 : 0;
-            verts.push_back(j.v); outs.push_back(out); items.push_back(it);
-            bytes += (double)(j.sd.n + nout) * esz; flops += 8.0 * j.sd.n * j.sd.d * chin;
-        }
-        // ComplexF64 on the f64 matrix cores: tiles of 16 fibers, 32 per workgroup
-        nt.resize(items.size());
-        const int tiles = f64mf ? plan_fiber_gemm_f64(items.data(), (int)items.size(), nt.data(), 32)
-                                : plan_fiber_gemm(items.data(), (int)items.size(), TR, mf ? (TR == 32 ? 16 : 4) : 1, nt.data());
-        for (auto& it : items) tb.push_back(it.tile_begin);
-        Buf np = dalloc(s, std::max(1, tiles) * sizeof(double));
-        const FiberItem* d = upload(s, items);
-        if (!items.empty())
-        { ProfScope ps(s, TNQS_PROF_GATE_APPLY, bytes, flops);
-          if (f64mf) launch_mfma_fiber_gemm_f64(s->stream, d, (int)items.size(), tiles, (int)KKmax, (int)NNmax, reinterpret_cast<double*>(np->p), true);
-          else if (mf) launch_mfma_fiber_gemm(s->stream, d, (int)items.size(), tiles, (int)KKmax, (int)NNmax, reinterpret_cast<double*>(np->p));
-          else launch_fiber_gemm<T>(s->stream, d, (int)items.size(), tiles, TR, (int)KKmax, reinterpret_cast<double*>(np->p)); }
-        norm_and_replace<T>(s, verts, outs, np, tb, nt, ao.normalize_tensors != 0);
+        FiberPass& P = spec_ok ? spec_plan : fresh_plan;
+        std::vector<int> vert_of; for (int i : own_idx) vert_of.push_back(sj[i].v);
+        const bool norm = ao.normalize_tensors != 0;
+        // the register-direct launches first (one per contracted dimension), then what they left: prepared only now, behind them
+        for (size_t k = 0; k < P.plan.size(); ++k) if (P.plan[k].route == FiberRoute::RowGemm) { P.launch<T>(s, k, TNQS_PROF_GATE_APPLY); norm_and_replace<T>(s, P, k, vert_of, norm); }
+        alloc_outs(P, false);
+        for (size_t k = 0; k < P.plan.size(); ++k) if (P.plan[k].route != FiberRoute::RowGemm) { P.prepare(s, k, /*norms=*/true); P.launch<T>(s, k, TNQS_PROF_GATE_APPLY); norm_and_replace<T>(s, P, k, vert_of, norm); }
     }
 
     // ---- 6. both bond messages := diag(S)  (apply_gates.jl:126-135), new bond dimension ---------------------------

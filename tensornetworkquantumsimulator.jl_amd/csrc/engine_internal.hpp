@@ -1,6 +1,7 @@
 // engine_internal.hpp -- declarations shared by the translation units of the host engine:
 //   engine_core.cpp   pool, graph, state container, tensor / message I/O
-//   engine_batch.cpp  batched building blocks: mode-product chains, Gram jobs, the SVD batch
+//   engine_batch.cpp  batched building blocks: fiber GEMM passes (FiberPass), mode-product chains, Gram jobs, the SVD batch
+//   fiber_plan.cpp    which fiber GEMM kernel a pass launches and its layout (FiberRoute, plan_fiber_pass; host code, no device call)
 //   bp_schedule.cpp   BP sweep order: default sequence, forest-cover sequence, level schedule (BPPlan; host graph code, no device call)
 //   engine_bp.cpp     BP update: sweep driver (BpUpdate), the launches of one level (BpLevelBatch), products kept across levels (ProdCache)
 //   gate_schedule.cpp apply_gates: validation of the gate list, the step schedule (GateSchedule; host code, no device call)
@@ -266,6 +267,45 @@ struct GramJob {      // out[i,j] = sum X[i,.] conj(Y[j,.]) over everything but 
     Buf final_msg;                 // set: the kernel that computed the message normalised and diffed it too (bp_small_site_kernel, matrix-core form): no msg_finalize item
 };
 
+// ---- fiber GEMM passes (out = in x_(s,leg) X: mode products, gate epilogue, one-site operators): every call site builds its items with the two helpers
+// below and runs them through a FiberPass; which kernel a pass launches is decided in fiber_plan.cpp alone ---------------------------------------------------
+// the item of a site tensor contracted over `leg` (keep_site: the site index takes part, D = Do = d) into a leg of dimension No; pointers left to the caller
+inline FiberItem site_fiber_item(const SD& sd, int leg, bool keep_site, int No, bool want_norm) {
+    FiberItem it{}; it.D = it.Do = keep_site ? sd.d : 1;
+    it.PA = (int)(sd.pre(leg) / it.D); it.K = sd.chi[leg]; it.PB = (int)sd.post(leg); it.No = No; it.want_norm = want_norm ? 1 : 0;
+    return it;
+}
+// one-site operators as operands: out[s'] = sum_s O[s', s] psi[s] (simple_update.jl:27) is the fiber GEMM with D = d, K = 1 and X[s + d s'] = O[s', s].
+// The operators of a pass (d x d, column-major O[s' + d s] as (re, im) pairs) travel in ONE upload
+template <class T> struct SiteOps {
+    std::vector<T> hx; std::vector<size_t> off; const T* dx = nullptr;
+    void add(const double* m, int d) {
+        off.push_back(hx.size());
+        for (int nn = 0; nn < d; ++nn) for (int kk = 0; kk < d; ++kk) { hx.push_back((T)m[2 * (nn + d * kk)]); hx.push_back((T)m[2 * (nn + d * kk) + 1]); }
+    }
+    void send(State* s) { dx = upload(s, hx); }
+    FiberItem item(size_t k, const SD& sd, const void* in, void* out, bool want_norm) const {
+        FiberItem it{}; it.in = in; it.out = out; it.X = dx + off[k];
+        it.D = it.Do = sd.d; it.PA = (int)(sd.n / sd.d); it.K = it.PB = it.No = 1; it.want_norm = want_norm ? 1 : 0;
+        return it;
+    }
+};
+// One pass, planned when it is constructed (plan_fiber_pass; the items' pointers may be filled in afterwards through plan[k].items / index) and run launch by
+// launch: prepare(k) allocates launch k's norm partials (norms: one double per workgroup) and uploads its descriptors, launch(k) enqueues it under a ProfScope of
+// class cls (cls < 0: none).  The two are separate because the gate epilogue prepares its register-direct launches before the batch's read-back and launches them
+// after it.  Bytes and flops come from the items; those of all RowGemm launches of a pass are booked on the first of them; book = false books none.
+struct FiberPass {
+    std::vector<FiberLaunch> plan; std::vector<const FiberItem*> d_items; std::vector<Buf> np;
+    std::vector<Buf> outs;      // the caller's: output buffers by position in ITS list, where it wants them to live and die with the pass
+    bool valid = false;
+    FiberPass() = default;
+    FiberPass(const std::vector<FiberItem>& items, const FiberRules& r, size_t esz)
+        : plan(plan_fiber_pass(items.data(), (int)items.size(), r, esz)), d_items(plan.size(), nullptr), np(plan.size()), valid(true) {}
+    void prepare(State* s, size_t k, bool norms);
+    template <class T> void launch(State* s, size_t k, int cls, bool book = true) const;
+    template <class T> void run(State* s, int cls, bool norms, bool book = true) { for (size_t k = 0; k < plan.size(); ++k) { prepare(s, k, norms); launch<T>(s, k, cls, book); } }
+};
+inline FiberRules fiber_rules_of(const State* s, FiberUse use) { return fiber_rules(use, s->dtype == TNQS_C64, use_mfma(), use_chi64()); }
 template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls, int cls_pair = -1);
 template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& jobs, int cls);
 template <class T> void svd_batch(State* s, const std::vector<JacobiItem>& all, bool with_v);

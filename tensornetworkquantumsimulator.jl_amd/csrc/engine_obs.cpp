@@ -180,18 +180,9 @@ template <class T> static void region_contract(State* s, int nr, const int32_t* 
                 const int d = sd.d; bool ident = true;
                 for (int aa = 0; aa < d && ident; ++aa) for (int bb = 0; bb < d; ++bb) if (m[2 * (aa + d * bb)] != (aa == bb ? 1.0 : 0.0) || m[2 * (aa + d * bb) + 1] != 0.0) { ident = false; break; }
                 if (!ident) {
-                    std::vector<T> hx;
-                    for (int nn = 0; nn < d; ++nn) for (int kk = 0; kk < d; ++kk) { hx.push_back((T)m[2 * (nn + d * kk)]); hx.push_back((T)m[2 * (nn + d * kk) + 1]); }
-                    std::vector<char> raw(reinterpret_cast<char*>(hx.data()), reinterpret_cast<char*>(hx.data()) + hx.size() * sizeof(T));
-                    const char* dx = upload(s, raw);
+                    SiteOps<T> op; op.add(m, d); op.send(s);
                     opbuf = dalloc(s, sd.n * esz);
-                    FiberItem it{}; it.in = ket; it.out = opbuf->p; it.X = dx;
-                    it.D = d; it.PA = (int)(sd.n / d); it.K = 1; it.PB = 1; it.Do = d; it.No = 1;
-                    const int TR = pick_TR(d, esz, 1);
-                    std::vector<FiberItem> items{it};
-                    const int tiles = plan_fiber_gemm(items.data(), 1, TR, 1);
-                    const FiberItem* dI = upload(s, items);
-                    launch_fiber_gemm<T>(s->stream, dI, 1, tiles, TR, d, nullptr);
+                    FiberPass({op.item(0, sd, ket, opbuf->p, false)}, fiber_rules_of(s, FiberUse::Plain), esz).run<T>(s, /*cls=*/-1, /*norms=*/false);
                     ket = opbuf->p;
                 }
             }

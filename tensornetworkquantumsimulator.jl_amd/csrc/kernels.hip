@@ -84,6 +84,19 @@ void launch_fiber_gemm(hipStream_t s, const FiberItem* d_items, int nitems, int 
 }
 template void launch_fiber_gemm<float>(hipStream_t, const FiberItem*, int, int, int, int, double*);
 template void launch_fiber_gemm<double>(hipStream_t, const FiberItem*, int, int, int, int, double*);
+// a planned launch (plan_fiber_pass, fiber_plan.cpp) on the launcher of its route
+template <class T>
+void launch_fiber_route(hipStream_t s, const FiberLaunch& L, const FiberItem* d, double* np) {
+    const int n = (int)L.items.size();
+    switch (L.route) {
+    case FiberRoute::RowGemm: launch_mfma_rowgemm(s, d, n, L.wgs, L.D, L.K, np); break;
+    case FiberRoute::F64: launch_mfma_fiber_gemm_f64(s, d, n, L.wgs, L.KKmax, L.NNmax, np, L.general); break;
+    case FiberRoute::Mfma: launch_mfma_fiber_gemm(s, d, n, L.wgs, L.KKmax, L.NNmax, np); break;
+    case FiberRoute::Generic: launch_fiber_gemm<T>(s, d, n, L.wgs, L.TR, L.KKmax, np); break;
+    }
+}
+template void launch_fiber_route<float>(hipStream_t, const FiberLaunch&, const FiberItem*, double*);
+template void launch_fiber_route<double>(hipStream_t, const FiberLaunch&, const FiberItem*, double*);
 
 // ------------------------------------------------------------------------------------------------------------
 // gram

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime_api.h>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace tnqs {
 
@@ -212,6 +213,27 @@ inline int plan_fiber_gemm(FiberItem* it, int n, int TR, int tpw, int* nwg = nul
     for (int i = 0; i < n; ++i) tile_params(it[i].PA, it[i].PB, TR, it[i].TA, it[i].TB, it[i].nta, it[i].ntb);
     return lay_out(it, n, &FiberItem::tile_begin, nwg, [&](FiberItem& f) { f.tpw = tpw; return (f.nta * f.ntb + tpw - 1) / tpw; });
 }
+// ---- the fiber GEMM kernels of a pass, decided once (fiber_plan.cpp: host only -- no device call, no State, no environment) ----------------------------------
+// generic tiled (fiber_gemm_kernel); f32 matrix-core tiles (mfma_fiber_gemm_w_kernel); register-direct (mfma_rowgemm_kernel / x3_rowgemm64_kernel); f64 matrix cores
+enum class FiberRoute { Generic, Mfma, RowGemm, F64 };
+enum class FiberUse { Chain, Epilogue, Plain };     // single-leg stage of a mode-product chain; gate epilogue; generic whatever the shape (one-site gate, second factorisation pass, region operator)
+struct FiberRules {       // what distinguishes the call sites (fiber_rules(use, ...)); the debug entry points set the fields themselves
+    bool f32 = true, use_mfma = true, use_chi64 = true;     // element type (ComplexF32 / ComplexF64) and the two switches, as values
+    int rg_D = 0, rg_cap = 0, rg_tpw = 0;                   // RowGemm: the D its items must have (0: never taken), the cap of its tpw rule, tpw forced (debug; 0: the rule)
+    bool matrix = false;                                    // what RowGemm leaves may go to the matrix cores (false: Generic)
+    bool general = false;                                   // F64: items with a site index or a norm (general kernel); decided from KKmax / NNmax instead of item by item
+    int kk_min = 8, mfma_tpw = 0, f64_tpw = 0;              // Mfma: smallest KKmax, tiles per workgroup (0: from the pass's tile count); F64: tpw (0: the kernel's rule)
+    int kk_floor = 1;                                       // KKmax is at least this (one-site gates: the site dimensions of the whole batch, owned or not)
+};
+FiberRules fiber_rules(FiberUse use, bool f32, bool use_mfma, bool use_chi64);
+struct FiberLaunch {      // one launch: its items laid out (TA / TB / nta / ntb / tile_begin / tpw set), index[k] = position of items[k] in the caller's list
+    FiberRoute route; int D, K;                             // RowGemm: D and K of all its items (otherwise 0)
+    int TR, tpw, KKmax, NNmax, wgs; bool general;           // wgs: workgroups = norm partials of the launch; nwg[k] of them belong to items[k], from items[k].tile_begin
+    std::vector<FiberItem> items; std::vector<int> index, nwg;
+};
+// the launches of one pass over `items` (geometry set: D, PA, K, PB, Do, No), in stream order: RowGemm K = 64, RowGemm K = 32, then everything else in one launch
+std::vector<FiberLaunch> plan_fiber_pass(const FiberItem* items, int n, const FiberRules& r, size_t esz);
+template <class T> void launch_fiber_route(hipStream_t s, const FiberLaunch& L, const FiberItem* d_items, double* d_norm_partials);
 template <class T, class Acc> void launch_gram(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks,
                                                int TR, int KKmax);
 // the Gram kernel of a batch, decided once by the caller: generic tiled; f32 matrix cores up to 32 x 32 / 64 x 64; message fused on the first
@@ -391,8 +413,8 @@ void launch_mfma_pair_gram2x16(hipStream_t s, const PairGram2x16Item* d_items, i
 
 // ---- MFMA fast paths (ComplexF32 only; kernels_mfma.hip) -----------------------------------------------------------
 int mfma_fiber_tile_rows(int KK, int NN);     // fibers per tile for the shape, 0 = not covered
-bool launch_mfma_fiber_gemm(hipStream_t s, const FiberItem* d_items, int nitems, int total_tiles, int KKmax, int NNmax,
-                            double* d_norm_partials);
+void launch_mfma_fiber_gemm(hipStream_t s, const FiberItem* d_items, int nitems, int total_tiles, int KKmax, int NNmax,
+                            double* d_norm_partials);      // throws on a shape that is not covered
 bool launch_mfma_gram32(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks, int KKmax);  // tiles of 64 fibers; writes 4 partials per chunk
 bool launch_mfma_gram64(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks, int KKmax);  // 32 < KK <= 64 (kernels_chi64.hip): ONE partial per chunk
 // fused (X x_r M) then Gram with Y: tiles of 64 fibers = (s:2) x (first row leg: 32); writes 4 partials per chunk

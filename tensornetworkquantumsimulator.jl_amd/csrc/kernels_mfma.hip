@@ -8,6 +8,7 @@
 // k = t + 16*h, so every lane reads 16 CONSECUTIVE floats of its operand row from LDS (4 x ds_read_b128).
 #include "kernels.hpp"
 #include "mfma_common.hpp"
+#include <stdexcept>
 #include <type_traits>
 #include "launch_util.hpp"
 
@@ -197,22 +198,17 @@ template <int KB, int NB> static size_t fiber_lds() {
     return (size_t)(4 * 2 * 32 * (CP + 1) + 2 * NNP * (KKP + 1)) * sizeof(float);
 }
 int mfma_fiber_tile_rows(int KK, int NN) { return (KK <= 64 && NN <= 64) ? 32 : 0; }
-// returns false if the shape is not covered (caller falls back to the generic kernel)
-bool launch_mfma_fiber_gemm(hipStream_t s, const FiberItem* d_items, int nitems, int total_tiles, int KKmax, int NNmax,
+void launch_mfma_fiber_gemm(hipStream_t s, const FiberItem* d_items, int nitems, int total_tiles, int KKmax, int NNmax,
                             double* d_norm_partials) {
-    if (total_tiles <= 0) return true;
+    if (total_tiles <= 0) return;
     if (KKmax <= 32 && NNmax <= 32) {
         const size_t lds = fiber_lds<1, 1>();
         hipLaunchKernelGGL((mfma_fiber_gemm_w_kernel<1, 1, 8>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
-        return true;
-    }
-    if (KKmax <= 64 && NNmax <= 64) {
+    } else if (KKmax <= 64 && NNmax <= 64) {
         const size_t lds = fiber_lds<2, 2>();
         set_max_dynamic_lds((const void*)mfma_fiber_gemm_w_kernel<2, 2, 16>, (size_t)lds);
         hipLaunchKernelGGL((mfma_fiber_gemm_w_kernel<2, 2, 16>), dim3(total_tiles), dim3(256), lds, s, d_items, nitems, d_norm_partials); TNQS_CHECK_LAUNCH();
-        return true;
-    }
-    return false;
+    } else throw std::runtime_error("launch_mfma_fiber_gemm: shape not covered");
 }
 
 // ------------------------------------------------------------------------------------------------------------
