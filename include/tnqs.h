@@ -161,6 +161,20 @@ int tnqs_truncate(tnqs_handle h, int maxdim, double cutoff, int normalize_tensor
  * expect = tr(op rho)/tr(rho), op[s',s] column-major complex128. */
 int tnqs_rdm_1site(tnqs_handle h, int v, double* out_rho);
 int tnqs_expect_1site(tnqs_handle h, int v, const double* op, double* out_re_im);
+/* Two-site reduced density matrices of bonds in one call (the reference's reduced_density_matrix(cache, [u, v]; alg = "bp") for adjacent u, v).  For request i = (u, v):
+ *   rho[s_u, s_v ; s_u', s_v'] = sum_{a, a'} E_u[(s_u, a), (s_u', a')] E_v[(s_v, a), (s_v', a')],
+ *   E_u[(s, a), (s', a')] = sum_rest (psi_u x_{k != v} m_{k -> u})[s, a, rest] conj(psi_u[s', a', rest]),
+ * un-normalised (pending scale factors of the site tensors included, as in tnqs_rdm_1site), with the site dimensions the handle has NOW (1 for a projected vertex).
+ * out_rho: the requests' (d_u d_v)^2 complex128 matrices one after the other, column-major, the FIRST listed vertex most significant (row = s_v + d_v s_u, column
+ * likewise), so <O_u O_v> = tr(kron(O_u, O_v) rho) / tr(rho) with the gate convention above.  edge_u == NULL or edge_v == NULL: every edge in tnqs_create order as
+ * (src, dst), n_edges is not read then; an empty call passes lists with n_edges = 0.  Both orientations and repeats are allowed: (v, u) returns the index-swapped matrix
+ * of (u, v), a repeated request is answered again.  The handle is not changed apart from deferred one-site gates being applied first (as tnqs_rdm_1site does).
+ * All ends of all distinct bonds are contracted in batches whose chain workspace stays under min(2 GiB, a quarter of the free device memory) -- a single end that needs
+ * more runs alone -- and the call ends with one read-back.  ComplexF32 handles: ends with 8 <= d chi <= 64 accumulate in f32 inside a chunk on the matrix cores (the BP
+ * message Gram's arithmetic), everything else (smaller, larger, or a bond whose other end is outside that range) in f64 on the generic kernel; chunks and the bond are
+ * summed in f64.  TNQS_ERR_INVALID: a pair that is not an edge, a bad vertex; TNQS_ERR_UNSUPPORTED: sharded handles, (d_u^2 + d_v^2) chi beyond the bond kernel's LDS
+ * (about 4096), d chi beyond the generic Gram kernel's. */
+int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_rho);
 /* all-vertex <op_v>: ops is nv consecutive d x d matrices; out is nv complex128 */
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out_re_im);
 
@@ -272,7 +286,10 @@ enum { TNQS_PROF_BP_MODEPROD = 0, TNQS_PROF_BP_GRAM = 1, TNQS_PROF_GATE_MODEPROD
         * sweeps) and of the batches of two-site gates (launches = batches) -- the kernel classes above overlap each other where a phase runs on two streams */
        TNQS_PROF_PHASE_BP_UPDATE = 10, TNQS_PROF_PHASE_GATE_BATCH = 11,
        /* every launch of tnqs_loop_weights; flops: 8 m n k per complex product of the batched GEMM */
-       TNQS_PROF_LOOP = 12, TNQS_PROF_NCLASSES = 13 };
+       TNQS_PROF_LOOP = 12,
+       /* the bond-contraction kernel of tnqs_rdm_edges (its chains and Grams are booked under TNQS_PROF_SMALL, as the one-site probe's); bytes: Gram partials read + matrices
+        * written, flops: 8 chi^2 (d_u d_v)^2 per bond */
+       TNQS_PROF_EDGE_RDM = 13, TNQS_PROF_NCLASSES = 14 };
 int tnqs_profile_enable(tnqs_handle h, int on);
 /* launches, total ms, algorithmic bytes (min traffic: operands read once + result written once) and flops */
 int tnqs_profile_get(tnqs_handle h, int cls, int64_t* launches, double* total_ms, double* alg_bytes, double* alg_flops);

@@ -145,6 +145,17 @@ int tnqs_dbg_symg_finish(int dtype, int nitems, const int* n, const void* USigma
 int tnqs_dbg_diag(int dtype, int nitems, const int* chi, const double* S, void* out, int guard);
 /* cscale_kernel<T>: dst_i = src_i (re[i] + i im[i]), len[i] numbers per item (any length) */
 int tnqs_dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard);
+/* ---- two-site reduced density matrices of bonds (csrc/kernels_rdm.hip, csrc/engine_rdm.cpp) ----
+ * edge_rdm_kernel<P>, ONE launch over nitems bonds (ptype 0: P = float, 1: P = double): partial_u / partial_v hold the items' Gram partials one after the other, item i's
+ * as nchunks_x[i] chunks of (d_x[i] chi[i])^2 complex numbers [chunk][(s + d a) + d chi (s' + d a')]; scale_u[i], scale_v[i]: the pending scale factors, 0 hands the kernel
+ * a null pointer (no factor pending).  out (complex128): `guard` elements, item 0 ((du dv)^2 elements), `guard` elements, item 1, ..., `guard` elements -- it goes to the device
+ * as the caller filled it and comes back whole.  An item the kernel's LDS does not hold: TNQS_ERR_UNSUPPORTED, nothing is written */
+int tnqs_dbg_edge_rdm(int ptype /*0 float, 1 double*/, int nitems, const int* du, const int* dv, const int* chi,
+                      const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
+                      const double* scale_u, const double* scale_v, void* out, int guard);
+/* tnqs_rdm_edges with the bound on a batch's chain workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of ends it ran */
+int tnqs_dbg_rdm_edges_ws(tnqs_handle h, int n_edges, const int32_t* eu, const int32_t* ev, double* out,
+                          int64_t workspace_bytes, int* nbatches_out);
 /* the pending real scale factor of the site tensor of v (a normalising gate only records 1/||psi_v||; the tensor the reference holds is the stored one times it): 1 when none is pending */
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor);
 #ifdef __cplusplus

@@ -8,6 +8,7 @@ reference repo):
   apply_gates / apply_circuit                                            src/Apply/apply_gates.jl:17-98,145
   truncate(bpc; maxdim, cutoff, edge_color, normalize_tensors)           src/truncate.jl:12-38
   expect(bpc, (op, [v]))                                                  src/expect.jl:54-82,114-121
+  rdm(bpc, [u, v]) / rdm_edges / expect_edges (adjacent u, v)             src/rdm.jl:52-73 (reduced_density_matrix, alg = "bp")
   maxvirtualdim                                                           src/TensorNetworks/abstracttensornetwork.jl:27-29
   sample(psi, nsamples; alg = "bp")                                       src/sampling.jl:3-46
   norm_sqr / norm (alg = "bp", "loopcorrections"), loopcorrected_partitionfunction   src/norm_sqr.jl:10-18,62-78, src/MessagePassing/loopcorrection.jl:3-14
@@ -476,8 +477,73 @@ def truncate(bpc, maxdim: int, cutoff: Optional[float] = None, edge_color=True,
     return out
 
 
+def _rdm_edges_raw(bpc: BeliefPropagationCache, edges) -> Tuple[list, List[np.ndarray]]:
+    """tnqs_rdm_edges: the un-normalised (d_u d_v) x (d_u d_v) matrices of `edges` (None: every edge of the graph) in request order, one device call"""
+    g = bpc.graph
+    req = list(g.edges) if edges is None else [tuple(e) for e in edges]
+    for e in req:
+        if len(e) != 2 or e[0] not in g.index or e[1] not in g.index or e[1] not in g.neighbors(e[0]):
+            raise L.TnqsArgumentError(f"{e!r} is not an edge of the graph: only single vertices and bonds are supported")
+    dim: Dict = {}
+    for e in req:
+        for v in e:
+            if v not in dim:
+                dim[v] = bpc._site_dim(v)
+    sizes = [(dim[a] * dim[b]) ** 2 for (a, b) in req]
+    out = np.zeros(sum(sizes), dtype=np.complex128)
+    if edges is None:
+        up, vp = None, None
+    else:
+        _u, up = L.i32([g.index[a] for (a, b) in req] or [0])
+        _v, vp = L.i32([g.index[b] for (a, b) in req] or [0])
+    L.check(L.lib.tnqs_rdm_edges(bpc._h, len(req), up, vp, out.ctypes.data_as(C.POINTER(C.c_double))))
+    mats, off = [], 0
+    for (a, b), n in zip(req, sizes):
+        dd = dim[a] * dim[b]
+        mats.append(np.ascontiguousarray(out[off:off + n].reshape(dd, dd, order="F")))
+        off += n
+    return req, mats
+
+
+def rdm_edges(bpc: BeliefPropagationCache, edges=None, normalize: bool = True) -> Dict:
+    """two-site reduced density matrices of bonds from the BP environment, all in one device call (reduced_density_matrix(cache, [u, v]; alg = "bp") of the
+    reference for adjacent u, v): {(u, v): rho} with rho[s_v + d_v s_u, s_v' + d_v s_u'] -- the first vertex most significant, so that
+    tr(np.kron(O_u, O_v) @ rho) is <O_u O_v> of a normalised rho.  edges = None: every edge of the graph; (v, u) gives the index-swapped matrix of (u, v)"""
+    req, mats = _rdm_edges_raw(bpc, edges)
+    return {e: (m / np.trace(m) if normalize else m) for e, m in zip(req, mats)}
+
+
+def expect_edges(bpc: BeliefPropagationCache, op, edges=None) -> np.ndarray:
+    """<O_u O_v> = tr(op rho_uv) / tr(rho_uv) for every listed bond (None: every edge of the graph, in its order) from ONE device call; `op`: a two-character
+    Pauli string ("ZZ"), a pair of d x d matrices (O_u, O_v), or one (d_u d_v) x (d_u d_v) matrix with the first vertex most significant.  The operator is
+    applied on the host"""
+    if isinstance(op, str):
+        if len(op) != 2:
+            raise L.TnqsArgumentError("expect_edges: a string observable names one operator per vertex of the bond (two characters)")
+        full = np.kron(gate_matrix(op[0]), gate_matrix(op[1]))
+    elif isinstance(op, (tuple, list)) or (isinstance(op, np.ndarray) and op.ndim == 3):
+        if len(op) != 2:
+            raise L.TnqsArgumentError("expect_edges: a pair of one-site operators is expected")
+        full = np.kron(np.asarray(op[0]), np.asarray(op[1]))
+    else:
+        full = np.asarray(op)
+    full = np.asarray(full, dtype=np.complex128)
+    req, mats = _rdm_edges_raw(bpc, edges)
+    out = np.zeros(len(req), dtype=np.complex128)
+    for i, (e, m) in enumerate(zip(req, mats)):
+        if full.shape != m.shape:
+            raise L.TnqsArgumentError(f"expect_edges: operator of shape {full.shape} on bond {e!r} of dimension {m.shape[0]}")
+        out[i] = np.sum(full * m.T) / np.trace(m)
+    return out
+
+
 def rdm(bpc: BeliefPropagationCache, v) -> np.ndarray:
-    """normalised single-site reduced density matrix rho[s, s'] from the BP environment"""
+    """normalised reduced density matrix from the BP environment: rho[s, s'] of a vertex, or -- for a list [u, v] of two adjacent vertices -- the two-site
+    matrix of that bond (rdm_edges)"""
+    if isinstance(v, list):
+        if len(v) != 2 or v[0] not in bpc.graph.index or v[1] not in bpc.graph.index or v[1] not in bpc.graph.neighbors(v[0]):
+            raise L.TnqsArgumentError(f"rdm: only single vertices and bonds (two adjacent vertices) are supported, got {v!r}")
+        return rdm_edges(bpc, [tuple(v)])[tuple(v)]
     d = bpc._site_dim(v)
     out = np.zeros((d, d), dtype=np.complex128, order="F")
     L.check(L.lib.tnqs_rdm_1site(bpc._h, bpc.graph.index[v], out.ctypes.data_as(C.POINTER(C.c_double))))
@@ -869,7 +935,9 @@ PROF_CLASSES = ("bp_modeprod", "bp_gram", "gate_modeprod", "gate_gram", "gate_ap
                 # whole phases on the handle's stream (critical path; the kernel classes above overlap where a phase uses two streams): launches = sweeps / batches
                 "phase_bp_update", "phase_gate_batch",
                 # every launch of tnqs_loop_weights (loopcorrected_partitionfunction); flops = 8 m n k per complex product of the batched GEMM
-                "loop")
+                "loop",
+                # the bond-contraction kernel of tnqs_rdm_edges (rdm_edges / expect_edges); its chains and Grams are booked under "small"
+                "edge_rdm")
 
 
 def profile_get(bpc: BeliefPropagationCache) -> dict:

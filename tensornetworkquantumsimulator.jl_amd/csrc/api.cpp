@@ -135,6 +135,9 @@ int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uin
 int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im) {
     return guard([&] { loop_weights(S(h), ncycles, cycle_len, cycle_verts, out_re_im); });
 }
+int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_rho) {
+    return guard([&] { rdm_edges(S(h), n_edges, edge_u, edge_v, out_rho); });
+}
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out) {
     return guard([&] { if (!ops || !out) throw Err(TNQS_ERR_INVALID, "expect_all: null"); expect_all(S(h), ops, out); });
 }
@@ -228,6 +231,8 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                  void dbg_symg_finish(int dtype, int nitems, const int* n, const void* USigma, const void* Vsvd, const void* irx, const void* iry, void* Xs, void* Xd, double* S, int guard);
                  void dbg_diag(int dtype, int nitems, const int* chi, const double* S, void* out, int guard);
                  void dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard);
+                 void dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
+                                   const double* scale_u, const double* scale_v, void* out, int guard);
                  double dbg_pending_scale(State* s, int v); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
@@ -329,6 +334,14 @@ int tnqs_dbg_symg_finish(int dtype, int nitems, const int* n, const void* USigma
 int tnqs_dbg_diag(int dtype, int nitems, const int* chi, const double* S, void* out, int guard_elems) { return guard([&] { dbg_diag(dtype, nitems, chi, S, out, guard_elems); }); }
 int tnqs_dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard_elems) {
     return guard([&] { dbg_cscale(dtype, nitems, len, src, re, im, dst, guard_elems); });
+}
+int tnqs_dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
+                      const double* scale_u, const double* scale_v, void* out, int guard_elems) {
+    return guard([&] { dbg_edge_rdm(ptype, nitems, du, dv, chi, nchunks_u, nchunks_v, partial_u, partial_v, scale_u, scale_v, out, guard_elems); });
+}
+int tnqs_dbg_rdm_edges_ws(tnqs_handle h, int n_edges, const int32_t* eu, const int32_t* ev, double* out, int64_t workspace_bytes, int* nbatches_out) {
+    return guard([&] { if (workspace_bytes < 1) throw Err(TNQS_ERR_INVALID, "dbg_rdm_edges_ws: the workspace bound must be positive");
+                       rdm_edges(S(h), n_edges, eu, ev, out, (size_t)workspace_bytes, nbatches_out); });
 }
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor) { return guard([&] { if (!factor) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: null output"); *factor = dbg_pending_scale(S(h), v); }); }
 }

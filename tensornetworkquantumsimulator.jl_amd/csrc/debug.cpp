@@ -1025,6 +1025,35 @@ void dbg_cscale(int dtype, int nitems, const int* len, const void* src, const do
     HIPCHK(hipDeviceSynchronize());
     gD.down(dst, "dst");
 }
+// edge_rdm_kernel<P> (kernels_rdm.hip), ONE launch over nitems bonds set up as engine_rdm.cpp sets them up: the items' Gram partials one after the other in partial_u /
+// partial_v (P numbers), scale_u / scale_v one double per item (0: a null pointer), out between guard bands of `guard` complex128 elements
+void dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
+                  const double* scale_u, const double* scale_v, void* out, int guard) {
+    need_gpu();
+    if ((ptype != 0 && ptype != 1) || nitems < 1 || !du || !dv || !chi || !nchunks_u || !nchunks_v || !partial_u || !partial_v || !scale_u || !scale_v || !out || guard < 0)
+        throw Err(TNQS_ERR_INVALID, "dbg_edge_rdm: bad arguments");
+    const size_t psz = ptype == 0 ? 8 : 16;
+    Slots sU, sV, sS; Guarded gO((size_t)guard * 16);
+    for (int i = 0; i < nitems; ++i) {
+        if (du[i] < 1 || dv[i] < 1 || chi[i] < 1 || nchunks_u[i] < 1 || nchunks_v[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_edge_rdm: dimensions and chunk counts >= 1");
+        if (edge_rdm_block(du[i], dv[i], chi[i]) < 1) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_edge_rdm: bond too large for the edge kernel");
+        const size_t ku = (size_t)du[i] * chi[i], kv = (size_t)dv[i] * chi[i], dd = (size_t)du[i] * dv[i];
+        sU.add((size_t)nchunks_u[i] * ku * ku * psz); sV.add((size_t)nchunks_v[i] * kv * kv * psz); sS.add(16); gO.add(dd * dd * 16);
+    }
+    sU.alloc(); sV.alloc(); sS.alloc(); gO.alloc();
+    put_all(sU, partial_u); put_all(sV, partial_v);
+    std::vector<EdgeRdmItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        const double f[2] = {scale_u[i], scale_v[i]}; sS.put(i, f);
+        items[i] = EdgeRdmItem{sU.at(i), sV.at(i), nchunks_u[i], nchunks_v[i], du[i], dv[i], chi[i],
+                               f[0] != 0.0 ? reinterpret_cast<const double*>(sS.at(i)) : nullptr, f[1] != 0.0 ? reinterpret_cast<const double*>(sS.at(i)) + 1 : nullptr, gO.at(i)};
+    }
+    DBuf dI(sizeof(EdgeRdmItem) * nitems);
+    sU.up(); sV.up(); sS.up(); gO.up(out); dI.up(items.data(), sizeof(EdgeRdmItem) * nitems);
+    if (ptype == 0) launch_edge_rdm<float>(nullptr, (const EdgeRdmItem*)dI.p, nitems); else launch_edge_rdm<double>(nullptr, (const EdgeRdmItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gO.down(out, "out");
+}
 // the pending real scale factor of site v (State::sscale): 1 when none is pending
 double dbg_pending_scale(State* s, int v) {
     if (v < 0 || v >= s->g->nv) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: bad vertex");

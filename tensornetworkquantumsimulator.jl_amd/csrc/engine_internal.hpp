@@ -10,6 +10,7 @@
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
 //   engine_loops.cpp  loop corrections: transfer matrices of simple cycles, ring products, traces (batched)
+//   engine_rdm.cpp    two-site reduced density matrices of bonds (batched chains + Grams, one contraction kernel)
 //   sharding.cpp      exchange step (RCCL or host callback)
 // and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
@@ -20,6 +21,7 @@
 //   kernels_chol.hip   Cholesky (square / packed), env prepare / finish  kernels_f64.hip    ComplexF64 on the f64 matrix cores
 //   kernels_theta.hip  per-gate small algebra: gate_eigs .. gate_finish  kernels_sample.hip sampling
 //   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, antiprojector, trace
+//   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs)
 #pragma once
 #include "engine.hpp"
 #include "kernels.hpp"

@@ -328,6 +328,20 @@ template <class T> void launch_loop_antiproject(hipStream_t s, const LoopProjIte
 struct LoopTraceItem { const void* X; const void* Y; int p, q; double* partial; double* out; int wg_begin, nwg; };
 int plan_loop_trace(LoopTraceItem* it, int n);
 template <class T> void launch_loop_trace(hipStream_t s, const LoopTraceItem* d_items, int nitems, int total_wgs);
+// two-site reduced density matrix of a bond (kernels_rdm.hip) from the Gram partials of its two ends, partial_x[chunk][i + KK_x j] with i = s + d_x a,
+// j = s' + d_x a', KK_x = d_x chi (type P, as run_grams leaves them):
+//   out[(s_v + d_v s_u) + d_u d_v (s_v' + d_v s_u')] = (*scale_u)^2 (*scale_v)^2 sum_{a, a'} E_u[(s_u, a), (s_u', a')] E_v[(s_v, a), (s_v', a')],  E_x = sum of x's chunks
+// (complex128, f64 throughout; a null scale pointer = 1).  One workgroup per item; no item touches another's output.
+struct EdgeRdmItem { const void* partial_u; const void* partial_v; int nchunks_u, nchunks_v; int du, dv, chi; const double* scale_u; const double* scale_v; void* out; };
+constexpr int kEdgeRdmLds = 64 * 1024;      // LDS of a workgroup: 4 accumulators per output entry, then a block of bra bond indices of both ends' E (complex128)
+// bra bond indices a' per block (0: the bond does not fit -- d_u d_v > 32 or (d_u^2 + d_v^2) chi > 4096 - 4 (d_u d_v)^2)
+__host__ __device__ inline int edge_rdm_block(int du, int dv, int chi) {
+    const long long acc = 64ll * du * dv * du * dv, per = 16ll * ((long long)du * du + (long long)dv * dv) * chi;
+    if (acc >= kEdgeRdmLds) return 0;
+    const long long nb = (kEdgeRdmLds - acc) / per;
+    return (int)(nb < chi ? nb : chi);
+}
+template <class P> void launch_edge_rdm(hipStream_t s, const EdgeRdmItem* d_items, int nitems);      // every item must have edge_rdm_block() >= 1
 // one-site gates on d = 2, ComplexF32: streaming 2x2 apply, norm partials [item][nbx]
 void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int nbx, double* d_norm_partials);
 
