@@ -175,6 +175,19 @@ int tnqs_expect_1site(tnqs_handle h, int v, const double* op, double* out_re_im)
  * summed in f64.  TNQS_ERR_INVALID: a pair that is not an edge, a bad vertex; TNQS_ERR_UNSUPPORTED: sharded handles, (d_u^2 + d_v^2) chi beyond the bond kernel's LDS
  * (about 4096), d chi beyond the generic Gram kernel's. */
 int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_rho);
+/* two-site density matrices of the ends of paths (reduced_density_matrix(cache, [u, w]; alg = "bp"), src/rdm.jl:52-73, with the path as the Steiner tree):
+ * path q has path_len[q] >= 2 vertices, listed one after the other in path_verts; out_rho receives, for q = 0.., for k = 1 .. path_len[q]-1, the
+ * un-normalised (d_p0 d_pk)^2 complex128 matrix of (p_0, p_k) in the layout of tnqs_rdm_edges */
+/* With E as in tnqs_rdm_edges and T_k[(b, b'), (a, a')] the double-layer transfer matrix of the inner vertex p_k (messages of every leg off the path absorbed):
+ *   L_0 = E_{p_0 -> p_1},  L_k[s, s'; b, b'] = sum_{a, a'} L_{k-1}[s, s'; a, a'] T_k[(b, b'), (a, a')],  rho_{p_0, p_k} = sum_{a, a'} L_{k-1}[s_u, s_u'; a, a'] E_{p_k -> p_{k-1}}[(s_w, a), (s_w', a')]
+ * -- one path gives the matrix of (p_0, p_k) for every k; k = 1 is the bond's matrix of tnqs_rdm_edges.  L is complex128 with f64 accumulation from the first step on,
+ * whatever the handle's type; it is NOT rescaled along the path (f64 range).  Paths must be INDUCED (no two non-consecutive vertices adjacent: the reference contracts the
+ * induced region, so a chord is an argument error, not another answer; a shortest path is always induced).  Paths are taken in order in batches whose workspace stays under
+ * min(2 GiB, a quarter of the free device memory) -- a path that needs more runs alone; ends and transfer matrices that several paths of a batch share are built once -- and
+ * the call ends with one read-back.  The handle is not changed apart from deferred one-site gates being applied first.  npaths = 0 is a no-op.
+ * TNQS_ERR_INVALID (before any device work): a bad vertex, consecutive vertices that are not adjacent, a repeated vertex, a chord, a length below 2, a null output;
+ * TNQS_ERR_UNSUPPORTED: sharded handles, an inner vertex of degree above 7, chi_a^2 chi_b^2 above INT_MAX / 4, a bond beyond the edge kernel's LDS, d_p0 above 4. */
+int tnqs_rdm_paths(tnqs_handle h, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out_rho);
 /* all-vertex <op_v>: ops is nv consecutive d x d matrices; out is nv complex128 */
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out_re_im);
 
@@ -289,7 +302,10 @@ enum { TNQS_PROF_BP_MODEPROD = 0, TNQS_PROF_BP_GRAM = 1, TNQS_PROF_GATE_MODEPROD
        TNQS_PROF_LOOP = 12,
        /* the bond-contraction kernel of tnqs_rdm_edges (its chains and Grams are booked under TNQS_PROF_SMALL, as the one-site probe's); bytes: Gram partials read + matrices
         * written, flops: 8 chi^2 (d_u d_v)^2 per bond */
-       TNQS_PROF_EDGE_RDM = 13, TNQS_PROF_NCLASSES = 14 };
+       TNQS_PROF_EDGE_RDM = 13,
+       /* the apply kernel and the bond contractions of tnqs_rdm_paths (its transfer matrices are booked under TNQS_PROF_LOOP, its chains and Grams under TNQS_PROF_SMALL);
+        * bytes: T read + L read + L written / partials read + matrices written, flops: 8 d^2 chi_a^2 chi_b^2 per step, 8 chi^2 (d_u d_w)^2 per pair */
+       TNQS_PROF_PATH_RDM = 14, TNQS_PROF_NCLASSES = 15 };
 int tnqs_profile_enable(tnqs_handle h, int on);
 /* launches, total ms, algorithmic bytes (min traffic: operands read once + result written once) and flops */
 int tnqs_profile_get(tnqs_handle h, int cls, int64_t* launches, double* total_ms, double* alg_bytes, double* alg_flops);

@@ -153,6 +153,22 @@ int tnqs_dbg_cscale(int dtype, int nitems, const int* len, const void* src, cons
 int tnqs_dbg_edge_rdm(int ptype /*0 float, 1 double*/, int nitems, const int* du, const int* dv, const int* chi,
                       const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
                       const double* scale_u, const double* scale_v, void* out, int guard);
+/* the same kernel with one partial type per end: edge_rdm_kernel<Pu, Pv> (tnqs_rdm_paths contracts a carried environment, double, with an end's Gram partial) */
+int tnqs_dbg_edge_rdm_mixed(int ptype_u /*0 float, 1 double*/, int ptype_v, int nitems, const int* du, const int* dv, const int* chi,
+                            const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
+                            const double* scale_u, const double* scale_v, void* out, int guard);
+/* path_apply_kernel<P, T>, ONE launch over nitems items: L_out_i = scale_i^2 L_in_i T_i with L_in_i the sum of nchunks_in[i] chunks of (d chi_a)^2 numbers of type P
+ * [chunk][(s + d a) + d chi_a (s' + d a')], T_i a chi_b^2 x chi_a^2 matrix of the state's type T[(b + chi_b b') + chi_b^2 (a + chi_a a')]; items one after the other in
+ * L_in and T; scale[i] = 0 hands the kernel a null pointer.  L_out (complex128) is laid out as guard, item 0 (ksplit[0] chunks of (d chi_b)^2 complex128), guard, item 1, ...,
+ * guard; it goes up as the caller filled it and comes back whole.  ksplit[i] = 0 means "as plan_path_apply chooses" (size L_out by tnqs_dbg_path_apply_plan).
+ * d[i]^2 > 16: TNQS_ERR_UNSUPPORTED, nothing is written */
+int tnqs_dbg_path_apply(int ptype_in /*0 float, 1 double*/, int dtype /*0 c64, 1 c128*/, int nitems, const int* d, const int* chi_a, const int* chi_b,
+                        const int* nchunks_in, const int* ksplit, const void* L_in, const void* T, const double* scale /*0: null*/, void* L_out, int guard);
+/* plan_path_apply on a launch of nitems items (host only): ksplit_out[i] = the column ranges item i gets (ksplit[i] where that is > 0), nrb_out[i] its row blocks */
+int tnqs_dbg_path_apply_plan(int nitems, const int* chi_a, const int* chi_b, const int* ksplit, int* ksplit_out, int* nrb_out);
+/* tnqs_rdm_paths with the bound on a batch's workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of paths it ran */
+int tnqs_dbg_rdm_paths_ws(tnqs_handle h, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out,
+                          int64_t workspace_bytes, int* nbatches_out);
 /* tnqs_rdm_edges with the bound on a batch's chain workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of ends it ran */
 int tnqs_dbg_rdm_edges_ws(tnqs_handle h, int n_edges, const int32_t* eu, const int32_t* ev, double* out,
                           int64_t workspace_bytes, int* nbatches_out);

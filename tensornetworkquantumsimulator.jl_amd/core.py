@@ -9,6 +9,7 @@ reference repo):
   truncate(bpc; maxdim, cutoff, edge_color, normalize_tensors)           src/truncate.jl:12-38
   expect(bpc, (op, [v]))                                                  src/expect.jl:54-82,114-121
   rdm(bpc, [u, v]) / rdm_edges / expect_edges (adjacent u, v)             src/rdm.jl:52-73 (reduced_density_matrix, alg = "bp")
+  rdm_paths / rdm_pairs / expect_pairs / correlation_function (any u, w)  src/rdm.jl:52-73 with the path from u to w as the Steiner tree
   maxvirtualdim                                                           src/TensorNetworks/abstracttensornetwork.jl:27-29
   sample(psi, nsamples; alg = "bp")                                       src/sampling.jl:3-46
   norm_sqr / norm (alg = "bp", "loopcorrections"), loopcorrected_partitionfunction   src/norm_sqr.jl:10-18,62-78, src/MessagePassing/loopcorrection.jl:3-14
@@ -513,27 +514,213 @@ def rdm_edges(bpc: BeliefPropagationCache, edges=None, normalize: bool = True) -
     return {e: (m / np.trace(m) if normalize else m) for e, m in zip(req, mats)}
 
 
+def _two_site_operator(op, who: str) -> np.ndarray:
+    """the (d_u d_v) x (d_u d_v) complex128 matrix of a two-site observable, first vertex most significant: a two-character Pauli string ("ZZ"), a pair of one-site
+    matrices (O_u, O_v), or the full matrix itself"""
+    if isinstance(op, str):
+        if len(op) != 2:
+            raise L.TnqsArgumentError(f"{who}: a string observable names one operator per vertex of the bond (two characters)")
+        full = np.kron(gate_matrix(op[0]), gate_matrix(op[1]))
+    elif isinstance(op, (tuple, list)) or (isinstance(op, np.ndarray) and op.ndim == 3):
+        if len(op) != 2:
+            raise L.TnqsArgumentError(f"{who}: a pair of one-site operators is expected")
+        full = np.kron(np.asarray(op[0]), np.asarray(op[1]))
+    else:
+        full = np.asarray(op)
+    return np.asarray(full, dtype=np.complex128)
+
+
 def expect_edges(bpc: BeliefPropagationCache, op, edges=None) -> np.ndarray:
     """<O_u O_v> = tr(op rho_uv) / tr(rho_uv) for every listed bond (None: every edge of the graph, in its order) from ONE device call; `op`: a two-character
     Pauli string ("ZZ"), a pair of d x d matrices (O_u, O_v), or one (d_u d_v) x (d_u d_v) matrix with the first vertex most significant.  The operator is
     applied on the host"""
-    if isinstance(op, str):
-        if len(op) != 2:
-            raise L.TnqsArgumentError("expect_edges: a string observable names one operator per vertex of the bond (two characters)")
-        full = np.kron(gate_matrix(op[0]), gate_matrix(op[1]))
-    elif isinstance(op, (tuple, list)) or (isinstance(op, np.ndarray) and op.ndim == 3):
-        if len(op) != 2:
-            raise L.TnqsArgumentError("expect_edges: a pair of one-site operators is expected")
-        full = np.kron(np.asarray(op[0]), np.asarray(op[1]))
-    else:
-        full = np.asarray(op)
-    full = np.asarray(full, dtype=np.complex128)
+    full = _two_site_operator(op, "expect_edges")
     req, mats = _rdm_edges_raw(bpc, edges)
     out = np.zeros(len(req), dtype=np.complex128)
     for i, (e, m) in enumerate(zip(req, mats)):
         if full.shape != m.shape:
             raise L.TnqsArgumentError(f"expect_edges: operator of shape {full.shape} on bond {e!r} of dimension {m.shape[0]}")
         out[i] = np.sum(full * m.T) / np.trace(m)
+    return out
+
+
+# ---- two-site density matrices of distant vertices: the two ENDS of a path (tnqs_rdm_paths) ----------------------------------------------------
+def _check_path(g, path) -> list:
+    """an induced path of the graph as a list of vertices, or TnqsArgumentError: the reference contracts the INDUCED region of the path's vertices, so a chord would be
+    summed over -- a different quantity, refused rather than answered"""
+    path = list(path)
+    if len(path) < 2:
+        raise L.TnqsArgumentError(f"rdm_paths: a path has at least two vertices, got {path!r}")
+    for v in path:
+        if v not in g.index:
+            raise L.TnqsArgumentError(f"rdm_paths: {v!r} is not a vertex of the graph")
+    if len(set(path)) != len(path):
+        raise L.TnqsArgumentError(f"rdm_paths: repeated vertex in the path {path!r}")
+    nb = [set(g.neighbors(v)) for v in path]
+    for k in range(len(path) - 1):
+        if path[k + 1] not in nb[k]:
+            raise L.TnqsArgumentError(f"rdm_paths: not a path: {path[k]!r} and {path[k + 1]!r} are not adjacent")
+    for k in range(len(path)):
+        for q in range(k + 2, len(path)):
+            if path[q] in nb[k]:
+                raise L.TnqsArgumentError(f"rdm_paths: the path has a chord ({path[k]!r} and {path[q]!r} are adjacent): only induced paths are supported "
+                                          "(a shortest path is always induced)")
+    return path
+
+
+def _rdm_paths_raw(bpc: BeliefPropagationCache, paths) -> List[List[np.ndarray]]:
+    """tnqs_rdm_paths: for every path, the un-normalised (d_p0 d_pk) x (d_p0 d_pk) matrices of (p_0, p_k), k = 1 .. len - 1; one device call"""
+    g = bpc.graph
+    paths = [_check_path(g, p) for p in paths]
+    if not paths:
+        return []
+    dim: Dict = {}
+    for p in paths:
+        for v in p:
+            if v not in dim:
+                dim[v] = bpc._site_dim(v)
+    sizes = [[(dim[p[0]] * dim[w]) ** 2 for w in p[1:]] for p in paths]
+    out = np.zeros(sum(sum(sz) for sz in sizes), dtype=np.complex128)
+    _l, lp = L.i32([len(p) for p in paths])
+    _v, vp = L.i32([g.index[v] for p in paths for v in p])
+    L.check(L.lib.tnqs_rdm_paths(bpc._h, len(paths), lp, vp, out.ctypes.data_as(C.POINTER(C.c_double))))
+    res, off = [], 0
+    for p, sz in zip(paths, sizes):
+        mats = []
+        for w, n in zip(p[1:], sz):
+            dd = dim[p[0]] * dim[w]
+            mats.append(np.ascontiguousarray(out[off:off + n].reshape(dd, dd, order="F")))
+            off += n
+        res.append(mats)
+    return res
+
+
+def _checked_trace(m: np.ndarray, pair) -> complex:
+    t = np.trace(m)
+    if t == 0 or not np.isfinite(t):
+        raise L.TnqsDomainError(f"rdm_paths: the density matrix of {pair!r} has trace {t!r}: the environment carried along the path left the range of float64 "
+                                "(it is not rescaled along the path)")
+    return t
+
+
+def rdm_paths(bpc: BeliefPropagationCache, paths, normalize: bool = True) -> List[Dict]:
+    """two-site reduced density matrices of the two ENDS of paths from the BP environment, all in one device call (reduced_density_matrix(cache, [u, w]; alg = "bp") of
+    the reference with the path as the Steiner tree): for every path p_0 .. p_n one dict {(p_0, p_k): rho, k = 1 .. n} -- a path yields the matrix of its first vertex
+    with EVERY later one -- in the layout of rdm_edges (first vertex most significant).  Paths must be induced (no two non-consecutive vertices adjacent; a shortest path
+    always is): TnqsArgumentError otherwise, before any device work.  The environment of p_0 is carried along the path in complex128 whatever the state's type, but it is
+    NOT rescaled on the way: float64's range is what it has, and a trace that comes back zero or non-finite raises TnqsDomainError naming the pair"""
+    paths = [list(p) for p in paths]
+    res = []
+    for p, mats in zip(paths, _rdm_paths_raw(bpc, paths)):
+        dct = {}
+        for w, m in zip(p[1:], mats):
+            t = _checked_trace(m, (p[0], w))
+            dct[(p[0], w)] = m / t if normalize else m
+        res.append(dct)
+    return res
+
+
+def _merge_pair_paths(paths) -> Tuple[list, list]:
+    """(merged, where): a path that is a prefix of another one of the list (same source, same first steps) rides on it -- merged holds the paths that are no such prefix,
+    where[i] = (index into merged, k) says that paths[i] ends at vertex k of that merged path.  Pure host logic"""
+    order = sorted(range(len(paths)), key=lambda i: -len(paths[i]))
+    merged, prefix_of, where = [], {}, [None] * len(paths)
+    for i in order:
+        key = tuple(paths[i])
+        if key not in prefix_of:
+            merged.append(list(paths[i]))
+            for k in range(1, len(key)):
+                prefix_of.setdefault(key[:k + 1], (len(merged) - 1, k))
+        where[i] = prefix_of[key]
+    return merged, where
+
+
+def _pair_path(g, u, w) -> list:
+    """the tree path from u to w of steiner_region(g, [u, w]): the path expect(bpc, (op, [u, w])) contracts"""
+    from .graphs import steiner_region
+    for v in (u, w):
+        if v not in g.index:
+            raise L.TnqsArgumentError(f"rdm_pairs: {v!r} is not a vertex of the graph")
+    if u == w:
+        raise L.TnqsArgumentError(f"rdm_pairs: a pair names two different vertices, got {(u, w)!r}")
+    try:
+        region, parent = steiner_region(g, [u, w])
+    except ValueError as e:
+        raise L.TnqsArgumentError(str(e))
+    path, i = [], region.index(w)
+    while i >= 0:
+        path.append(region[i]); i = parent[i]
+    return path[::-1]
+
+
+def _rdm_pairs_raw(bpc: BeliefPropagationCache, pairs) -> Tuple[list, List[np.ndarray]]:
+    g = bpc.graph
+    pairs = [tuple(p) for p in pairs]
+    for p in pairs:
+        if len(p) != 2:
+            raise L.TnqsArgumentError(f"rdm_pairs: a pair names two vertices, got {p!r}")
+    need, seen = [], set()                       # pairs that get a path: (w, u) listed after (u, w) is the index swap of it
+    for (u, w) in pairs:
+        if (u, w) not in seen and (w, u) not in seen:
+            need.append((u, w))
+        seen.add((u, w))
+    merged, where = _merge_pair_paths([_pair_path(g, u, w) for (u, w) in need])
+    raw = _rdm_paths_raw(bpc, merged)
+    have = {pr: raw[j][k - 1] for pr, (j, k) in zip(need, where)}
+    mats = []
+    for (u, w) in pairs:
+        if (u, w) in have:
+            mats.append(have[(u, w)])
+        else:
+            m = have[(w, u)]; dw, du = bpc._site_dim(w), bpc._site_dim(u)
+            mats.append(np.ascontiguousarray(m.reshape(dw, du, dw, du).transpose(1, 0, 3, 2).reshape(du * dw, du * dw)))
+    return pairs, mats
+
+
+def rdm_pairs(bpc: BeliefPropagationCache, pairs, normalize: bool = True) -> Dict:
+    """{(u, w): rho} for arbitrary pairs of vertices from ONE device call (rdm_paths): the path of a pair is the tree path from u to w of steiner_region(g, [u, w]) -- the
+    one expect(bpc, (op, [u, w])) contracts, so the two agree.  A pair whose path is a prefix of another requested pair's path from the same source rides on it; adjacent
+    pairs are allowed; (w, u) listed after (u, w) is the index swap, done on the host"""
+    req, mats = _rdm_pairs_raw(bpc, pairs)
+    return {pr: (m / _checked_trace(m, pr) if normalize else m) for pr, m in zip(req, mats)}
+
+
+def expect_pairs(bpc: BeliefPropagationCache, op, pairs) -> np.ndarray:
+    """<O_u O_w> = tr(op rho_uw) / tr(rho_uw) for every listed pair of vertices (adjacent or not) from ONE device call; `op` as in expect_edges, applied on the host"""
+    full = _two_site_operator(op, "expect_pairs")
+    req, mats = _rdm_pairs_raw(bpc, pairs)
+    out = np.zeros(len(req), dtype=np.complex128)
+    for i, (pr, m) in enumerate(zip(req, mats)):
+        if full.shape != m.shape:
+            raise L.TnqsArgumentError(f"expect_pairs: operator of shape {full.shape} on the pair {pr!r} of dimension {m.shape[0]}")
+        out[i] = np.sum(full * m.T) / _checked_trace(m, pr)
+    return out
+
+
+def correlation_function(bpc: BeliefPropagationCache, op, path, connected: bool = False) -> np.ndarray:
+    """<O_{p0} O_{pk}>, k = 1 .. n - 1, along an induced path p_0 .. p_{n-1} from ONE device call; `op`: a pair of one-site operators (O_first, O_other) or a
+    two-character Pauli string.  connected = True subtracts <O_{p0}> <O_{pk}> taken from the partial traces of the SAME two-site matrix: no further device call, and
+    consistent by construction.  The environment is not rescaled along the path (see rdm_paths)"""
+    if isinstance(op, str):
+        if len(op) != 2:
+            raise L.TnqsArgumentError("correlation_function: a string observable names one operator per end (two characters)")
+        a, b = gate_matrix(op[0]), gate_matrix(op[1])
+    else:
+        if len(op) != 2:
+            raise L.TnqsArgumentError("correlation_function: a pair of one-site operators is expected")
+        a, b = np.asarray(op[0]), np.asarray(op[1])
+    a = np.asarray(a, dtype=np.complex128); b = np.asarray(b, dtype=np.complex128)
+    path = list(path)
+    (mats,) = _rdm_paths_raw(bpc, [path])
+    out = np.zeros(len(mats), dtype=np.complex128)
+    for k, m in enumerate(mats):
+        du, dw = a.shape[0], b.shape[0]
+        if m.shape[0] != du * dw:
+            raise L.TnqsArgumentError(f"correlation_function: operators of dimensions {du}, {dw} on the pair {(path[0], path[k + 1])!r} of dimension {m.shape[0]}")
+        r4 = (m / _checked_trace(m, (path[0], path[k + 1]))).reshape(du, dw, du, dw)
+        out[k] = np.einsum("as,bt,stab->", a, b, r4)
+        if connected:
+            out[k] -= np.einsum("as,sbab->", a, r4) * np.einsum("bt,atab->", b, r4)
     return out
 
 
@@ -937,7 +1124,10 @@ PROF_CLASSES = ("bp_modeprod", "bp_gram", "gate_modeprod", "gate_gram", "gate_ap
                 # every launch of tnqs_loop_weights (loopcorrected_partitionfunction); flops = 8 m n k per complex product of the batched GEMM
                 "loop",
                 # the bond-contraction kernel of tnqs_rdm_edges (rdm_edges / expect_edges); its chains and Grams are booked under "small"
-                "edge_rdm")
+                "edge_rdm",
+                # the apply kernel and the bond contractions of tnqs_rdm_paths (rdm_paths / rdm_pairs / expect_pairs / correlation_function); its transfer matrices
+                # are booked under "loop", its chains and Grams under "small"
+                "path_rdm")
 
 
 def profile_get(bpc: BeliefPropagationCache) -> dict:

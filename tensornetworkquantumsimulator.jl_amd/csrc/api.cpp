@@ -138,6 +138,9 @@ int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, cons
 int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_rho) {
     return guard([&] { rdm_edges(S(h), n_edges, edge_u, edge_v, out_rho); });
 }
+int tnqs_rdm_paths(tnqs_handle h, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out_rho) {
+    return guard([&] { rdm_paths(S(h), npaths, path_len, path_verts, out_rho); });
+}
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out) {
     return guard([&] { if (!ops || !out) throw Err(TNQS_ERR_INVALID, "expect_all: null"); expect_all(S(h), ops, out); });
 }
@@ -233,6 +236,10 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                  void dbg_cscale(int dtype, int nitems, const int* len, const void* src, const double* re, const double* im, void* dst, int guard);
                  void dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
                                    const double* scale_u, const double* scale_v, void* out, int guard);
+                 void dbg_edge_rdm_mixed(int ptype_u, int ptype_v, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u,
+                                         const void* partial_v, const double* scale_u, const double* scale_v, void* out, int guard);
+                 void dbg_path_apply(int ptype_in, int dtype, int nitems, const int* d, const int* chi_a, const int* chi_b, const int* nchunks_in, const int* ksplit, const void* L_in, const void* T,
+                                     const double* scale, void* L_out, int guard);
                  double dbg_pending_scale(State* s, int v); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
@@ -342,6 +349,26 @@ int tnqs_dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const
 int tnqs_dbg_rdm_edges_ws(tnqs_handle h, int n_edges, const int32_t* eu, const int32_t* ev, double* out, int64_t workspace_bytes, int* nbatches_out) {
     return guard([&] { if (workspace_bytes < 1) throw Err(TNQS_ERR_INVALID, "dbg_rdm_edges_ws: the workspace bound must be positive");
                        rdm_edges(S(h), n_edges, eu, ev, out, (size_t)workspace_bytes, nbatches_out); });
+}
+int tnqs_dbg_edge_rdm_mixed(int ptype_u, int ptype_v, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u,
+                            const void* partial_v, const double* scale_u, const double* scale_v, void* out, int guard_elems) {
+    return guard([&] { dbg_edge_rdm_mixed(ptype_u, ptype_v, nitems, du, dv, chi, nchunks_u, nchunks_v, partial_u, partial_v, scale_u, scale_v, out, guard_elems); });
+}
+int tnqs_dbg_path_apply(int ptype_in, int dtype, int nitems, const int* d, const int* chi_a, const int* chi_b, const int* nchunks_in, const int* ksplit, const void* L_in, const void* T,
+                        const double* scale, void* L_out, int guard_elems) {
+    return guard([&] { dbg_path_apply(ptype_in, dtype, nitems, d, chi_a, chi_b, nchunks_in, ksplit, L_in, T, scale, L_out, guard_elems); });
+}
+int tnqs_dbg_path_apply_plan(int nitems, const int* chi_a, const int* chi_b, const int* ksplit, int* ksplit_out, int* nrb_out) {
+    return guard([&] { if (nitems < 1 || !chi_a || !chi_b || !ksplit || !ksplit_out || !nrb_out) throw Err(TNQS_ERR_INVALID, "dbg_path_apply_plan: bad arguments");
+                       std::vector<PathApplyItem> it(nitems);
+                       for (int i = 0; i < nitems; ++i) { if (chi_a[i] < 1 || chi_b[i] < 1 || ksplit[i] < 0) throw Err(TNQS_ERR_INVALID, "dbg_path_apply_plan: bad item");
+                                                          it[i] = PathApplyItem{nullptr, nullptr, nullptr, nullptr, 1, chi_a[i], chi_b[i], 1, ksplit[i], 0, 0}; }
+                       plan_path_apply(it.data(), nitems);
+                       for (int i = 0; i < nitems; ++i) { ksplit_out[i] = it[i].ksplit; nrb_out[i] = it[i].nrb; } });
+}
+int tnqs_dbg_rdm_paths_ws(tnqs_handle h, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out, int64_t workspace_bytes, int* nbatches_out) {
+    return guard([&] { if (workspace_bytes < 1) throw Err(TNQS_ERR_INVALID, "dbg_rdm_paths_ws: the workspace bound must be positive");
+                       rdm_paths(S(h), npaths, path_len, path_verts, out, (size_t)workspace_bytes, nbatches_out); });
 }
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor) { return guard([&] { if (!factor) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: null output"); *factor = dbg_pending_scale(S(h), v); }); }
 }

@@ -1027,18 +1027,19 @@ void dbg_cscale(int dtype, int nitems, const int* len, const void* src, const do
 }
 // edge_rdm_kernel<P> (kernels_rdm.hip), ONE launch over nitems bonds set up as engine_rdm.cpp sets them up: the items' Gram partials one after the other in partial_u /
 // partial_v (P numbers), scale_u / scale_v one double per item (0: a null pointer), out between guard bands of `guard` complex128 elements
-void dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
-                  const double* scale_u, const double* scale_v, void* out, int guard) {
+// ptype_u / ptype_v: the partial type of each end (dbg_edge_rdm: the same for both)
+void dbg_edge_rdm_mixed(int ptype_u, int ptype_v, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u,
+                        const void* partial_v, const double* scale_u, const double* scale_v, void* out, int guard) {
     need_gpu();
-    if ((ptype != 0 && ptype != 1) || nitems < 1 || !du || !dv || !chi || !nchunks_u || !nchunks_v || !partial_u || !partial_v || !scale_u || !scale_v || !out || guard < 0)
+    if ((ptype_u != 0 && ptype_u != 1) || (ptype_v != 0 && ptype_v != 1) || nitems < 1 || !du || !dv || !chi || !nchunks_u || !nchunks_v || !partial_u || !partial_v || !scale_u || !scale_v || !out || guard < 0)
         throw Err(TNQS_ERR_INVALID, "dbg_edge_rdm: bad arguments");
-    const size_t psz = ptype == 0 ? 8 : 16;
+    const size_t psz_u = ptype_u == 0 ? 8 : 16, psz_v = ptype_v == 0 ? 8 : 16;
     Slots sU, sV, sS; Guarded gO((size_t)guard * 16);
     for (int i = 0; i < nitems; ++i) {
         if (du[i] < 1 || dv[i] < 1 || chi[i] < 1 || nchunks_u[i] < 1 || nchunks_v[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_edge_rdm: dimensions and chunk counts >= 1");
         if (edge_rdm_block(du[i], dv[i], chi[i]) < 1) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_edge_rdm: bond too large for the edge kernel");
         const size_t ku = (size_t)du[i] * chi[i], kv = (size_t)dv[i] * chi[i], dd = (size_t)du[i] * dv[i];
-        sU.add((size_t)nchunks_u[i] * ku * ku * psz); sV.add((size_t)nchunks_v[i] * kv * kv * psz); sS.add(16); gO.add(dd * dd * 16);
+        sU.add((size_t)nchunks_u[i] * ku * ku * psz_u); sV.add((size_t)nchunks_v[i] * kv * kv * psz_v); sS.add(16); gO.add(dd * dd * 16);
     }
     sU.alloc(); sV.alloc(); sS.alloc(); gO.alloc();
     put_all(sU, partial_u); put_all(sV, partial_v);
@@ -1050,9 +1051,52 @@ void dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int
     }
     DBuf dI(sizeof(EdgeRdmItem) * nitems);
     sU.up(); sV.up(); sS.up(); gO.up(out); dI.up(items.data(), sizeof(EdgeRdmItem) * nitems);
-    if (ptype == 0) launch_edge_rdm<float>(nullptr, (const EdgeRdmItem*)dI.p, nitems); else launch_edge_rdm<double>(nullptr, (const EdgeRdmItem*)dI.p, nitems);
+    const EdgeRdmItem* di = (const EdgeRdmItem*)dI.p;
+    if (ptype_u == ptype_v) { if (ptype_u == 0) launch_edge_rdm<float>(nullptr, di, nitems); else launch_edge_rdm<double>(nullptr, di, nitems); }
+    else if (ptype_u == 0) launch_edge_rdm_mixed<float, double>(nullptr, di, nitems); else launch_edge_rdm_mixed<double, float>(nullptr, di, nitems);
     HIPCHK(hipDeviceSynchronize());
     gO.down(out, "out");
+}
+void dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u, const void* partial_v,
+                  const double* scale_u, const double* scale_v, void* out, int guard) {
+    dbg_edge_rdm_mixed(ptype, ptype, nitems, du, dv, chi, nchunks_u, nchunks_v, partial_u, partial_v, scale_u, scale_v, out, guard);
+}
+// path_apply_kernel<P, T> (kernels_rdm.hip), ONE launch over nitems (environment, transfer matrix) pairs set up as engine_paths.cpp sets them up: L_in holds the items'
+// nchunks_in[i] chunks of (d chi_a)^2 numbers of type P one after the other, T the items' chi_b^2 x chi_a^2 matrices of the state's type, scale one double per item (0: a
+// null pointer), L_out ksplit[i] chunks of (d chi_b)^2 complex128 per item between guard bands of `guard` elements; ksplit[i] = 0: as plan_path_apply chooses
+void dbg_path_apply(int ptype_in, int dtype, int nitems, const int* d, const int* chi_a, const int* chi_b, const int* nchunks_in, const int* ksplit, const void* L_in, const void* T,
+                    const double* scale, void* L_out, int guard) {
+    need_gpu();
+    if ((ptype_in != 0 && ptype_in != 1) || (dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !d || !chi_a || !chi_b || !nchunks_in || !ksplit || !L_in || !T || !scale || !L_out || guard < 0)
+        throw Err(TNQS_ERR_INVALID, "dbg_path_apply: bad arguments");
+    const size_t psz = ptype_in == 0 ? 8 : 16, esz = dtype == TNQS_C64 ? 8 : 16;
+    std::vector<PathApplyItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        if (d[i] < 1 || chi_a[i] < 1 || chi_b[i] < 1 || nchunks_in[i] < 1 || ksplit[i] < 0) throw Err(TNQS_ERR_INVALID, "dbg_path_apply: dimensions and chunk counts >= 1, splits >= 0");
+        if (d[i] * d[i] > 16) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_path_apply: more than 16 rows (d > 4)");
+        if ((size_t)chi_a[i] * chi_a[i] * chi_b[i] * chi_b[i] > (size_t)INT_MAX / 4) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_path_apply: bond dimension too large");
+        items[i] = PathApplyItem{nullptr, nullptr, nullptr, nullptr, d[i], chi_a[i], chi_b[i], nchunks_in[i], ksplit[i], 0, 0};
+    }
+    const int wgs = plan_path_apply(items.data(), nitems);
+    for (int i = 0; i < nitems; ++i) if (ksplit[i] == 0 ? items[i].ksplit < 1 : items[i].ksplit != ksplit[i]) throw Err(TNQS_ERR_INVALID, "dbg_path_apply: the plan changed a given split");
+    Slots sL, sT, sS; Guarded gO((size_t)guard * 16);
+    for (int i = 0; i < nitems; ++i) {
+        const size_t ka = (size_t)d[i] * chi_a[i], kb = (size_t)d[i] * chi_b[i];
+        sL.add((size_t)nchunks_in[i] * ka * ka * psz); sT.add((size_t)chi_a[i] * chi_a[i] * chi_b[i] * chi_b[i] * esz); sS.add(8); gO.add((size_t)items[i].ksplit * kb * kb * 16);
+    }
+    sL.alloc(); sT.alloc(); sS.alloc(); gO.alloc();
+    put_all(sL, L_in); put_all(sT, T);
+    for (int i = 0; i < nitems; ++i) {
+        sS.put(i, &scale[i]);
+        items[i].L_in = sL.at(i); items[i].T = sT.at(i); items[i].L_out = gO.at(i); items[i].scale = scale[i] != 0.0 ? reinterpret_cast<const double*>(sS.at(i)) : nullptr;
+    }
+    DBuf dI(sizeof(PathApplyItem) * nitems);
+    sL.up(); sT.up(); sS.up(); gO.up(L_out); dI.up(items.data(), sizeof(PathApplyItem) * nitems);
+    const PathApplyItem* di = (const PathApplyItem*)dI.p;
+    if (dtype == TNQS_C64) { if (ptype_in == 0) launch_path_apply<float, float>(nullptr, di, nitems, wgs); else launch_path_apply<double, float>(nullptr, di, nitems, wgs); }
+    else { if (ptype_in == 0) launch_path_apply<float, double>(nullptr, di, nitems, wgs); else launch_path_apply<double, double>(nullptr, di, nitems, wgs); }
+    HIPCHK(hipDeviceSynchronize());
+    gO.down(L_out, "L_out");
 }
 // the pending real scale factor of site v (State::sscale): 1 when none is pending
 double dbg_pending_scale(State* s, int v) {

@@ -231,6 +231,9 @@ void loop_weights(State* s, int ncycles, const int32_t* cycle_len, const int32_t
 // engine_rdm.cpp: un-normalised two-site reduced density matrices of bonds, (d_u d_v)^2 complex128 each, one after the other (null lists: every edge as (src, dst));
 // workspace_bytes: bound on the chain temporaries of a batch of ends (0: min(2 GiB, a quarter of the free device memory)); nbatches (may be null): batches run
 void rdm_edges(State* s, int n_edges, const int32_t* eu, const int32_t* ev, double* out_rho, size_t workspace_bytes = 0, int* nbatches = nullptr);
+// engine_paths.cpp: un-normalised two-site reduced density matrices of the ends of induced paths: for path q, for k = 1 .. path_len[q] - 1, the (d_p0 d_pk)^2 complex128
+// matrix of (p_0, p_k), one after the other; workspace_bytes: bound on a batch's workspace (0: min(2 GiB, a quarter of the free device memory)); nbatches (may be null): batches run
+void rdm_paths(State* s, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out_rho, size_t workspace_bytes = 0, int* nbatches = nullptr);
 void prof_collect(State* s);
 void materialize_pending_all(State* s);      // apply every deferred one-site gate (State::pend1)
 // sharding.cpp

@@ -11,6 +11,7 @@
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
 //   engine_loops.cpp  loop corrections: transfer matrices of simple cycles, ring products, traces (batched)
 //   engine_rdm.cpp    two-site reduced density matrices of bonds (batched chains + Grams, one contraction kernel)
+//   engine_paths.cpp  two-site reduced density matrices of the ends of paths (environments, transfer matrices, the sweep along the path)
 //   sharding.cpp      exchange step (RCCL or host callback)
 // and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
@@ -21,7 +22,7 @@
 //   kernels_chol.hip   Cholesky (square / packed), env prepare / finish  kernels_f64.hip    ComplexF64 on the f64 matrix cores
 //   kernels_theta.hip  per-gate small algebra: gate_eigs .. gate_finish  kernels_sample.hip sampling
 //   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, antiprojector, trace
-//   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs)
+//   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs), environment through a transfer matrix (path RDMs)
 #pragma once
 #include "engine.hpp"
 #include "kernels.hpp"
@@ -310,6 +311,15 @@ struct FiberPass {
 inline FiberRules fiber_rules_of(const State* s, FiberUse use) { return fiber_rules(use, s->dtype == TNQS_C64, use_mfma(), use_chi64()); }
 template <class T> void run_chains(State* s, std::vector<Chain>& chains, int cls, int cls_pair = -1);
 template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& jobs, int cls);
+// one end (u, leg) of a bond and its environment E_u[(s, a), (s', a')] as Gram partials (engine_rdm.cpp run_env_ends; shared by rdm_edges and rdm_paths).
+// cls: the Gram route class -- 0 = f64 accumulation (partials double), 1 / 2 = the f32 matrix-core Grams (partials float; ComplexF32 states with env_f32_class(KK) != 0 only)
+struct EnvEnd { int u = -1, leg = -1; SD sd; int KK = 0; size_t ws_bytes = 0; int cls = 0; Buf partial; int nchunks = 0; };
+int env_f32_class(int KK);
+template <class T> void run_env_ends(State* s, std::vector<EnvEnd>& ends, size_t e0, size_t e1);
+// a vertex with an in-leg ja (bond dimension ca) and an out-leg jb (cb), and its double-layer transfer matrix T[(b + cb b') + cb^2 (a + ca a')] (engine_loops.cpp
+// build_transfer_matrices; shared by loop_weights and rdm_paths); phi / psi: the permuted operands of the GEMM that wrote T
+struct TransferVertex { int v, ja, jb, ca, cb; SD sd; Buf phi, psi, T; };
+template <class T> void build_transfer_matrices(State* s, const std::vector<TransferVertex*>& lvs, const char* who);
 template <class T> void svd_batch(State* s, const std::vector<JacobiItem>& all, bool with_v);
 void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail = nullptr, int* d_polish_sweeps = nullptr);     // svd_batch's Cholesky-QR route (ComplexF32, no V)
 // optimistic: (apply_gates, a tolerance given) return after ENQUEUING the first sweep with its verdict left as a Check (engine.hpp); iters_before: sweeps this

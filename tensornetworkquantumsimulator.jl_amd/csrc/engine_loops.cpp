@@ -11,7 +11,7 @@
 namespace tnqs {
 
 namespace {
-struct LoopVertex { int v, ja, jb, ca, cb; SD sd; Buf phi, psi, T; };
+using LoopVertex = TransferVertex;
 struct LoopCycle { std::vector<LoopVertex> lv; std::vector<Buf> prod; size_t ws_bytes = 0; };
 
 LoopCycle describe_cycle(const State* s, const int32_t* cv, int L) {
@@ -33,17 +33,16 @@ LoopCycle describe_cycle(const State* s, const int32_t* cv, int L) {
 }
 }  // namespace
 
-template <class T> static void loop_batch(State* s, std::vector<LoopCycle>& cyc, double* out /* 2 doubles per cycle */) {
+// Steps 1-3 of a transfer-matrix batch (shared with engine_paths.cpp): for every listed vertex, T[(b, b'), (a, a')] with the messages of every leg but ja, jb absorbed
+// on the ket side.  One chain launch set, the permuted copies, ONE batched GEMM; all booked under TNQS_PROF_LOOP.  Pending one-site gates must have been applied.
+template <class T> void build_transfer_matrices(State* s, const std::vector<TransferVertex*>& lvs, const char* who) {
     const Graph& g = *s->g;
     const size_t esz = s->esz();
-    std::vector<LoopVertex*> lvs; std::vector<int> verts;
-    for (auto& c : cyc) for (auto& x : c.lv) { lvs.push_back(&x); if (std::find(verts.begin(), verts.end(), x.v) == verts.end()) verts.push_back(x.v); }
-    materialize_pending(s, verts);
-    // 1. phi = psi with the messages of every leg outside the cycle absorbed on the ket side
+    // 1. phi = psi with the messages of every leg off the cycle / path absorbed on the ket side
     std::vector<Chain> chains(lvs.size());
     for (size_t i = 0; i < lvs.size(); ++i) {
-        LoopVertex& x = *lvs[i];
-        if (!s->site[x.v]) throw Err(TNQS_ERR_INVALID, "loop_weights: vertex not owned by this rank");
+        TransferVertex& x = *lvs[i];
+        if (!s->site[x.v]) throw Err(TNQS_ERR_INVALID, std::string(who) + ": vertex not owned by this rank");
         Chain& c = chains[i]; c.v = x.v; c.src = s->site[x.v]->p; c.sd = x.sd;
         for (int j = 0; j < x.sd.z; ++j) { if (j == x.ja || j == x.jb) continue; const int de = g.dedge(g.nbr[x.v][j], x.v); if (s->msg[de]) c.steps.push_back({j, s->msg[de]->p}); }
     }
@@ -53,7 +52,7 @@ template <class T> static void loop_batch(State* s, std::vector<LoopCycle>& cyc,
     {
         ProfScope ps(s, TNQS_PROF_LOOP, 0, 0);
         for (size_t i = 0; i < lvs.size(); ++i) {
-            LoopVertex& x = *lvs[i];
+            TransferVertex& x = *lvs[i];
             auto permuted = [&](const void* src) {
                 Buf o = dalloc(s, x.sd.n * esz);
                 PermItem it{}; it.in = src; it.out = o->p; it.ndim = x.sd.z + 1; it.n = x.sd.n;
@@ -81,6 +80,18 @@ template <class T> static void loop_batch(State* s, std::vector<LoopCycle>& cyc,
         ProfScope ps(s, TNQS_PROF_LOOP, bbytes, bflops);
         launch_loop_cgemm<T>(s->stream, d, (int)build.size(), tiles);
     }
+}
+template void build_transfer_matrices<float>(State*, const std::vector<TransferVertex*>&, const char*);
+template void build_transfer_matrices<double>(State*, const std::vector<TransferVertex*>&, const char*);
+
+template <class T> static void loop_batch(State* s, std::vector<LoopCycle>& cyc, double* out /* 2 doubles per cycle */) {
+    const Graph& g = *s->g;
+    const size_t esz = s->esz();
+    std::vector<LoopVertex*> lvs; std::vector<int> verts;
+    for (auto& c : cyc) for (auto& x : c.lv) { lvs.push_back(&x); if (std::find(verts.begin(), verts.end(), x.v) == verts.end()) verts.push_back(x.v); }
+    materialize_pending(s, verts);
+    // 1-3. T_k of every vertex of every cycle
+    build_transfer_matrices<T>(s, lvs, "loop_weights");
     // 4. A_k T_k in place: f = m_{v_k -> v_{k+1}}, b = m_{v_{k+1} -> v_k} (unset message = identity)
     {
         std::unordered_map<int, Buf> ident;

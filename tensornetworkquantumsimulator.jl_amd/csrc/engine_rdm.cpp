@@ -10,12 +10,39 @@
 
 namespace tnqs {
 
-namespace {
-struct EdgeEnd { int u, leg; SD sd; int KK; size_t ws_bytes; Buf partial; int nchunks = 0; };
+using EdgeEnd = EnvEnd;
+
 // the Gram route class of a ComplexF32 end: 1 / 2 = f32 accumulation on the matrix cores up to 32 x 32 / 64 x 64 (run_grams<float, float>, the BP message Gram's
 // arithmetic), 0 = f64 accumulation on the generic kernel (run_grams<float, double>)
-int f32_class(int KK) { return (use_mfma() && KK >= 8 && KK <= 32) ? 1 : (use_mfma() && use_chi64() && KK > 32 && KK <= 64) ? 2 : 0; }
-}  // namespace
+int env_f32_class(int KK) { return (use_mfma() && KK >= 8 && KK <= 32) ? 1 : (use_mfma() && use_chi64() && KK > 32 && KK <= 64) ? 2 : 0; }
+
+// The environments E of ends [e0, e1) (shared with engine_paths.cpp): 1. the end's site tensor with the messages of every leg but its own absorbed on the ket side,
+// 2. E = the Gram that keeps the site index and that leg, one launch per route class (EnvEnd::cls).  Leaves partial / nchunks; booked under TNQS_PROF_SMALL.
+template <class T> void run_env_ends(State* s, std::vector<EnvEnd>& ends, size_t e0, size_t e1) {
+    const Graph& g = *s->g;
+    constexpr bool f32 = std::is_same<T, float>::value;
+    std::vector<Chain> chains(e1 - e0);
+    for (size_t i = e0; i < e1; ++i) {
+        const EnvEnd& x = ends[i];
+        Chain& c = chains[i - e0]; c.v = x.u; c.src = s->site[x.u]->p; c.sd = x.sd;
+        for (int j = 0; j < x.sd.z; ++j) { if (j == x.leg) continue; const int de = g.dedge(g.nbr[x.u][j], x.u); if (s->msg[de]) c.steps.push_back({j, s->msg[de]->p}); }
+    }
+    run_chains<T>(s, chains, TNQS_PROF_SMALL);
+    std::vector<GramJob> jobs[3];
+    std::vector<size_t> who[3];
+    for (size_t i = e0; i < e1; ++i) {
+        GramJob j{}; j.X = chains[i - e0].result; j.Y = chains[i - e0].src; j.sd = ends[i].sd; j.leg = ends[i].leg; j.keep_site = true;
+        jobs[ends[i].cls].push_back(j); who[ends[i].cls].push_back(i);
+    }
+    for (int cls = 0; cls < 3; ++cls) {
+        if (jobs[cls].empty()) continue;
+        if constexpr (f32) { if (cls) run_grams<float, float>(s, jobs[cls], TNQS_PROF_SMALL); else run_grams<float, double>(s, jobs[cls], TNQS_PROF_SMALL); }
+        else run_grams<double, double>(s, jobs[cls], TNQS_PROF_SMALL);
+        for (size_t q = 0; q < jobs[cls].size(); ++q) { EnvEnd& x = ends[who[cls][q]]; x.partial = jobs[cls][q].partial; x.nchunks = jobs[cls][q].nchunks; }
+    }
+}
+template void run_env_ends<float>(State*, std::vector<EnvEnd>&, size_t, size_t);
+template void run_env_ends<double>(State*, std::vector<EnvEnd>&, size_t, size_t);
 
 template <class T> static void rdm_edges_t(State* s, const std::vector<int>& bonds /* distinct edge ids */, const std::vector<size_t>& off /* of bond k in d_out, complex numbers */,
                                            Buf d_out, size_t budget, int* nbatches) {
@@ -34,35 +61,16 @@ template <class T> static void rdm_edges_t(State* s, const std::vector<int>& bon
             if (!s->site[x.u]) throw Err(TNQS_ERR_INVALID, "rdm_edges: vertex not owned by this rank");
         }
         if (edge_rdm_block(s->d[uv[0]], s->d[uv[1]], s->chi[e]) < 1) throw Err(TNQS_ERR_UNSUPPORTED, "rdm_edges: bond too large for the edge kernel ((d_u^2 + d_v^2) chi must stay below 4096)");
-        acc32[k] = f32 && f32_class(ends[2 * k].KK) && f32_class(ends[2 * k + 1].KK);
+        acc32[k] = f32 && env_f32_class(ends[2 * k].KK) && env_f32_class(ends[2 * k + 1].KK);
+        for (int q = 0; q < 2; ++q) ends[2 * k + q].cls = acc32[k] ? env_f32_class(ends[2 * k + q].KK) : 0;
     }
     size_t launched = 0;                                 // bonds [0, launched) have been handed to the edge kernel
     for (size_t e0 = 0; e0 < ends.size();) {
         size_t e1 = e0, bytes = 0;
         while (e1 < ends.size() && (e1 == e0 || bytes + ends[e1].ws_bytes <= budget)) bytes += ends[e1++].ws_bytes;
         if (nbatches) ++*nbatches;
-        // 1. the end's site tensor with the messages of every leg but the bond's absorbed on the ket side
-        std::vector<Chain> chains(e1 - e0);
-        for (size_t i = e0; i < e1; ++i) {
-            const EdgeEnd& x = ends[i];
-            Chain& c = chains[i - e0]; c.v = x.u; c.src = s->site[x.u]->p; c.sd = x.sd;
-            for (int j = 0; j < x.sd.z; ++j) { if (j == x.leg) continue; const int de = g.dedge(g.nbr[x.u][j], x.u); if (s->msg[de]) c.steps.push_back({j, s->msg[de]->p}); }
-        }
-        run_chains<T>(s, chains, TNQS_PROF_SMALL);
-        // 2. E = Gram that keeps the site index and the bond's leg, one launch per route class
-        std::vector<GramJob> jobs[3];
-        std::vector<size_t> who[3];
-        for (size_t i = e0; i < e1; ++i) {
-            GramJob j{}; j.X = chains[i - e0].result; j.Y = chains[i - e0].src; j.sd = ends[i].sd; j.leg = ends[i].leg; j.keep_site = true;
-            const int cls = acc32[i / 2] ? f32_class(ends[i].KK) : 0;
-            jobs[cls].push_back(j); who[cls].push_back(i);
-        }
-        for (int cls = 0; cls < 3; ++cls) {
-            if (jobs[cls].empty()) continue;
-            if constexpr (f32) { if (cls) run_grams<float, float>(s, jobs[cls], TNQS_PROF_SMALL); else run_grams<float, double>(s, jobs[cls], TNQS_PROF_SMALL); }
-            else run_grams<double, double>(s, jobs[cls], TNQS_PROF_SMALL);
-            for (size_t q = 0; q < jobs[cls].size(); ++q) { EdgeEnd& x = ends[who[cls][q]]; x.partial = jobs[cls][q].partial; x.nchunks = jobs[cls][q].nchunks; }
-        }
+        // 1. + 2. the environments of the batch's ends
+        run_env_ends<T>(s, ends, e0, e1);
         // 3. every bond whose two ends are done: the chunks of both ends summed and the bond contracted, straight into the call's output
         std::vector<EdgeRdmItem> items[2]; double pbytes = 0, flops = 0;
         const size_t ready = e1 / 2;

@@ -342,6 +342,19 @@ __host__ __device__ inline int edge_rdm_block(int du, int dv, int chi) {
     return (int)(nb < chi ? nb : chi);
 }
 template <class P> void launch_edge_rdm(hipStream_t s, const EdgeRdmItem* d_items, int nitems);      // every item must have edge_rdm_block() >= 1
+// the same kernel with one partial type per end (u: Pu, v: Pv): the bond contraction of tnqs_rdm_paths, whose u operand is the environment carried along the path (double)
+template <class Pu, class Pv> void launch_edge_rdm_mixed(hipStream_t s, const EdgeRdmItem* d_items, int nitems);
+// the environment of a path's source carried through the transfer matrix of an inner vertex (kernels_rdm.hip path_apply_kernel<P, T>):
+//   L_out[j][(s + d b) + d chi_b (s' + d b')] = (*scale)^2 sum_{(a, a') in column range j} L_in[(s + d a) + d chi_a (s' + d a')] T[(b + chi_b b') + chi_b^2 (a + chi_a a')]
+// L_in = the sum of nchunks_in chunks of type P (Gram-partial layout), T of the state's type, L_out ksplit chunks of complex128; f64 throughout; d <= 4 (16 rows of L).
+// Grid of an item: nrb row blocks of 256 rows (b, b') x ksplit column ranges; workgroup (rb, j) writes its rows of chunk j, every element of every chunk exactly once.
+struct PathApplyItem { const void* L_in; const void* T; void* L_out; const double* scale; int d, chi_a, chi_b, nchunks_in, ksplit; int wg_begin, nrb; };
+constexpr int kPathApplyCols = 64;          // columns of L_in staged in LDS per pass (64 x 16 complex128 = 16 KiB)
+constexpr int kPathApplyMaxSplit = 16;      // column ranges per item at the most (each is a chunk the next step reads)
+constexpr int kPathApplyTargetWgs = 256;    // a launch aims at one workgroup per compute unit
+// sets nrb, wg_begin and -- where it is 0 -- ksplit = clamp(ceil(256 / row blocks of the launch), 1, min(16, chi_a^2 / 64)); returns the launch's workgroups
+int plan_path_apply(PathApplyItem* it, int n);
+template <class P, class T> void launch_path_apply(hipStream_t s, const PathApplyItem* d_items, int nitems, int total_wgs);
 // one-site gates on d = 2, ComplexF32: streaming 2x2 apply, norm partials [item][nbx]
 void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int nbx, double* d_norm_partials);
 
