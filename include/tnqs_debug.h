@@ -174,6 +174,42 @@ int tnqs_dbg_rdm_edges_ws(tnqs_handle h, int n_edges, const int32_t* eu, const i
                           int64_t workspace_bytes, int* nbatches_out);
 /* the pending real scale factor of the site tensor of v (a normalising gate only records 1/||psi_v||; the tensor the reference holds is the stored one times it): 1 when none is pending */
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor);
+/* ---- the gate path's per-gate small algebra (csrc/kernels_theta.hip and the small_svd_* kernels of csrc/kernels_svd.hip; dtype 0 c64 = T float, 1 c128 = T double).  ONE launch
+ * of every kernel over nitems gates / sites of different sizes; the descriptors are filled by the rules of engine_gates.cpp (gate_items, run_theta, second_pass, add_small_svd)
+ * and the same launches run in the same order.  Inputs hold the items' arrays one after the other; on the device every sub-array starts at a multiple of 256 bytes.  Every
+ * output array with a `guard` holds guard elements, item 0, guard elements, item 1, ..., guard elements (elements of the array's own type), goes up as the caller filled it and
+ * comes back whole.  The small integer outputs (info, texp, failure flags, ranks) and truncerr are contiguous per launch as in the engine's read-back buffer: they go up as
+ * filled and come back.  A gate with d^2 chi > 512 (or a site the named kernel does not take): TNQS_ERR_UNSUPPORTED as in the engine, nothing is written ----
+ * HOST ONLY (no device is touched): the gate (d1 d2 x d1 d2 complex128, column-major, first vertex most significant) as an operator sum g = sum_k a_k (x) b_k, as gate_items()
+ * gets it: *kappa_out terms, fa_out[k][s' + d1 s] (room for min(d1, d2)^2 d1^2 numbers), fb_out[k][s' + d2 s] (min(d1, d2)^2 d2^2) */
+int tnqs_dbg_operator_sum(const void* gate, int d1, int d2, int* kappa_out, void* fa_out, void* fb_out);
+/* the launches of run_theta(): gate_theta -> gate_theta_mm -> lowrank_g -> chol / chol_packed -> lowrank_m (ComplexF64: -> lowrank_bw -> lowrank_g -> chol -> lowrank_ll ->
+ * lowrank_m) -> theta_scale.  Per item: dims = (d1, d2, chi); n_s = d_s chi; mode[2], rk[2], tau[2] per site: mode 0 eigen (GA = G V, GV = V, GW = V), 1 Cholesky (GV = L,
+ * GW = (L^-1)^dagger), 2 explicit factor (GV = R^dagger, GW = R^+, rk columns); F1, F2: (GA, GV, GW) of site 1 / 2, three n_s x n_s complex128 matrices per item; gate as above;
+ * maxdim (<= 0: none); lowrank_on: the operator-sum / low-rank switch (TNQS_NO_LOWRANK unset = 1).  stop_after: 0 gate_theta, 1 gate_theta_mm, 2 the low-rank block, 3 theta_scale.
+ * low_sizes_out, 6 ints per item: the element counts of lowA (Mr K), lowB (Nc K), lowG, lowL (K K), lowQ (Nc K), lowL2c (2 K K: L2, then Lc = L1 L2; ComplexF64) -- 0 where the host
+ * rule of gate_items() does not hand the workspace out (Mr = d1^2 chi, Nc = d2^2 chi, K = kappa chi).  info == NULL: only low_sizes_out is filled (HOST ONLY) and the call returns.
+ * Outputs: info (8 ints per item), lam1 / lam2 (n_s doubles), idx1 / idx2 (n_s ints), theta, theta0 (Mr Nc numbers of T), thetaV (max(Mr, Nc)^2 numbers of T), lowA .. lowL2c
+ * (complex128, sized by low_sizes_out), texp (1 int per item), lowfail (2 ints per item: the gate's failure flag -- pass 1, with pass 2 folded in by lowrank_ll -- and the raw flag of pass 2, which means nothing
+ * where info[7] = 0: its Cholesky then ran on a Gram matrix nothing wrote) */
+int tnqs_dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode, const int* rk, const void* F1, const void* F2, const double* tau, const void* gate,
+                        const int* maxdim, int lowrank_on, int stop_after, int* low_sizes_out, int* info, double* lam1, double* lam2, int* idx1, int* idx2,
+                        void* theta, void* theta0, void* thetaV, void* lowA, void* lowB, void* lowG, void* lowL, void* lowQ, void* lowL2c, int* texp, int* lowfail, int guard);
+/* gate_finish_kernel<T> alone on what the SVD stage leaves.  Per item: dims = (d1, d2, chi); info_in = (r1, r2, wide, K): info[0], [1], [5], [7]; texp; theta: the rotated columns
+ * (max(Mr, Nc) x min(Mr, Nc) numbers of T with Mr = r1 d1, Nc = r2 d2; any column order); thetaV: min(Mr, Nc)^2 numbers of T; lam (n_s doubles), idx (n_s ints; the first r_s are
+ * read) and GW (n_s x n_s complex128) of both sites; maxdim, cutoff, normalize, chi_cap.  Outputs: S (chi_cap doubles per item, guard counts doubles), info_out (chi', status),
+ * truncerr (1 double per item), X1 (n_1 x d1 chi_cap numbers of T), X2 (n_2 x d2 chi_cap) */
+int tnqs_dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in, const int* texp, const void* theta, const void* thetaV, const double* lam1, const double* lam2,
+                         const int* idx1, const int* idx2, const void* GW1, const void* GW2, const int* maxdim, const double* cutoff, const int* normalize, const int* chi_cap,
+                         double* S, int* info_out, double* truncerr, void* X1, void* X2, int guard);
+/* the second factorisation pass: qr2_rinv_kernel (stage 0: X1 = R1^+ only; GV, A2, V2, tau, GVout, GWout, rk may be NULL), then qr2_compose_kernel (stage 1: both, X1 formed on the
+ * device).  Per item n x n complex128 matrices: first-pass GW, GV, lam (n doubles), idx (n ints), r; the eigen pair (A2 = G2 V2, V2) of the second Gram matrix; tau.  Outputs X1,
+ * GVout, GWout (n x n complex128) and rk.  n > 256: TNQS_ERR_UNSUPPORTED */
+int tnqs_dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,
+                 void* X1, void* GVout, void* GWout, int* rk, int guard);
+/* small_svd_prepare_kernel<T> -> the f64 Jacobi -> small_svd_finish_kernel on site tensors [d][low][chi_b][hi] of type T (shape: 4 ints per item) with N = low hi < n = d chi_b <= 256
+ * (else TNQS_ERR_UNSUPPORTED): GA, GV (n x n complex128): column j < N of GV = left singular vector u_j of M[(s,b), outer] = conj(psi), GA[:, j] = sigma_j^2 u_j; columns >= N zero */
+int tnqs_dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard);
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,16 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                                          const void* partial_v, const double* scale_u, const double* scale_v, void* out, int guard);
                  void dbg_path_apply(int ptype_in, int dtype, int nitems, const int* d, const int* chi_a, const int* chi_b, const int* nchunks_in, const int* ksplit, const void* L_in, const void* T,
                                      const double* scale, void* L_out, int guard);
+                 int dbg_operator_sum(const void* gate, int d1, int d2, void* fa_out, void* fb_out);
+                 void dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode, const int* rk, const void* F1, const void* F2, const double* tau, const void* gate,
+                                     const int* maxdim, int lowrank_on, int stop_after, int* low_sizes, int* info, double* lam1, double* lam2, int* idx1, int* idx2,
+                                     void* theta, void* theta0, void* thetaV, void* lowA, void* lowB, void* lowG, void* lowL, void* lowQ, void* lowL2c, int* texp, int* lowfail, int guard);
+                 void dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in, const int* texp, const void* theta, const void* thetaV, const double* lam1, const double* lam2,
+                                      const int* idx1, const int* idx2, const void* GW1, const void* GW2, const int* maxdim, const double* cutoff, const int* normalize, const int* chi_cap,
+                                      double* S, int* info_out, double* truncerr, void* X1, void* X2, int guard);
+                 void dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,
+                              void* X1, void* GVout, void* GWout, int* rk, int guard);
+                 void dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard);
                  double dbg_pending_scale(State* s, int v); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
@@ -371,4 +381,25 @@ int tnqs_dbg_rdm_paths_ws(tnqs_handle h, int npaths, const int32_t* path_len, co
                        rdm_paths(S(h), npaths, path_len, path_verts, out, (size_t)workspace_bytes, nbatches_out); });
 }
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor) { return guard([&] { if (!factor) throw Err(TNQS_ERR_INVALID, "dbg_pending_scale: null output"); *factor = dbg_pending_scale(S(h), v); }); }
+int tnqs_dbg_operator_sum(const void* gate, int d1, int d2, int* kappa_out, void* fa_out, void* fb_out) {
+    return guard([&] { if (!kappa_out) throw Err(TNQS_ERR_INVALID, "dbg_operator_sum: null output"); *kappa_out = dbg_operator_sum(gate, d1, d2, fa_out, fb_out); });
+}
+int tnqs_dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode, const int* rk, const void* F1, const void* F2, const double* tau, const void* gate,
+                        const int* maxdim, int lowrank_on, int stop_after, int* low_sizes_out, int* info, double* lam1, double* lam2, int* idx1, int* idx2,
+                        void* theta, void* theta0, void* thetaV, void* lowA, void* lowB, void* lowG, void* lowL, void* lowQ, void* lowL2c, int* texp, int* lowfail, int guard_elems) {
+    return guard([&] { dbg_gate_theta(dtype, nitems, dims, mode, rk, F1, F2, tau, gate, maxdim, lowrank_on, stop_after, low_sizes_out, info, lam1, lam2, idx1, idx2, theta, theta0, thetaV,
+                                      lowA, lowB, lowG, lowL, lowQ, lowL2c, texp, lowfail, guard_elems); });
+}
+int tnqs_dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in, const int* texp, const void* theta, const void* thetaV, const double* lam1, const double* lam2,
+                         const int* idx1, const int* idx2, const void* GW1, const void* GW2, const int* maxdim, const double* cutoff, const int* normalize, const int* chi_cap,
+                         double* S, int* info_out, double* truncerr, void* X1, void* X2, int guard_elems) {
+    return guard([&] { dbg_gate_finish(dtype, nitems, dims, info_in, texp, theta, thetaV, lam1, lam2, idx1, idx2, GW1, GW2, maxdim, cutoff, normalize, chi_cap, S, info_out, truncerr, X1, X2, guard_elems); });
+}
+int tnqs_dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,
+                 void* X1, void* GVout, void* GWout, int* rk, int guard_elems) {
+    return guard([&] { dbg_qr2(stage, nitems, n, GW, GV, lam, idx, r, A2, V2, tau, X1, GVout, GWout, rk, guard_elems); });
+}
+int tnqs_dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard_elems) {
+    return guard([&] { dbg_small_svd(dtype, nitems, shape, src, GA, GV, guard_elems); });
+}
 }

@@ -7,14 +7,14 @@
 #include <memory>
 #include <string>
 #include "engine.hpp"
+#include "engine_internal.hpp"
 #include "kernels.hpp"
 #include "launch_util.hpp"
 #include "../../include/tnqs_debug.h"
 
 namespace tnqs {
-#define HIPCHK(x) hipchk((x), #x)
 struct DBuf { void* p = nullptr; explicit DBuf(size_t n) { HIPCHK(hipMalloc(&p, n ? n : 1)); } ~DBuf() { (void)hipFree(p); }
-              void up(const void* h, size_t n) { HIPCHK(hipMemcpy(p, h, n, hipMemcpyHostToDevice)); } void down(void* h, size_t n) { HIPCHK(hipMemcpy(h, p, n, hipMemcpyDeviceToHost)); } };
+              void up(const void* h, size_t n) { if (n) HIPCHK(hipMemcpy(p, h, n, hipMemcpyHostToDevice)); } void down(void* h, size_t n) { if (n) HIPCHK(hipMemcpy(h, p, n, hipMemcpyDeviceToHost)); } };
 static void need_gpu() { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Err(TNQS_ERR_HIP, "no HIP device available"); }
 
 void dbg_jacobi(int dtype, int m, int n, void* A, void* V, int* sweeps) {
@@ -644,7 +644,6 @@ void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fai
 
 // ---- the small-site BP message kernel and the message epilogue, set up as engine_bp.cpp sets them up --------------------------------------------------------
 namespace {
-inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 // a device array of slots that start at 256-byte multiples (the engine's sub-buffers); the gaps keep a 0xff filling that is checked after the launch, so a
 // kernel that writes past its slot is reported instead of going unnoticed
 struct Slots {
@@ -1106,5 +1105,282 @@ double dbg_pending_scale(State* s, int v) {
     HIPCHK(hipStreamSynchronize(s->stream));
     double f = 1.0; HIPCHK(hipMemcpy(&f, s->sscale[v]->p, 8, hipMemcpyDeviceToHost));
     return f;
+}
+// ---- the gate path's per-gate small algebra (kernels_theta.hip and the small_svd_* kernels of kernels_svd.hip): ONE launch of every kernel over nitems gates / sites of
+// different sizes.  The descriptors are filled by the rules of engine_gates.cpp (gate_items, run_theta, second_pass, add_small_svd) and the same launch_* functions run in
+// the same order -- keep the two in step.  Inputs: the items' arrays one after the other, every sub-array at a multiple of 256 bytes on the device.  Outputs: guard bands
+// as above.  The small integer arrays (info, texp, failure flags, ranks) are contiguous per launch as in the engine's read-back buffer: they go up as filled and come back ----
+namespace {
+struct GateDims { int d1, d2, chi, n1, n2, Mr, Nc; };
+// d^2 chi > 512: the engine refuses the gate (gate_items)
+GateDims gate_dims(const char* who, const int* dims, int i) {
+    const int d1 = dims[3 * i], d2 = dims[3 * i + 1], chi = dims[3 * i + 2];
+    if (d1 < 1 || d2 < 1 || chi < 1) throw Err(TNQS_ERR_INVALID, std::string(who) + ": d1, d2, chi >= 1");
+    if ((long long)d1 * d1 * chi > 512 || (long long)d2 * d2 * chi > 512) throw Err(TNQS_ERR_UNSUPPORTED, std::string(who) + ": d^2*chi > 512 is not supported by the theta SVD kernels");
+    return GateDims{d1, d2, chi, d1 * chi, d2 * chi, d1 * d1 * chi, d2 * d2 * chi};
+}
+void up_ints(DBuf& d, const int* h, size_t n) { d.up(h, sizeof(int) * n); }
+}
+// HOST ONLY: the operator-sum factors of a two-site gate as gate_items() gets them
+int dbg_operator_sum(const void* gate, int d1, int d2, void* fa_out, void* fb_out) {
+    if (!gate || d1 < 1 || d2 < 1 || d1 > 16 || d2 > 16) throw Err(TNQS_ERR_INVALID, "dbg_operator_sum: bad arguments");
+    std::vector<std::complex<double>> fa, fb;
+    const int kappa = operator_sum(reinterpret_cast<const double*>(gate), d1, d2, fa, fb);
+    if (fa_out && !fa.empty()) std::memcpy(fa_out, fa.data(), fa.size() * 16);
+    if (fb_out && !fb.empty()) std::memcpy(fb_out, fb.data(), fb.size() * 16);
+    return kappa;
+}
+// the launches of TwoSiteBatch::run_theta.  info == NULL: only low_sizes is filled (host only)
+void dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode, const int* rk, const void* F1, const void* F2, const double* tau, const void* gate,
+                    const int* maxdim, int lowrank_on, int stop_after, int* low_sizes, int* info, double* lam1, double* lam2, int* idx1, int* idx2,
+                    void* theta, void* theta0, void* thetaV, void* lowA, void* lowB, void* lowG, void* lowL, void* lowQ, void* lowL2c, int* texp, int* lowfail, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !dims || !mode || !rk || !F1 || !F2 || !tau || !gate || !maxdim || !low_sizes || stop_after < 0 || stop_after > 3 || guard < 0)
+        throw Err(TNQS_ERR_INVALID, "dbg_gate_theta: bad arguments");
+    const bool F32 = dtype == TNQS_C64; const size_t esz = F32 ? 8 : 16;
+    std::vector<GateDims> gd(nitems); std::vector<int> kappa(nitems, 0), cap(nitems); std::vector<char> low(nitems, 0), lowq(nitems, 0);
+    std::vector<std::vector<std::complex<double>>> fa(nitems), fb(nitems);
+    const char* hg = (const char*)gate; std::vector<size_t> goff(nitems + 1, 0);
+    for (int i = 0; i < nitems; ++i) {
+        gd[i] = gate_dims("dbg_gate_theta", dims, i);
+        for (int sd = 0; sd < 2; ++sd) {
+            const int m = mode[2 * i + sd], n = sd ? gd[i].n2 : gd[i].n1;
+            if (m < 0 || m > 2 || (m == 2 && (rk[2 * i + sd] < 0 || rk[2 * i + sd] > n))) throw Err(TNQS_ERR_INVALID, "dbg_gate_theta: mode in {0, 1, 2}, 0 <= rk <= n");
+        }
+        const size_t dd = (size_t)gd[i].d1 * gd[i].d2; goff[i + 1] = goff[i] + dd * dd * 16;
+    }
+    for (int i = 0; i < nitems; ++i) {      // gate_items(): cap, operator sum, and where the low-rank workspaces are handed out
+        const GateDims& g = gd[i];
+        cap[i] = std::min(g.Mr, g.Nc); if (maxdim[i] > 0) cap[i] = std::min(cap[i], maxdim[i]);
+        if (lowrank_on) kappa[i] = operator_sum(reinterpret_cast<const double*>(hg + goff[i]), g.d1, g.d2, fa[i], fb[i]);
+        const int K = kappa[i] * g.chi;
+        if (lowrank_on && kappa[i] > 0) {
+            const bool lds_fits = F32 || jacobi_lds(jacobi_lds_bytes(g.Mr, K, false, esz)) > 0;
+            if (K < g.Nc && K <= 128 && cap[i] <= K && g.Mr >= g.Nc && lds_fits) {
+                low[i] = 1;
+                if (F32 && use_precond_svd() && theta_svd_pre_covers(g.Mr, K) && K <= 96) lowq[i] = 1;
+            }
+        }
+        int* z = low_sizes + 6 * i;
+        z[0] = kappa[i] > 0 ? g.Mr * K : 0; z[1] = kappa[i] > 0 ? g.Nc * K : 0; z[2] = low[i] ? K * K : 0; z[3] = z[2]; z[4] = lowq[i] ? g.Nc * K : 0; z[5] = (low[i] && !F32) ? 2 * K * K : 0;
+    }
+    if (!info) return;
+    if (!lam1 || !lam2 || !idx1 || !idx2 || !theta || !theta0 || !thetaV || !lowA || !lowB || !lowG || !lowL || !lowQ || !lowL2c || !texp || !lowfail)
+        throw Err(TNQS_ERR_INVALID, "dbg_gate_theta: null output");
+    need_gpu();
+    Slots sF1, sF2, sGate, sOp, sRk, sW, sB1, sG2;
+    Guarded gLam1((size_t)guard * 8), gLam2((size_t)guard * 8), gIdx1((size_t)guard * 4), gIdx2((size_t)guard * 4), gTh(guard * esz), gTh0(guard * esz), gTv(guard * esz),
+            gA((size_t)guard * 16), gB((size_t)guard * 16), gG((size_t)guard * 16), gL((size_t)guard * 16), gQ((size_t)guard * 16), gL2c((size_t)guard * 16);
+    for (int i = 0; i < nitems; ++i) {
+        const GateDims& g = gd[i]; const int* z = low_sizes + 6 * i; const size_t KK = (size_t)z[2];
+        for (int k = 0; k < 3; ++k) { sF1.add((size_t)g.n1 * g.n1 * 16); sF2.add((size_t)g.n2 * g.n2 * 16); }
+        sGate.add(goff[i + 1] - goff[i]); sOp.add(fa[i].size() * 16); sOp.add(fb[i].size() * 16); sRk.add(8);
+        sW.add(KK * 16); sB1.add(F32 ? 0 : (size_t)z[1] * 16 * (low[i] ? 1 : 0)); sG2.add(F32 ? 0 : KK * 16);
+        gLam1.add((size_t)g.n1 * 8); gLam2.add((size_t)g.n2 * 8); gIdx1.add((size_t)g.n1 * 4); gIdx2.add((size_t)g.n2 * 4);
+        const size_t mx = (size_t)std::max(g.Mr, g.Nc);
+        gTh.add((size_t)g.Mr * g.Nc * esz); gTh0.add((size_t)g.Mr * g.Nc * esz); gTv.add(mx * mx * esz);
+        gA.add((size_t)z[0] * 16); gB.add((size_t)z[1] * 16); gG.add((size_t)z[2] * 16); gL.add((size_t)z[3] * 16); gQ.add((size_t)z[4] * 16); gL2c.add((size_t)z[5] * 16);
+    }
+    for (Slots* s : {&sF1, &sF2, &sGate, &sOp, &sRk, &sW, &sB1, &sG2}) s->alloc();
+    for (Guarded* g : {&gLam1, &gLam2, &gIdx1, &gIdx2, &gTh, &gTh0, &gTv, &gA, &gB, &gG, &gL, &gQ, &gL2c}) g->alloc();
+    put_all(sF1, F1); put_all(sF2, F2); put_all(sGate, gate);
+    for (int i = 0; i < nitems; ++i) { if (!fa[i].empty()) { sOp.put(2 * i, fa[i].data()); sOp.put(2 * i + 1, fb[i].data()); } sRk.put(i, rk + 2 * i); }
+    DBuf dInfo(32 * (size_t)nitems), dFail(8 * (size_t)nitems), dTexp(4 * (size_t)nitems);
+    HIPCHK(hipMemset(dInfo.p, 0, 32 * (size_t)nitems)); HIPCHK(hipMemset(dFail.p, 0, 8 * (size_t)nitems));      // run_theta zeroes info and both failure-flag arrays
+    up_ints(dTexp, texp, nitems);
+    std::vector<GateItem> gitems(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        const GateDims& g = gd[i]; GateItem& it = gitems[i]; it = GateItem{};
+        it.GA1 = sF1.at(3 * i); it.GV1 = sF1.at(3 * i + 1); it.GW1 = sF1.at(3 * i + 2); it.GA2 = sF2.at(3 * i); it.GV2 = sF2.at(3 * i + 1); it.GW2 = sF2.at(3 * i + 2);
+        it.chol1 = mode[2 * i]; it.chol2 = mode[2 * i + 1]; it.n1 = g.n1; it.n2 = g.n2; it.d1 = g.d1; it.d2 = g.d2; it.chi = g.chi;
+        it.gate = reinterpret_cast<const double*>(sGate.at(i));
+        if (lowrank_on && kappa[i] > 0) {
+            it.kappa = kappa[i]; it.opA = reinterpret_cast<const double*>(sOp.at(2 * i)); it.opB = reinterpret_cast<const double*>(sOp.at(2 * i + 1));
+            it.lowA = gA.at(i); it.lowB = gB.at(i);
+            if (low[i]) { it.lowG = gG.at(i); it.lowL = gL.at(i); if (lowq[i]) { it.lowW = sW.at(i); it.lowQ = gQ.at(i); } }
+        }
+        it.lam1 = (double*)gLam1.at(i); it.lam2 = (double*)gLam2.at(i); it.idx1 = (int*)gIdx1.at(i); it.idx2 = (int*)gIdx2.at(i);
+        it.theta = gTh.at(i); it.thetaV = gTv.at(i); it.theta0 = gTh0.at(i);
+        it.maxdim = maxdim[i]; it.chi_cap = cap[i];
+        it.tau1 = tau[2 * i]; it.tau2 = tau[2 * i + 1];
+        it.rk1 = mode[2 * i] == 2 ? (const int*)sRk.at(i) : nullptr; it.rk2 = mode[2 * i + 1] == 2 ? (const int*)sRk.at(i) + 1 : nullptr;
+        it.info = (int*)dInfo.p + 8 * i; it.lowfail = (const int*)dFail.p + i; it.texp = (int*)dTexp.p + i;
+    }
+    DBuf dI(sizeof(GateItem) * nitems); dI.up(gitems.data(), sizeof(GateItem) * nitems);
+    for (Slots* s : {&sF1, &sF2, &sGate, &sOp, &sRk, &sW, &sB1, &sG2}) s->up();
+    gLam1.up(lam1); gLam2.up(lam2); gIdx1.up(idx1); gIdx2.up(idx2); gTh.up(theta); gTh0.up(theta0); gTv.up(thetaV);
+    gA.up(lowA); gB.up(lowB); gG.up(lowG); gL.up(lowL); gQ.up(lowQ); gL2c.up(lowL2c);
+    const GateItem* d_gitems = (const GateItem*)dI.p;
+    bool lowrank_on_batch = false; for (int i = 0; i < nitems; ++i) lowrank_on_batch = lowrank_on_batch || gitems[i].lowA;
+    // ---- run_theta ----
+    std::vector<std::unique_ptr<DBuf>> keep;
+    auto upload_vec = [&](const void* p, size_t bytes) { keep.emplace_back(new DBuf(bytes)); keep.back()->up(p, bytes); return keep.back()->p; };
+    if (F32) launch_gate_theta<float>(nullptr, d_gitems, nitems); else launch_gate_theta<double>(nullptr, d_gitems, nitems);
+    if (stop_after >= 1 && lowrank_on_batch) { if (F32) launch_gate_theta_mm<float>(nullptr, d_gitems, nitems); else launch_gate_theta_mm<double>(nullptr, d_gitems, nitems); }
+    if (stop_after >= 2) {
+        std::vector<CholItem> lc, lc2; int kmax = 1;
+        std::vector<GateItem> g2, g3; std::vector<LowQr2Item> qi;
+        for (int q = 0; q < nitems; ++q) {
+            if (!gitems[q].lowG) continue;
+            const int K = gitems[q].kappa * gitems[q].chi; const size_t KK = (size_t)K * K;
+            int* fail1 = (int*)dFail.p + q;
+            lc.push_back(CholItem{gitems[q].lowG, const_cast<void*>(gitems[q].lowL), (K <= 96 || !F32) ? (void*)sW.at(q) : nullptr, K, fail1, !F32 ? 1e-12 : rank_tau(true, K)});
+            kmax = std::max(kmax, K);
+            if (!F32) {
+                int* fail2 = (int*)dFail.p + nitems + q;
+                char* L2 = gL2c.at(q); char* Lc = gL2c.at(q) + KK * 16;
+                lc2.push_back(CholItem{sG2.at(q), L2, nullptr, K, fail2, 1e-3});
+                GateItem a = gitems[q]; a.lowB = sB1.at(q); a.lowG = sG2.at(q); a.lowL = L2; g2.push_back(a);
+                GateItem b = gitems[q]; b.lowL = Lc; g3.push_back(b);
+                qi.push_back(LowQr2Item{gitems[q].lowB, sW.at(q), sB1.at(q), gitems[q].lowL, L2, Lc, gitems[q].info, gitems[q].d2, fail1, fail2});
+            }
+        }
+        if (!lc.empty()) {
+            const CholItem* dc = (const CholItem*)upload_vec(lc.data(), sizeof(CholItem) * lc.size()); launch_lowrank_g(nullptr, d_gitems, nitems);
+            if (kmax <= 96) launch_chol(nullptr, dc, (int)lc.size(), kmax); else launch_chol_packed(nullptr, dc, (int)lc.size(), kmax);
+            if (F32) launch_lowrank_m<float>(nullptr, d_gitems, nitems);
+            else {
+                const LowQr2Item* dq = (const LowQr2Item*)upload_vec(qi.data(), sizeof(LowQr2Item) * qi.size());
+                const GateItem* d2 = (const GateItem*)upload_vec(g2.data(), sizeof(GateItem) * g2.size()); const GateItem* d3 = (const GateItem*)upload_vec(g3.data(), sizeof(GateItem) * g3.size());
+                const CholItem* dc2 = (const CholItem*)upload_vec(lc2.data(), sizeof(CholItem) * lc2.size());
+                launch_lowrank_bw(nullptr, dq, (int)qi.size());
+                launch_lowrank_g(nullptr, d2, (int)g2.size());
+                if (kmax <= 96) launch_chol(nullptr, dc2, (int)lc2.size(), kmax); else launch_chol_packed(nullptr, dc2, (int)lc2.size(), kmax);
+                launch_lowrank_ll(nullptr, dq, (int)qi.size());
+                launch_lowrank_m<double>(nullptr, d3, (int)g3.size());
+            }
+        }
+    }
+    if (stop_after >= 3) { if (F32) launch_theta_scale<float>(nullptr, d_gitems, nitems); else launch_theta_scale<double>(nullptr, d_gitems, nitems); }
+    HIPCHK(hipDeviceSynchronize());
+    sW.down("lowW"); sB1.down("lowB1"); sG2.down("lowG2");
+    gLam1.down(lam1, "lam1"); gLam2.down(lam2, "lam2"); gIdx1.down(idx1, "idx1"); gIdx2.down(idx2, "idx2"); gTh.down(theta, "theta"); gTh0.down(theta0, "theta0"); gTv.down(thetaV, "thetaV");
+    gA.down(lowA, "lowA"); gB.down(lowB, "lowB"); gG.down(lowG, "lowG"); gL.down(lowL, "lowL"); gQ.down(lowQ, "lowQ"); gL2c.down(lowL2c, "lowL2c");
+    dInfo.down(info, 32 * (size_t)nitems); dTexp.down(texp, 4 * (size_t)nitems);
+    std::vector<int> hf(2 * (size_t)nitems); dFail.down(hf.data(), 8 * (size_t)nitems);
+    for (int i = 0; i < nitems; ++i) { lowfail[2 * i] = hf[i]; lowfail[2 * i + 1] = hf[nitems + i]; }
+}
+// gate_finish_kernel<T> alone, on what the SVD stage leaves: theta_i (ld x ncol rotated columns, ld = max, ncol = min of (r1 d1, r2 d2)), thetaV_i (ncol x ncol)
+void dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in, const int* texp, const void* theta, const void* thetaV, const double* lam1, const double* lam2,
+                     const int* idx1, const int* idx2, const void* GW1, const void* GW2, const int* maxdim, const double* cutoff, const int* normalize, const int* chi_cap,
+                     double* S, int* info_out, double* truncerr, void* X1, void* X2, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !dims || !info_in || !texp || !theta || !thetaV || !lam1 || !lam2 || !idx1 || !idx2 || !GW1 || !GW2 || !maxdim || !cutoff ||
+        !normalize || !chi_cap || !S || !info_out || !truncerr || !X1 || !X2 || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: bad arguments");
+    const bool F32 = dtype == TNQS_C64; const size_t esz = F32 ? 8 : 16;
+    std::vector<GateDims> gd(nitems);
+    Slots sTh, sTv, sLam1, sLam2, sIdx1, sIdx2, sW1, sW2; Guarded gS((size_t)guard * 8), gX1(guard * esz), gX2(guard * esz);
+    size_t i1 = 0, i2 = 0;
+    for (int i = 0; i < nitems; ++i) {
+        const GateDims g = gd[i] = gate_dims("dbg_gate_finish", dims, i);
+        const int r1 = info_in[4 * i], r2 = info_in[4 * i + 1], wide = info_in[4 * i + 2], K = info_in[4 * i + 3];
+        if (r1 < 1 || r1 > g.n1 || r2 < 1 || r2 > g.n2) throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: 1 <= r <= n");
+        const int Mr = r1 * g.d1, Nc = r2 * g.d2, ncol = std::min(Mr, Nc);
+        if ((wide != 0) != (Mr < Nc) || K < 0 || K > ncol || (K > 0 && wide) || chi_cap[i] < 1 || chi_cap[i] > std::min(g.Mr, g.Nc) || texp[i] < -120 || texp[i] > 120)
+            throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: inconsistent info / chi_cap / texp");
+        for (int a = 0; a < r1; ++a) if (idx1[i1 + a] < 0 || idx1[i1 + a] >= g.n1) throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: idx1 out of range");
+        for (int c = 0; c < r2; ++c) if (idx2[i2 + c] < 0 || idx2[i2 + c] >= g.n2) throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: idx2 out of range");
+        i1 += g.n1; i2 += g.n2;
+        sTh.add((size_t)Mr * Nc * esz); sTv.add((size_t)ncol * ncol * esz); sLam1.add((size_t)g.n1 * 8); sLam2.add((size_t)g.n2 * 8); sIdx1.add((size_t)g.n1 * 4); sIdx2.add((size_t)g.n2 * 4);
+        sW1.add((size_t)g.n1 * g.n1 * 16); sW2.add((size_t)g.n2 * g.n2 * 16);
+        gS.add((size_t)chi_cap[i] * 8); gX1.add((size_t)g.n1 * g.d1 * chi_cap[i] * esz); gX2.add((size_t)g.n2 * g.d2 * chi_cap[i] * esz);
+    }
+    need_gpu();
+    for (Slots* s : {&sTh, &sTv, &sLam1, &sLam2, &sIdx1, &sIdx2, &sW1, &sW2}) s->alloc();
+    gS.alloc(); gX1.alloc(); gX2.alloc();
+    put_all(sTh, theta); put_all(sTv, thetaV); put_all(sLam1, lam1); put_all(sLam2, lam2); put_all(sIdx1, idx1); put_all(sIdx2, idx2); put_all(sW1, GW1); put_all(sW2, GW2);
+    std::vector<int> hinfo(8 * (size_t)nitems, 0);
+    for (int i = 0; i < nitems; ++i) { hinfo[8 * i] = info_in[4 * i]; hinfo[8 * i + 1] = info_in[4 * i + 1]; hinfo[8 * i + 5] = info_in[4 * i + 2] ? 1 : 0; hinfo[8 * i + 7] = info_in[4 * i + 3];
+                                       hinfo[8 * i + 2] = info_out[2 * i]; hinfo[8 * i + 3] = info_out[2 * i + 1]; }
+    DBuf dInfo(32 * (size_t)nitems), dTexp(4 * (size_t)nitems), dTerr(8 * (size_t)nitems), dI(sizeof(GateItem) * nitems);
+    up_ints(dInfo, hinfo.data(), 8 * (size_t)nitems); up_ints(dTexp, texp, nitems); dTerr.up(truncerr, 8 * (size_t)nitems);
+    std::vector<GateItem> gitems(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        const GateDims& g = gd[i]; GateItem& it = gitems[i]; it = GateItem{};
+        it.GW1 = sW1.at(i); it.GW2 = sW2.at(i); it.n1 = g.n1; it.n2 = g.n2; it.d1 = g.d1; it.d2 = g.d2; it.chi = g.chi;
+        it.lam1 = (double*)sLam1.at(i); it.lam2 = (double*)sLam2.at(i); it.idx1 = (int*)sIdx1.at(i); it.idx2 = (int*)sIdx2.at(i);
+        it.theta = sTh.at(i); it.thetaV = sTv.at(i); it.X1 = gX1.at(i); it.X2 = gX2.at(i); it.S = (double*)gS.at(i);
+        it.info = (int*)dInfo.p + 8 * i; it.truncerr = (double*)dTerr.p + i; it.texp = (int*)dTexp.p + i;
+        it.maxdim = maxdim[i]; it.cutoff = cutoff[i]; it.normalize = normalize[i]; it.chi_cap = chi_cap[i];
+    }
+    dI.up(gitems.data(), sizeof(GateItem) * nitems);
+    for (Slots* s : {&sTh, &sTv, &sLam1, &sLam2, &sIdx1, &sIdx2, &sW1, &sW2}) s->up();
+    gS.up(S); gX1.up(X1); gX2.up(X2);
+    if (F32) launch_gate_finish<float>(nullptr, (const GateItem*)dI.p, nitems); else launch_gate_finish<double>(nullptr, (const GateItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gS.down(S, "S"); gX1.down(X1, "X1"); gX2.down(X2, "X2");
+    dInfo.down(hinfo.data(), 32 * (size_t)nitems); dTerr.down(truncerr, 8 * (size_t)nitems);
+    for (int i = 0; i < nitems; ++i) { info_out[2 * i] = hinfo[8 * i + 2]; info_out[2 * i + 1] = hinfo[8 * i + 3]; }
+}
+// qr2_rinv_kernel (stage 0: X1 only), then qr2_compose_kernel (stage 1), as second_pass() runs them.  n x n complex128 matrices per item
+void dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,
+             void* X1, void* GVout, void* GWout, int* rk, int guard) {
+    if (stage < 0 || stage > 1 || nitems < 1 || !n || !GW || !lam || !idx || !r || !X1 || guard < 0 || (stage == 1 && (!GV || !A2 || !V2 || !tau || !GVout || !GWout || !rk)))
+        throw Err(TNQS_ERR_INVALID, "dbg_qr2: bad arguments");
+    size_t io = 0;
+    for (int i = 0; i < nitems; ++i) {
+        if (n[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_qr2: n >= 1");
+        if (n[i] > 256) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_qr2: n > 256 (d*chi of a site the engine takes is at most 256)");
+        if (r[i] < 0 || r[i] > n[i]) throw Err(TNQS_ERR_INVALID, "dbg_qr2: 0 <= r <= n");
+        for (int a = 0; a < r[i]; ++a) if (idx[io + a] < 0 || idx[io + a] >= n[i]) throw Err(TNQS_ERR_INVALID, "dbg_qr2: idx out of range");
+        io += n[i];
+    }
+    need_gpu();
+    Slots sW, sV, sLam, sIdx, sA2, sV2; Guarded gX((size_t)guard * 16), gGV((size_t)guard * 16), gGW((size_t)guard * 16);
+    for (int i = 0; i < nitems; ++i) {
+        const size_t nn = (size_t)n[i] * n[i] * 16;
+        sW.add(nn); sV.add(nn); sA2.add(nn); sV2.add(nn); sLam.add((size_t)n[i] * 8); sIdx.add((size_t)n[i] * 4); gX.add(nn); gGV.add(stage ? nn : 0); gGW.add(stage ? nn : 0);
+    }
+    for (Slots* s : {&sW, &sV, &sLam, &sIdx, &sA2, &sV2}) s->alloc();
+    gX.alloc(); gGV.alloc(); gGW.alloc();
+    put_all(sW, GW); put_all(sLam, lam); put_all(sIdx, idx);
+    if (stage) { put_all(sV, GV); put_all(sA2, A2); put_all(sV2, V2); }
+    DBuf dR(4 * (size_t)nitems), dRk(4 * (size_t)nitems); up_ints(dR, r, nitems); if (stage) up_ints(dRk, rk, nitems);
+    std::vector<Qr2RinvItem> ri(nitems); std::vector<Qr2ComposeItem> ci(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        ri[i] = Qr2RinvItem{sW.at(i), (const double*)sLam.at(i), (const int*)sIdx.at(i), (const int*)dR.p + i, n[i], gX.at(i)};
+        ci[i] = Qr2ComposeItem{sA2.at(i), sV2.at(i), gX.at(i), sV.at(i), (const double*)sLam.at(i), (const int*)sIdx.at(i), (const int*)dR.p + i, n[i], stage ? tau[i] : 0.0,
+                               gGV.at(i), gGW.at(i), (int*)dRk.p + i};
+    }
+    DBuf dRi(sizeof(Qr2RinvItem) * nitems), dCi(sizeof(Qr2ComposeItem) * nitems);
+    dRi.up(ri.data(), sizeof(Qr2RinvItem) * nitems); dCi.up(ci.data(), sizeof(Qr2ComposeItem) * nitems);
+    for (Slots* s : {&sW, &sV, &sLam, &sIdx, &sA2, &sV2}) s->up();
+    gX.up(X1); if (stage) { gGV.up(GVout); gGW.up(GWout); }
+    launch_qr2_rinv(nullptr, (const Qr2RinvItem*)dRi.p, nitems);
+    if (stage) launch_qr2_compose(nullptr, (const Qr2ComposeItem*)dCi.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gX.down(X1, "X1");
+    if (stage) { gGV.down(GVout, "GVout"); gGW.down(GWout, "GWout"); dRk.down(rk, 4 * (size_t)nitems); }
+}
+// small_svd_prepare_kernel<T> -> launch_jacobi<double> -> small_svd_finish_kernel on site tensors [d][low][chi_b][hi] (shape: 4 ints per item) with low * hi < d * chi_b
+void dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !shape || !src || !GA || !GV || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_small_svd: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sSrc, sM; Guarded gA((size_t)guard * 16), gV((size_t)guard * 16);
+    for (int i = 0; i < nitems; ++i) {
+        const int d = shape[4 * i], lo = shape[4 * i + 1], cb = shape[4 * i + 2], hi = shape[4 * i + 3];
+        if (d < 1 || lo < 1 || cb < 1 || hi < 1) throw Err(TNQS_ERR_INVALID, "dbg_small_svd: dimensions >= 1");
+        const long long n = (long long)d * cb, N = (long long)lo * hi;
+        if (!(N < n && n <= 256)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_small_svd: the small-SVD route takes sites with fewer fibers than columns (low*hi < d*chi_b <= 256)");
+        sSrc.add((size_t)(n * N) * esz); sM.add((size_t)(n * N) * 16); gA.add((size_t)(n * n) * 16); gV.add((size_t)(n * n) * 16);
+    }
+    need_gpu();
+    sSrc.alloc(); sM.alloc(); gA.alloc(); gV.alloc();
+    put_all(sSrc, src);
+    std::vector<SmallSvdItem> si; std::vector<JacobiItem> sji;
+    for (int i = 0; i < nitems; ++i) {
+        const int d = shape[4 * i], lo = shape[4 * i + 1], cb = shape[4 * i + 2], hi = shape[4 * i + 3];
+        si.push_back(SmallSvdItem{sSrc.at(i), sM.at(i), gA.at(i), gV.at(i), d, lo, cb, hi});
+        sji.push_back(JacobiItem{sM.at(i), nullptr, d * cb, lo * hi, nullptr});
+    }
+    DBuf dS(sizeof(SmallSvdItem) * nitems), dJ(sizeof(JacobiItem) * nitems);
+    dS.up(si.data(), sizeof(SmallSvdItem) * nitems); dJ.up(sji.data(), sizeof(JacobiItem) * nitems);
+    sSrc.up(); sM.up(); gA.up(GA); gV.up(GV);
+    const SmallSvdItem* ds = (const SmallSvdItem*)dS.p; const JacobiItem* dj = (const JacobiItem*)dJ.p;
+    // engine_gates.cpp launch_small_svd
+    if (dtype == TNQS_C64) launch_small_svd_prepare<float>(nullptr, ds, nitems); else launch_small_svd_prepare<double>(nullptr, ds, nitems);
+    size_t lds = 0; for (auto& j : sji) lds = std::max(lds, jacobi_lds_bytes(j.m, j.n, false, 16));
+    launch_jacobi<double>(nullptr, dj, nitems, 60, jacobi_lds(lds), mmax_of(sji));
+    launch_small_svd_finish(nullptr, ds, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    sM.down("M"); gA.down(GA, "GA"); gV.down(GV, "GV");
 }
 }  // namespace tnqs

@@ -197,8 +197,8 @@ static std::vector<Gate2> absorb_pending(const State* s, const std::vector<Gate2
 
 // the gate as an operator sum g = sum_k a_k (x) b_k: O[(s1',s1),(s2',s2)] = g[(s1' s2'),(s1 s2)] factorised by elimination with complete pivoting
 // (exact rank factorisation).  Returns kappa, the operator Schmidt rank (2 for Rzz / Rxx / CNOT / CPHASE, 4 for SWAP); fa gets the kappa columns a_k
-// (d1^2 each), fb the kappa rows b_k (d2^2 each)
-static int operator_sum(const double* mat, int d1, int d2, std::vector<std::complex<double>>& fa, std::vector<std::complex<double>>& fb) {
+// (d1^2 each), fb the kappa rows b_k (d2^2 each).  (Declared in engine_internal.hpp: debug.cpp dbg_gate_theta / dbg_operator_sum call it too.)
+int operator_sum(const double* mat, int d1, int d2, std::vector<std::complex<double>>& fa, std::vector<std::complex<double>>& fb) {
     const int dd = d1 * d2, na = d1 * d1, nb = d2 * d2;
     std::vector<std::complex<double>> O((size_t)na * nb);
     const std::complex<double>* gm = reinterpret_cast<const std::complex<double>*>(mat);
@@ -399,7 +399,7 @@ template <class T> struct TwoSiteBatch {
         for (size_t q = 0; q < own_idx.size(); ++q) gauged_of[own_idx[q]] = chains[q].result;
     }
 
-    // the small-SVD items of site i (its n x N matricised psi~ goes to a fresh M)
+    // the small-SVD items of site i (its n x N matricised psi~ goes to a fresh M); debug.cpp dbg_small_svd fills the same two items
     void add_small_svd(size_t i, std::vector<SmallSvdItem>& si, std::vector<JacobiItem>& sji) {
         const int n = nof(i); const size_t Nout = sj[i].sd.n / (size_t)n;
         Buf M = dalloc(s, (size_t)n * Nout * 16); s->keepalive.push_back(M);
@@ -538,6 +538,7 @@ template <class T> struct TwoSiteBatch {
     }
 
     // ---- 4. theta = gate . (R1 R2), SVD, truncation, X1 / X2  (simple_update.jl:51-59): the per-gate workspaces and GateItems -------------
+    // (debug.cpp dbg_gate_theta / dbg_gate_finish fill GateItems by the same rules for the kernel-level tests: keep the two in step)
     void gate_items() {
         ws.resize(ng); gitems.resize(pg.size());
         for (int gi = 0; gi < ng; ++gi) {
@@ -635,6 +636,7 @@ template <class T> struct TwoSiteBatch {
         d_gitems = upload(s, gitems);       // (read again after the host synchronisations of the batch: a device copy, not upload_small)
     }
 
+    // (debug.cpp dbg_gate_theta issues the same launches in the same order)
     void run_theta() {
         HIPCHK(hipMemsetAsync(d_rb->p, 0, rb.terr, s->stream));       // info and both low-rank failure flag arrays (contiguous)
         ProfScope ps(s, TNQS_PROF_SMALL, 0, 0);
@@ -748,7 +750,7 @@ template <class T> struct TwoSiteBatch {
     // so R = R2 R1 is as accurate as a Householder R.  
     // Sharded: the owner of a site forms Q1 and its Gram matrix, one more all-gather (same slots as the first Gram exchange, issued
     // by every rank whether or not it has a flagged site -- it is a collective) hands it to the partner rank, and both compose the
-    // same factor from the same inputs.
+    // same factor from the same inputs.  (debug.cpp dbg_qr2 fills Qr2RinvItem / Qr2ComposeItem as this does.)
     void second_pass() {
         std::vector<size_t> rs; std::vector<int> rq;
         for (int q = 0; q < npg; ++q) for (int side = 0; side < 2; ++side) {

@@ -247,6 +247,8 @@ inline SD site_dims(const State* s, int v) {
 // number of elements of a site tensor (no allocation: site_dims builds a vector)
 inline size_t site_nelem(const State* s, int v) { size_t n = (size_t)s->d[v]; for (int e : s->g->nbr_e[v]) n *= (size_t)s->chi[e]; return n; }
 inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
+// the two-site gate as an operator sum g = sum_k a_k (x) b_k (engine_gates.cpp): returns kappa; fa: kappa x d1^2, fb: kappa x d2^2 numbers, appended
+int operator_sum(const double* mat, int d1, int d2, std::vector<std::complex<double>>& fa, std::vector<std::complex<double>>& fb);
 void exchange(State* s, size_t bytes_per_rank);                       // sharding.cpp
 void check_exchange(const State* s, size_t bytes_per_rank);           // call BEFORE enqueuing anything that writes into s->exch
 

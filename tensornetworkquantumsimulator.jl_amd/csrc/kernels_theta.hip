@@ -207,7 +207,8 @@ __global__ __launch_bounds__(1024) void lowrank_g_kernel(const GateItem* __restr
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * ti + kq + 4 * r, j = 16 * tj + l15;
-            if (i < K && j < K && i <= j) { LG[i + (size_t)K * j] = cmake<double>(cr[r], ci[r]); if (i != j) LG[j + (size_t)K * i] = cmake<double>(cr[r], -ci[r]); }
+            // (the diagonal's imaginary part is zero in exact arithmetic; its two sums of products round differently, so it is written as zero: G is Hermitian exactly)
+            if (i < K && j < K && i <= j) { LG[i + (size_t)K * j] = cmake<double>(cr[r], i == j ? 0.0 : ci[r]); if (i != j) LG[j + (size_t)K * i] = cmake<double>(cr[r], -ci[r]); }
         }
     }
 }
