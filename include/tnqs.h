@@ -258,6 +258,24 @@ int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uin
  * TNQS_ERR_INVALID: a list that is not a cycle of the graph; TNQS_ERR_UNSUPPORTED: sharded handles, vertex degree > 7. */
 int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im);
 
+/* ---- overlap of two states ---------------------------------------------------------------------------------------
+ * inner(psi, phi; alg = "bp") (src/inner.jl:65-69): BP on BilinearForm(ket, bra).  out_log_re_im = the reference's freenergy
+ * (complex log of the overlap, imaginary part in (-pi, pi]); the overlap is its exp.  Neither handle's messages are read or written.
+ * The conjugate is on the SECOND argument: the value is sum psi conj(phi), what the reference's code computes (bra = dag(prime(phi))) whatever its docstring says.
+ * The two handles share graph (vertex and edge lists as given to tnqs_create), CURRENT site dimensions, element type and device; bond dimensions are free per handle
+ * and edge, up to 64.  The form's messages are chi_ket(e) x chi_bra(e) matrices m[a + chi_ket b] that live in buffers of the call, the rectangular delta to begin with;
+ * sweeps are Gauss-Seidel over the sequence of bp_opts, exactly as tnqs_bp_update runs them (same default sequence, same level schedule), every message absorbed on the
+ * ket's side; message_diff is averaged over the sequence.  opts == NULL: the reference's defaults for a bare `update` of the form cache -- maxiter 25 (1 on a tree), NO
+ * tolerance, default sequence (a NaN tolerance in opts selects 1e-5 / 1e-8 as in tnqs_bp_update).  Without a tolerance the host is not consulted between sweeps and
+ * *final_diff is the last sweep's average; with one there is one read-back per sweep.  Non-convergence is not an error: *niter == maxiter, *final_diff returned.
+ * Scalars are f64 whatever the element type: log z = sum_v log(vertex scalar) - sum_e log(edge scalar), complex logs.  A vertex or edge scalar that is exactly zero
+ * gives (-inf, 0) (the reference's free energy is -Inf, the overlap 0); a NaN or infinite scalar is TNQS_ERR_NUMERIC.  ket == bra is allowed.  Deferred one-site gates
+ * of both handles are applied first (as tnqs_rdm_1site does), pending scale factors are honoured; the work runs on the ket's stream, behind whatever the bra's holds.
+ * TNQS_ERR_UNSUPPORTED: a sharded handle, a bond dimension above 64 (the rectangular Gram kernel takes 1..64; there is no scalar form);
+ * TNQS_ERR_INVALID: different vertex / edge lists, site dimensions, element types or devices, a null pointer -- all before any device work.
+ * niter, final_diff may be NULL. */
+int tnqs_inner_bp(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff);
+
 /* ---- multi-GPU sharding (no reference analogue).  A rank owns a vertex subset: it holds only
  *      those site tensors and does all per-vertex work for them; messages are replicated.  The library calls
  *      the host-supplied all-gather at the exchange points (host side: torch.distributed over RCCL). --------- */

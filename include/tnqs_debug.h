@@ -210,6 +210,23 @@ int tnqs_dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void
 /* small_svd_prepare_kernel<T> -> the f64 Jacobi -> small_svd_finish_kernel on site tensors [d][low][chi_b][hi] of type T (shape: 4 ints per item) with N = low hi < n = d chi_b <= 256
  * (else TNQS_ERR_UNSUPPORTED): GA, GV (n x n complex128): column j < N of GV = left singular vector u_j of M[(s,b), outer] = conj(psi), GA[:, j] = sigma_j^2 u_j; columns >= N zero */
 int tnqs_dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard);
+/* ---- overlap of two states (csrc/kernels_inner.hip, csrc/engine_inner.cpp; dtype 0 c64, 1 c128) ----
+ * inner_gram_kernel<T> followed by inner_finalize_kernel<T> with normalize = 0 (the chunk sum), ONE launch each over nitems items set up as engine_inner.cpp sets them up.
+ * shape: (PA, Ka, Kb, PB) per item; X: the items' [PA][Ka][PB] arrays one after the other, Y likewise with Kb (Y == NULL: Y = X, every item then needs Ka == Kb).
+ * out_i[a + Ka b] = sum_{p, q} X_i[p, a, q] conj(Y_i[p, b, q]) in the element type, laid out as guard, item 0 (Ka Kb numbers), guard, item 1, ..., guard: it goes up as the
+ * caller filled it and comes back whole; the partials are guarded on the device as well.  max_chunks <= 0: the engine's chunking, else at most that many chunks per item;
+ * nchunks_out[i] (may be NULL): the chunks item i was summed from.  route_out (may be NULL): TNQS_DBG_ROUTE_INNER_MFMA.  A dimension outside 1..64: TNQS_ERR_UNSUPPORTED
+ * (there is no scalar form), nothing is written */
+#define TNQS_DBG_ROUTE_INNER_MFMA 9    /* inner_gram_kernel<T>: v_mfma_f32_16x16x4_f32 (c64) / v_mfma_f64_16x16x4_f64 (c128) */
+int tnqs_dbg_inner_gram(int dtype, int nitems, const int* shape, const void* X, const void* Y, void* out, int max_chunks, int* nchunks_out, int guard, int* route_out);
+/* inner_finalize_kernel<T>, ONE launch over nitems messages.  Item i: nchunks[i] partials of rows[i] cols[i] numbers of the element type laid out [chunk][a + rows b], the
+ * items one after the other; new_msg_i = their f64 sum, divided by its element sum when normalize[i] != 0 and that sum is not exactly zero; diff_out[i] =
+ * message_diff(new_msg_i, old_msg_i) (the rectangular delta where has_old[i] == 0 or old_msg == NULL); sum_out[2 i, 2 i + 1] = the raw element sum.  new_msg: guard, item 0,
+ * guard, ..., guard as above.  rows or cols outside 1..64: TNQS_ERR_UNSUPPORTED, nothing is written */
+int tnqs_dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols, const int* nchunks, const void* partials, const void* old_msg, const int* has_old,
+                            const int* normalize, void* new_msg, double* diff_out, double* sum_out, int guard);
+/* tnqs_inner_bp with the bound on a batch's chain workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of messages it ran */
+int tnqs_dbg_inner_bp_ws(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, int64_t workspace_bytes, int* nbatches_out);
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ reference repo):
   maxvirtualdim                                                           src/TensorNetworks/abstracttensornetwork.jl:27-29
   sample(psi, nsamples; alg = "bp")                                       src/sampling.jl:3-46
   norm_sqr / norm (alg = "bp", "loopcorrections"), loopcorrected_partitionfunction   src/norm_sqr.jl:10-18,62-78, src/MessagePassing/loopcorrection.jl:3-14
+  inner / log_inner (alg = "bp")                                          src/inner.jl:65-69, src/Forms/bilinearform.jl:16-25
 Every flop runs in libtnqs_hip.so; this file only marshals arguments through the C ABI (include/tnqs.h)."""
 from __future__ import annotations
 
@@ -1048,6 +1049,48 @@ def norm_sqr(x, alg: str, max_configuration_size: Optional[int] = None, cache_up
 def norm(x, alg: str, **kwargs) -> complex:
     """norm = sqrt(norm_sqr) (src/norm_sqr.jl:80-81)"""
     return complex(np.sqrt(complex(norm_sqr(x, alg, **kwargs))))
+
+
+def _site_dims_of(x) -> list:
+    if isinstance(x, TensorNetworkState):
+        return [x.tensors[v].shape[0] for v in x.graph.vertices]
+    return [x._site_dim(v) for v in x.graph.vertices]
+
+
+def log_inner(psi, phi, alg: str = "bp", cache_update_kwargs: Optional[dict] = None, device: int = 0, info: Optional[dict] = None) -> complex:
+    """log of inner(psi, phi; alg = "bp") (src/inner.jl:65-69): belief propagation on BilinearForm(psi, phi), the reference's freenergy of the form cache -- a complex
+    number whose imaginary part lies in (-pi, pi]; the overlap of two un-normalised states on a large lattice overflows a double, its log does not.  The conjugate is on
+    the SECOND argument, sum psi conj(phi): the reference's docstring says <psi|phi>, its code builds bra = dag(prime(phi)), and the code is what this follows.
+    psi, phi: a TensorNetworkState (uploaded to a temporary handle on `device`) or a BeliefPropagationCache, whose network is used as it stands on its handle -- nothing
+    is uploaded, its own messages are neither read nor changed, and `device` is not used for it.  Same graph and site dimensions; bond dimensions are free per state.
+    cache_update_kwargs: maxiter, tolerance, edge_sequence (and normalize) as `update` takes them; omitted: the reference's defaults for a bare `update` of the form
+    cache -- maxiter 25 (1 on a tree), no tolerance, the default sequence.  info (optional dict) receives niter, diff and converged.  (-inf + 0j: the overlap is 0.)"""
+    if alg != "bp":
+        raise L.TnqsError(f'inner: algorithm choice not supported; supported on the HIP path: "bp" (received {alg!r})')
+    for x in (psi, phi):
+        if not isinstance(x, (TensorNetworkState, BeliefPropagationCache)):
+            raise TypeError("inner: expected a TensorNetworkState or a BeliefPropagationCache")
+    ga, gb = psi.graph, phi.graph
+    if list(ga.vertices) != list(gb.vertices) or [tuple(e) for e in ga.edges] != [tuple(e) for e in gb.edges]:
+        raise L.TnqsArgumentError("inner: the two states must live on the same graph (same vertices and edges in the same order)")
+    if _site_dims_of(psi) != _site_dims_of(phi):
+        raise L.TnqsArgumentError("inner: the two states must have the same site dimensions")
+    if np.dtype(psi.dtype) != np.dtype(phi.dtype):
+        raise L.TnqsArgumentError(f"inner: the two states must have the same element type (received {np.dtype(psi.dtype)} and {np.dtype(phi.dtype)})")
+    o, keep = _bp_opts(ga, {} if cache_update_kwargs is None else cache_update_kwargs)
+    ket = psi if isinstance(psi, BeliefPropagationCache) else BeliefPropagationCache(psi, device=device)
+    bra = ket if phi is psi else (phi if isinstance(phi, BeliefPropagationCache) else BeliefPropagationCache(phi, device=device))
+    out = np.zeros(2, dtype=np.float64)
+    niter, diff = C.c_int(), C.c_double()
+    L.check(L.lib.tnqs_inner_bp(ket._h, bra._h, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(niter), C.byref(diff)))
+    if info is not None:
+        info.update(niter=niter.value, diff=diff.value, converged=bool(o.tolerance >= 0 and diff.value <= o.tolerance))
+    return complex(out[0], out[1])
+
+
+def inner(psi, phi, alg: str = "bp", cache_update_kwargs: Optional[dict] = None, device: int = 0, info: Optional[dict] = None) -> complex:
+    """inner(psi, phi; alg = "bp") = exp(log_inner(...)) = sum psi conj(phi) in the BP approximation (exact on trees); see log_inner for the arguments"""
+    return complex(np.exp(log_inner(psi, phi, alg=alg, cache_update_kwargs=cache_update_kwargs, device=device, info=info)))
 
 
 def site_probabilities(bpc: BeliefPropagationCache, v) -> np.ndarray:

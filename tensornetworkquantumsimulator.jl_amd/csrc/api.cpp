@@ -141,6 +141,9 @@ int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int3
 int tnqs_rdm_paths(tnqs_handle h, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out_rho) {
     return guard([&] { rdm_paths(S(h), npaths, path_len, path_verts, out_rho); });
 }
+int tnqs_inner_bp(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff) {
+    return guard([&] { inner_bp(S(ket), S(bra), opts, out_log_re_im, niter, final_diff); });
+}
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out) {
     return guard([&] { if (!ops || !out) throw Err(TNQS_ERR_INVALID, "expect_all: null"); expect_all(S(h), ops, out); });
 }
@@ -250,6 +253,9 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                  void dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,
                               void* X1, void* GVout, void* GWout, int* rk, int guard);
                  void dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard);
+                 void dbg_inner_gram(int dtype, int nitems, const int* shape, const void* X, const void* Y, void* out, int max_chunks, int* nchunks_out, int guard, int* route);
+                 void dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols, const int* nchunks, const void* partials, const void* old_msg, const int* has_old,
+                                         const int* normalize, void* new_msg, double* diff, double* sum, int guard);
                  double dbg_pending_scale(State* s, int v); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
@@ -401,5 +407,16 @@ int tnqs_dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void
 }
 int tnqs_dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard_elems) {
     return guard([&] { dbg_small_svd(dtype, nitems, shape, src, GA, GV, guard_elems); });
+}
+int tnqs_dbg_inner_gram(int dtype, int nitems, const int* shape, const void* X, const void* Y, void* out, int max_chunks, int* nchunks_out, int guard_elems, int* route_out) {
+    return guard([&] { dbg_inner_gram(dtype, nitems, shape, X, Y, out, max_chunks, nchunks_out, guard_elems, route_out); });
+}
+int tnqs_dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols, const int* nchunks, const void* partials, const void* old_msg, const int* has_old,
+                            const int* normalize, void* new_msg, double* diff_out, double* sum_out, int guard_elems) {
+    return guard([&] { dbg_inner_finalize(dtype, nitems, rows, cols, nchunks, partials, old_msg, has_old, normalize, new_msg, diff_out, sum_out, guard_elems); });
+}
+int tnqs_dbg_inner_bp_ws(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, int64_t workspace_bytes, int* nbatches_out) {
+    return guard([&] { if (workspace_bytes < 1) throw Err(TNQS_ERR_INVALID, "dbg_inner_bp_ws: the workspace bound must be positive");
+                       inner_bp(S(ket), S(bra), opts, out_log_re_im, niter, final_diff, (size_t)workspace_bytes, nbatches_out); });
 }
 }

@@ -1383,4 +1383,71 @@ void dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, voi
     HIPCHK(hipDeviceSynchronize());
     sM.down("M"); gA.down(GA, "GA"); gV.down(GV, "GV");
 }
+
+// ---- overlap of two states (kernels_inner.hip), the descriptors filled as engine_inner.cpp run_batch fills them -----------------------------------------------
+// ONE launch_inner_gram<T> over nitems items (PA, Ka, Kb, PB), then launch_inner_finalize<T> with normalize = 0 as the chunk sum
+void dbg_inner_gram(int dtype, int nitems, const int* shape, const void* X, const void* Y, void* out, int max_chunks, int* nchunks_out, int guard, int* route) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !shape || !X || !out || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_inner_gram: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sX, sY, sP; Guarded gO((size_t)guard * esz);
+    std::vector<InnerGramItem> gi(nitems); std::vector<int> npart(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        const int* q = shape + 4 * i;
+        if (q[0] < 1 || q[1] < 1 || q[2] < 1 || q[3] < 1 || (long long)q[0] * q[3] > INT_MAX / 64) throw Err(TNQS_ERR_INVALID, "dbg_inner_gram: bad shape");
+        if (!inner_gram_covers(q[1], q[2])) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_inner_gram: the rectangular Gram takes 1 <= Ka, Kb <= 64");
+        if (!Y && q[1] != q[2]) throw Err(TNQS_ERR_INVALID, "dbg_inner_gram: Y == X needs Ka == Kb");
+        gi[i] = InnerGramItem{}; gi[i].PA = q[0]; gi[i].Ka = q[1]; gi[i].Kb = q[2]; gi[i].PB = q[3];
+        sX.add((size_t)q[0] * q[1] * q[3] * esz); if (Y) sY.add((size_t)q[0] * q[2] * q[3] * esz); gO.add((size_t)q[1] * q[2] * esz);
+    }
+    need_gpu();
+    const int chunks = plan_inner_gram(gi.data(), nitems, esz, max_chunks, npart.data());
+    for (int i = 0; i < nitems; ++i) sP.add((size_t)npart[i] * gi[i].Ka * gi[i].Kb * esz);
+    sX.alloc(); if (Y) sY.alloc(); sP.alloc(); gO.alloc();
+    put_all(sX, X); if (Y) put_all(sY, Y);
+    std::vector<InnerFinalItem> fi(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        gi[i].X = sX.at(i); gi[i].Y = Y ? sY.at(i) : sX.at(i); gi[i].partial = sP.at(i);
+        fi[i] = InnerFinalItem{sP.at(i), npart[i], gi[i].Ka, gi[i].Kb, nullptr, gO.at(i), nullptr, nullptr, 0};
+    }
+    DBuf dG(sizeof(InnerGramItem) * nitems), dF(sizeof(InnerFinalItem) * nitems);
+    dG.up(gi.data(), sizeof(InnerGramItem) * nitems); dF.up(fi.data(), sizeof(InnerFinalItem) * nitems);
+    sX.up(); if (Y) sY.up(); sP.up(); gO.up(out);
+    if (dtype == TNQS_C64) { launch_inner_gram<float>(nullptr, (const InnerGramItem*)dG.p, nitems, chunks); launch_inner_finalize<float>(nullptr, (const InnerFinalItem*)dF.p, nitems); }
+    else { launch_inner_gram<double>(nullptr, (const InnerGramItem*)dG.p, nitems, chunks); launch_inner_finalize<double>(nullptr, (const InnerFinalItem*)dF.p, nitems); }
+    HIPCHK(hipDeviceSynchronize());
+    sP.down("the Gram partials"); gO.down(out, "out");
+    if (nchunks_out) std::copy(npart.begin(), npart.end(), nchunks_out);
+    if (route) *route = TNQS_DBG_ROUTE_INNER_MFMA;
+}
+// ONE launch_inner_finalize<T> over nitems messages of rows[i] x cols[i]
+void dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols, const int* nchunks, const void* partials, const void* old_msg, const int* has_old,
+                        const int* normalize, void* new_msg, double* diff, double* sum, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !rows || !cols || !nchunks || !partials || !normalize || !new_msg || (old_msg && !has_old) || guard < 0)
+        throw Err(TNQS_ERR_INVALID, "dbg_inner_finalize: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sP, sOld; Guarded gN((size_t)guard * esz);
+    for (int i = 0; i < nitems; ++i) {
+        if (rows[i] < 1 || cols[i] < 1 || nchunks[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_inner_finalize: rows, cols, nchunks >= 1");
+        if (!inner_gram_covers(rows[i], cols[i])) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_inner_finalize: rows, cols <= 64");
+        const size_t mb = (size_t)rows[i] * cols[i] * esz;
+        sP.add(mb * nchunks[i]); sOld.add(mb); gN.add(mb);
+    }
+    need_gpu();
+    sP.alloc(); sOld.alloc(); gN.alloc();
+    put_all(sP, partials);
+    DBuf dD(sizeof(double) * nitems), dS(sizeof(double) * 2 * nitems), dF(sizeof(InnerFinalItem) * nitems);
+    std::vector<InnerFinalItem> fi(nitems);
+    size_t om = 0;
+    for (int i = 0; i < nitems; ++i) {
+        const bool old = old_msg && has_old[i]; if (old) sOld.put(i, (const char*)old_msg + om);
+        om += sOld.len[i];
+        fi[i] = InnerFinalItem{sP.at(i), nchunks[i], rows[i], cols[i], old ? sOld.at(i) : nullptr, gN.at(i), diff ? (double*)dD.p + i : nullptr, sum ? (double*)dS.p + 2 * i : nullptr, normalize[i]};
+    }
+    sP.up(); sOld.up(); gN.up(new_msg); dF.up(fi.data(), sizeof(InnerFinalItem) * nitems);
+    if (dtype == TNQS_C64) launch_inner_finalize<float>(nullptr, (const InnerFinalItem*)dF.p, nitems); else launch_inner_finalize<double>(nullptr, (const InnerFinalItem*)dF.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gN.down(new_msg, "new_msg");
+    if (diff) dD.down(diff, sizeof(double) * nitems);
+    if (sum) dS.down(sum, sizeof(double) * 2 * nitems);
+}
 }  // namespace tnqs

@@ -234,6 +234,10 @@ void rdm_edges(State* s, int n_edges, const int32_t* eu, const int32_t* ev, doub
 // engine_paths.cpp: un-normalised two-site reduced density matrices of the ends of induced paths: for path q, for k = 1 .. path_len[q] - 1, the (d_p0 d_pk)^2 complex128
 // matrix of (p_0, p_k), one after the other; workspace_bytes: bound on a batch's workspace (0: min(2 GiB, a quarter of the free device memory)); nbatches (may be null): batches run
 void rdm_paths(State* s, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out_rho, size_t workspace_bytes = 0, int* nbatches = nullptr);
+// engine_inner.cpp: inner(psi, phi; alg = "bp") -- BP on the bilinear form of two handles (same graph, site dimensions, element type and device; free bond dimensions
+// up to 64); out_log_re_im = log z with the imaginary part in (-pi, pi] ((-inf, 0) when a scalar is exactly zero); opts == null: maxiter 25 (1 on a tree), no tolerance,
+// default sequence; workspace_bytes: bound on the chain temporaries of a batch of messages (0: min(2 GiB, a quarter of the free device memory)); nbatches (may be null)
+void inner_bp(State* ket, State* bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, size_t workspace_bytes = 0, int* nbatches = nullptr);
 void prof_collect(State* s);
 void materialize_pending_all(State* s);      // apply every deferred one-site gate (State::pend1)
 // sharding.cpp

@@ -12,6 +12,7 @@
 //   engine_loops.cpp  loop corrections: transfer matrices of simple cycles, ring products, traces (batched)
 //   engine_rdm.cpp    two-site reduced density matrices of bonds (batched chains + Grams, one contraction kernel)
 //   engine_paths.cpp  two-site reduced density matrices of the ends of paths (environments, transfer matrices, the sweep along the path)
+//   engine_inner.cpp  overlap of two states: BP on the bilinear form (rectangular messages, mode products that change a leg's dimension, form scalars)
 //   sharding.cpp      exchange step (RCCL or host callback)
 // and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
@@ -23,6 +24,7 @@
 //   kernels_theta.hip  per-gate small algebra: gate_eigs .. gate_finish  kernels_sample.hip sampling
 //   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, antiprojector, trace
 //   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs), environment through a transfer matrix (path RDMs)
+//   kernels_inner.hip  overlap of two states: rectangular two-operand Gram (f32 / f64 matrix cores), bilinear message epilogue, form scalars
 #pragma once
 #include "engine.hpp"
 #include "kernels.hpp"

@@ -355,6 +355,22 @@ constexpr int kPathApplyTargetWgs = 256;    // a launch aims at one workgroup pe
 // sets nrb, wg_begin and -- where it is 0 -- ksplit = clamp(ceil(256 / row blocks of the launch), 1, min(16, chi_a^2 / 64)); returns the launch's workgroups
 int plan_path_apply(PathApplyItem* it, int n);
 template <class P, class T> void launch_path_apply(hipStream_t s, const PathApplyItem* d_items, int nitems, int total_wgs);
+// ---- overlap of two states (kernels_inner.hip; engine_inner.cpp) --------------------------------------------------------------------------------------------------
+// rectangular two-operand Gram on the matrix cores: partial[c][a + Ka b] = sum over chunk c of the contracted range (p, q) of X[p, a, q] conj(Y[p, b, q]),
+// X = [PA][Ka][PB], Y = [PA][Kb][PB] (complex<T>; partials complex<T>: f32 accumulation for ComplexF32, as the BP message Gram).  1 <= Ka, Kb <= 64; nothing else is taken
+struct InnerGramItem { const void* X; const void* Y; void* partial; int PA, Ka, Kb, PB; int chunk_begin, nchunks, blocks_per_chunk; };
+inline bool inner_gram_covers(int Ka, int Kb) { return Ka >= 1 && Ka <= 64 && Kb >= 1 && Kb <= 64; }
+int plan_inner_gram(InnerGramItem* it, int n, size_t esz, int max_chunks, int* npart);      // max_chunks <= 0: the engine's chunking; returns the launch's workgroups
+template <class T> void launch_inner_gram(hipStream_t s, const InnerGramItem* d_items, int nitems, int total_chunks);
+// epilogue of a rows x cols bilinear message (index a + rows b; rows, cols <= 64): new_msg = sum of the chunks (f64), divided by its element sum when normalize != 0
+// and that sum is not exactly zero; *diff_out = message_diff(new_msg, old_msg) (null old_msg: the rectangular delta); sum_out[0, 1] = the raw element sum.
+// diff_out / sum_out may be null
+struct InnerFinalItem { const void* partial; int nchunks, rows, cols; const void* old_msg; void* new_msg; double* diff_out; double* sum_out; int normalize; };
+template <class T> void launch_inner_finalize(hipStream_t s, const InnerFinalItem* d_items, int nitems);
+// out[0, 1] = (sum_ab m[a, b] mr[a, b]) * r * (*scale_a) * (*scale_b) in f64; a null message = the rectangular delta, a null scale = 1; r = the complex number at
+// rawsum when that pointer is set, normalize != 0 and the number is not exactly zero (m = raw / sum(raw): the product is then sum_ab raw[a, b] mr[a, b]), else 1
+struct InnerScalarItem { const void* m; const void* mr; int rows, cols; const double* rawsum; int normalize; const double* scale_a; const double* scale_b; double* out; };
+template <class T> void launch_inner_scalar(hipStream_t s, const InnerScalarItem* d_items, int nitems);
 // one-site gates on d = 2, ComplexF32: streaming 2x2 apply, norm partials [item][nbx]
 void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int nbx, double* d_norm_partials);
 
