@@ -645,23 +645,37 @@ void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fai
 // ---- the small-site BP message kernel and the message epilogue, set up as engine_bp.cpp sets them up --------------------------------------------------------
 namespace {
 // a device array of slots that start at 256-byte multiples (the engine's sub-buffers); the gaps keep a 0xff filling that is checked after the launch, so a
-// kernel that writes past its slot is reported instead of going unnoticed
+// kernel that writes past its slot is reported instead of going unnoticed.  Plain slots (no guard) are filled with put() and sent with up().
+// With guard_bytes the array is an output as the caller hands it over: guard band, item 0, guard band, item 1, ..., guard band.  On the device every item has the band
+// that follows it right behind it (the leading band right in front of item 0).  The whole array goes up as the caller filled it (up(src)) and comes back whole
+// (down(dst, what)), so a write outside an item shows in a guard band or is reported here
 struct Slots {
-    std::vector<size_t> off, len; std::vector<char> host; std::unique_ptr<DBuf> dev;
-    void add(size_t bytes) { off.push_back(total); len.push_back(bytes); total += round256(bytes); }
+    size_t gb, total; std::vector<size_t> off, len; std::vector<char> host; std::unique_ptr<DBuf> dev;
+    explicit Slots(size_t guard_bytes = 0) : gb(guard_bytes), total(round256(guard_bytes)) {}
+    void add(size_t bytes) { off.push_back(total); len.push_back(bytes); total += round256(bytes + gb); }
     void alloc() { host.assign(total ? total : 1, (char)0xff); dev.reset(new DBuf(total)); }
     void put(size_t i, const void* src) { std::memcpy(host.data() + off[i], src, len[i]); }
     void get(size_t i, void* dst) const { std::memcpy(dst, host.data() + off[i], len[i]); }
-    void up() { dev->up(host.data(), total); }
-    void down(const char* what) {
-        dev->down(host.data(), total);
-        for (size_t i = 0; i < off.size(); ++i)
-            for (size_t b = off[i] + len[i]; b < off[i] + round256(len[i]); ++b)
-                if (host[b] != (char)0xff) throw Err(TNQS_ERR_INVALID, std::string("dbg: a kernel wrote past the end of a slot of ") + what);
-    }
     char* at(size_t i) const { return (char*)dev->p + off[i]; }
-    size_t total = 0;
+    void up() { dev->up(host.data(), total); }
+    void up(const void* src) { caller(const_cast<void*>(src), false); up(); }
+    void down(const char* what) { fetch(std::string("dbg: a kernel wrote past the end of a slot of ") + what); }
+    void down(void* dst, const char* what) { fetch(std::string("dbg: a kernel wrote outside an item of ") + what); caller(dst, true); }
+private:
+    void fetch(const std::string& complaint) {
+        dev->down(host.data(), total);
+        auto gap = [&](size_t b0, size_t b1) { for (size_t b = b0; b < b1; ++b) if (host[b] != (char)0xff) throw Err(TNQS_ERR_INVALID, complaint); };
+        gap(0, round256(gb) - gb);
+        for (size_t i = 0; i < off.size(); ++i) gap(off[i] + len[i] + gb, off[i] + round256(len[i] + gb));
+    }
+    void caller(void* arr, bool out) {      // between the caller's contiguous array (bands included) and the slots
+        char* p = (char*)arr;
+        auto move = [&](char* h, size_t n) { if (out) std::memcpy(p, h, n); else std::memcpy(h, p, n); p += n; };
+        move(host.data() + round256(gb) - gb, gb);
+        for (size_t i = 0; i < off.size(); ++i) move(host.data() + off[i], len[i] + gb);
+    }
 };
+using Guarded = Slots;      // an output array with guard bands: Guarded g(guard_bytes)
 }
 // ONE launch_bp_small_site over nitems (site, outgoing leg) pairs (ComplexF32): item i is a site tensor [d[i]][chi_0]..[chi_{z[i]-1}] with the outgoing leg jo[i];
 // chi / present: the items' legs one after the other; psi: the items' tensors one after the other; M: one chi_k x chi_k matrix (M[q + chi_k qo]) per leg of every
@@ -684,7 +698,7 @@ void dbg_small_site(int nitems, const int* d, const int* z, const int* chi, cons
         for (int k = 0; k < z[i]; ++k) { if (c[k] < 1) throw Err(TNQS_ERR_INVALID, "dbg_small_site: leg dimension < 1"); n *= (size_t)c[k]; }
         if (!bp_small_site_covers(d[i], z[i], c, n)) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_small_site: site not covered by bp_small_site_kernel (z <= 8, chi <= 32, <= 8192 elements)");
         if (jo[i] < 0 || jo[i] >= z[i]) throw Err(TNQS_ERR_INVALID, "dbg_small_site: outgoing leg out of range");
-        bool all16 = (n % 256) == 0; for (int k = 0; k < z[i]; ++k) all16 = all16 && c[k] == 16;      // the engine's rule (engine_bp.cpp)
+        const bool all16 = bp_small_site_mfma_form(z[i], c, n);
         if (form == 1 && !all16) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_small_site: the matrix-core form takes sites whose legs are all 16-dimensional");
         SmallMsgItem& it = items[i]; it = SmallMsgItem{};
         it.d = d[i]; it.z = z[i]; it.jo = jo[i]; it.mfma = (form != 0 && all16) ? 1 : 0; it.normalize = normalize;
@@ -832,32 +846,6 @@ void dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const voi
 // env_prepare, env_finish; kernels_util.hip: diag, cscale): ONE launch over nitems items of different n, the descriptors filled as engine_obs.cpp / engine_gates.cpp
 // fill them.  Inputs: the items' arrays one after the other.  Outputs: `guard` caller-filled elements, item 0, `guard` elements, item 1, ..., `guard` elements ----
 namespace {
-// an output array as the caller hands it over.  On the device every item starts at a multiple of 256 bytes with the guard band that follows it right behind it (the
-// leading band right in front of item 0); the alignment gaps keep a 0xff filling that is checked after the launch.  The whole array goes up as the caller filled it
-// and comes back whole, so a write outside an item shows in a guard band or is reported here
-struct Guarded {
-    size_t gb, total; std::vector<size_t> off, len; std::vector<char> host; std::unique_ptr<DBuf> dev;
-    explicit Guarded(size_t guard_bytes) : gb(guard_bytes), total(round256(guard_bytes)) {}
-    void add(size_t bytes) { off.push_back(total); len.push_back(bytes); total += round256(bytes + gb); }
-    void alloc() { host.assign(total ? total : 1, (char)0xff); dev.reset(new DBuf(total)); }
-    char* at(size_t i) const { return (char*)dev->p + off[i]; }
-    void up(const void* src) {
-        const char* p = (const char*)src;
-        std::memcpy(host.data() + round256(gb) - gb, p, gb); p += gb;
-        for (size_t i = 0; i < off.size(); ++i) { std::memcpy(host.data() + off[i], p, len[i] + gb); p += len[i] + gb; }
-        dev->up(host.data(), total);
-    }
-    void down(void* dst, const char* what) {
-        dev->down(host.data(), total);
-        auto gap = [&](size_t b0, size_t b1) { for (size_t b = b0; b < b1; ++b) if (host[b] != (char)0xff)
-                                                   throw Err(TNQS_ERR_INVALID, std::string("dbg: a kernel wrote outside an item of ") + what); };
-        gap(0, round256(gb) - gb);
-        for (size_t i = 0; i < off.size(); ++i) gap(off[i] + len[i] + gb, off[i] + round256(len[i] + gb));
-        char* p = (char*)dst;
-        std::memcpy(p, host.data() + round256(gb) - gb, gb); p += gb;
-        for (size_t i = 0; i < off.size(); ++i) { std::memcpy(p, host.data() + off[i], len[i] + gb); p += len[i] + gb; }
-    }
-};
 // input arrays: the items one after the other on the host, 256-byte aligned slots on the device
 void put_all(Slots& s, const void* src) { const char* p = (const char*)src; for (size_t i = 0; i < s.off.size(); ++i) { s.put(i, p); p += s.len[i]; } }
 void post_check(const char* who, int dtype, int nitems, const int* n, int guard) {
@@ -1107,19 +1095,24 @@ double dbg_pending_scale(State* s, int v) {
     return f;
 }
 // ---- the gate path's per-gate small algebra (kernels_theta.hip and the small_svd_* kernels of kernels_svd.hip): ONE launch of every kernel over nitems gates / sites of
-// different sizes.  The descriptors are filled by the rules of engine_gates.cpp (gate_items, run_theta, second_pass, add_small_svd) and the same launch_* functions run in
-// the same order -- keep the two in step.  Inputs: the items' arrays one after the other, every sub-array at a multiple of 256 bytes on the device.  Outputs: guard bands
-// as above.  The small integer arrays (info, texp, failure flags, ranks) are contiguous per launch as in the engine's read-back buffer: they go up as filled and come back ----
+// different sizes.  The route rule, the launch chain and the item fills are the engine's own (gate_theta.cpp: theta_route, launch_theta_chain, small_svd_items /
+// launch_small_svd, Qr2Site); what is written here is where the arrays live.  Inputs: the items' arrays one after the other, every sub-array at a multiple of 256 bytes on
+// the device.  Outputs: guard bands as above.  The small integer arrays (info, texp, failure flags, ranks) are contiguous per launch as in the engine's read-back buffer:
+// they go up as filled and come back ----
 namespace {
-struct GateDims { int d1, d2, chi, n1, n2, Mr, Nc; };
-// d^2 chi > 512: the engine refuses the gate (gate_items)
-GateDims gate_dims(const char* who, const int* dims, int i) {
-    const int d1 = dims[3 * i], d2 = dims[3 * i + 1], chi = dims[3 * i + 2];
-    if (d1 < 1 || d2 < 1 || chi < 1) throw Err(TNQS_ERR_INVALID, std::string(who) + ": d1, d2, chi >= 1");
-    if ((long long)d1 * d1 * chi > 512 || (long long)d2 * d2 * chi > 512) throw Err(TNQS_ERR_UNSUPPORTED, std::string(who) + ": d^2*chi > 512 is not supported by the theta SVD kernels");
-    return GateDims{d1, d2, chi, d1 * chi, d2 * chi, d1 * d1 * chi, d2 * d2 * chi};
+struct GateDims : ThetaRoute { int d1, d2, chi; };
+// item i as the engine sees it: dimensions, the refusal of d^2 chi > 512, cap, and -- given the gate's kappa -- the route
+GateDims gate_dims(const char* who, bool F32, const int* dims, int i, int kappa = 0, int maxdim = 0) {
+    GateDims g; g.d1 = dims[3 * i]; g.d2 = dims[3 * i + 1]; g.chi = dims[3 * i + 2];
+    if (g.d1 < 1 || g.d2 < 1 || g.chi < 1) throw Err(TNQS_ERR_INVALID, std::string(who) + ": d1, d2, chi >= 1");
+    static_cast<ThetaRoute&>(g) = theta_route(F32, g.d1, g.d2, g.chi, kappa, maxdim);
+    return g;
 }
 void up_ints(DBuf& d, const int* h, size_t n) { d.up(h, sizeof(int) * n); }
+const void* upload_dbuf(void* keep, const void* p, size_t bytes) {      // DescUpload into a plain device allocation that lives as long as `keep`
+    auto& k = *static_cast<std::vector<std::unique_ptr<DBuf>>*>(keep);
+    k.emplace_back(new DBuf(bytes)); k.back()->up(p, bytes); return k.back()->p;
+}
 }
 // HOST ONLY: the operator-sum factors of a two-site gate as gate_items() gets them
 int dbg_operator_sum(const void* gate, int d1, int d2, void* fa_out, void* fb_out) {
@@ -1130,38 +1123,29 @@ int dbg_operator_sum(const void* gate, int d1, int d2, void* fa_out, void* fb_ou
     if (fb_out && !fb.empty()) std::memcpy(fb_out, fb.data(), fb.size() * 16);
     return kappa;
 }
-// the launches of TwoSiteBatch::run_theta.  info == NULL: only low_sizes is filled (host only)
+// TwoSiteBatch::run_theta's launch_theta_chain up to stage stop_after.  info == NULL: only low_sizes is filled (host only)
 void dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode, const int* rk, const void* F1, const void* F2, const double* tau, const void* gate,
                     const int* maxdim, int lowrank_on, int stop_after, int* low_sizes, int* info, double* lam1, double* lam2, int* idx1, int* idx2,
                     void* theta, void* theta0, void* thetaV, void* lowA, void* lowB, void* lowG, void* lowL, void* lowQ, void* lowL2c, int* texp, int* lowfail, int guard) {
     if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !dims || !mode || !rk || !F1 || !F2 || !tau || !gate || !maxdim || !low_sizes || stop_after < 0 || stop_after > 3 || guard < 0)
         throw Err(TNQS_ERR_INVALID, "dbg_gate_theta: bad arguments");
     const bool F32 = dtype == TNQS_C64; const size_t esz = F32 ? 8 : 16;
-    std::vector<GateDims> gd(nitems); std::vector<int> kappa(nitems, 0), cap(nitems); std::vector<char> low(nitems, 0), lowq(nitems, 0);
+    std::vector<GateDims> gd(nitems); std::vector<int> kappa(nitems, 0);
     std::vector<std::vector<std::complex<double>>> fa(nitems), fb(nitems);
     const char* hg = (const char*)gate; std::vector<size_t> goff(nitems + 1, 0);
     for (int i = 0; i < nitems; ++i) {
-        gd[i] = gate_dims("dbg_gate_theta", dims, i);
+        gd[i] = gate_dims("dbg_gate_theta", F32, dims, i);
         for (int sd = 0; sd < 2; ++sd) {
             const int m = mode[2 * i + sd], n = sd ? gd[i].n2 : gd[i].n1;
             if (m < 0 || m > 2 || (m == 2 && (rk[2 * i + sd] < 0 || rk[2 * i + sd] > n))) throw Err(TNQS_ERR_INVALID, "dbg_gate_theta: mode in {0, 1, 2}, 0 <= rk <= n");
         }
         const size_t dd = (size_t)gd[i].d1 * gd[i].d2; goff[i + 1] = goff[i] + dd * dd * 16;
     }
-    for (int i = 0; i < nitems; ++i) {      // gate_items(): cap, operator sum, and where the low-rank workspaces are handed out
-        const GateDims& g = gd[i];
-        cap[i] = std::min(g.Mr, g.Nc); if (maxdim[i] > 0) cap[i] = std::min(cap[i], maxdim[i]);
-        if (lowrank_on) kappa[i] = operator_sum(reinterpret_cast<const double*>(hg + goff[i]), g.d1, g.d2, fa[i], fb[i]);
-        const int K = kappa[i] * g.chi;
-        if (lowrank_on && kappa[i] > 0) {
-            const bool lds_fits = F32 || jacobi_lds(jacobi_lds_bytes(g.Mr, K, false, esz)) > 0;
-            if (K < g.Nc && K <= 128 && cap[i] <= K && g.Mr >= g.Nc && lds_fits) {
-                low[i] = 1;
-                if (F32 && use_precond_svd() && theta_svd_pre_covers(g.Mr, K) && K <= 96) lowq[i] = 1;
-            }
-        }
+    for (int i = 0; i < nitems; ++i) {      // the operator sum, and what theta_route hands out for it
+        if (lowrank_on) kappa[i] = operator_sum(reinterpret_cast<const double*>(hg + goff[i]), gd[i].d1, gd[i].d2, fa[i], fb[i]);
+        const ThetaRoute& r = gd[i] = gate_dims("dbg_gate_theta", F32, dims, i, kappa[i], maxdim[i]);
         int* z = low_sizes + 6 * i;
-        z[0] = kappa[i] > 0 ? g.Mr * K : 0; z[1] = kappa[i] > 0 ? g.Nc * K : 0; z[2] = low[i] ? K * K : 0; z[3] = z[2]; z[4] = lowq[i] ? g.Nc * K : 0; z[5] = (low[i] && !F32) ? 2 * K * K : 0;
+        z[0] = (int)r.nA; z[1] = (int)r.nB; z[2] = z[3] = (int)r.nG; z[4] = (int)r.nQ; z[5] = 2 * (int)r.nG2;
     }
     if (!info) return;
     if (!lam1 || !lam2 || !idx1 || !idx2 || !theta || !theta0 || !thetaV || !lowA || !lowB || !lowG || !lowL || !lowQ || !lowL2c || !texp || !lowfail)
@@ -1171,36 +1155,40 @@ void dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode, con
     Guarded gLam1((size_t)guard * 8), gLam2((size_t)guard * 8), gIdx1((size_t)guard * 4), gIdx2((size_t)guard * 4), gTh(guard * esz), gTh0(guard * esz), gTv(guard * esz),
             gA((size_t)guard * 16), gB((size_t)guard * 16), gG((size_t)guard * 16), gL((size_t)guard * 16), gQ((size_t)guard * 16), gL2c((size_t)guard * 16);
     for (int i = 0; i < nitems; ++i) {
-        const GateDims& g = gd[i]; const int* z = low_sizes + 6 * i; const size_t KK = (size_t)z[2];
+        const GateDims& g = gd[i];
         for (int k = 0; k < 3; ++k) { sF1.add((size_t)g.n1 * g.n1 * 16); sF2.add((size_t)g.n2 * g.n2 * 16); }
         sGate.add(goff[i + 1] - goff[i]); sOp.add(fa[i].size() * 16); sOp.add(fb[i].size() * 16); sRk.add(8);
-        sW.add(KK * 16); sB1.add(F32 ? 0 : (size_t)z[1] * 16 * (low[i] ? 1 : 0)); sG2.add(F32 ? 0 : KK * 16);
+        sW.add(g.nG * 16); sB1.add(g.nB1 * 16); sG2.add(g.nG2 * 16);
         gLam1.add((size_t)g.n1 * 8); gLam2.add((size_t)g.n2 * 8); gIdx1.add((size_t)g.n1 * 4); gIdx2.add((size_t)g.n2 * 4);
         const size_t mx = (size_t)std::max(g.Mr, g.Nc);
         gTh.add((size_t)g.Mr * g.Nc * esz); gTh0.add((size_t)g.Mr * g.Nc * esz); gTv.add(mx * mx * esz);
-        gA.add((size_t)z[0] * 16); gB.add((size_t)z[1] * 16); gG.add((size_t)z[2] * 16); gL.add((size_t)z[3] * 16); gQ.add((size_t)z[4] * 16); gL2c.add((size_t)z[5] * 16);
+        gA.add(g.nA * 16); gB.add(g.nB * 16); gG.add(g.nG * 16); gL.add(g.nG * 16); gQ.add(g.nQ * 16); gL2c.add(2 * g.nG2 * 16);      // lowL2c: L2, then Lc
     }
     for (Slots* s : {&sF1, &sF2, &sGate, &sOp, &sRk, &sW, &sB1, &sG2}) s->alloc();
     for (Guarded* g : {&gLam1, &gLam2, &gIdx1, &gIdx2, &gTh, &gTh0, &gTv, &gA, &gB, &gG, &gL, &gQ, &gL2c}) g->alloc();
     put_all(sF1, F1); put_all(sF2, F2); put_all(sGate, gate);
     for (int i = 0; i < nitems; ++i) { if (!fa[i].empty()) { sOp.put(2 * i, fa[i].data()); sOp.put(2 * i + 1, fb[i].data()); } sRk.put(i, rk + 2 * i); }
     DBuf dInfo(32 * (size_t)nitems), dFail(8 * (size_t)nitems), dTexp(4 * (size_t)nitems);
-    HIPCHK(hipMemset(dInfo.p, 0, 32 * (size_t)nitems)); HIPCHK(hipMemset(dFail.p, 0, 8 * (size_t)nitems));      // run_theta zeroes info and both failure-flag arrays
+    HIPCHK(hipMemset(dInfo.p, 0, 32 * (size_t)nitems)); HIPCHK(hipMemset(dFail.p, 0, 8 * (size_t)nitems));      // as run_theta zeroes them in front of the chain
     up_ints(dTexp, texp, nitems);
-    std::vector<GateItem> gitems(nitems);
+    std::vector<GateItem> gitems(nitems); std::vector<ThetaLowWs> lows(nitems);
     for (int i = 0; i < nitems; ++i) {
-        const GateDims& g = gd[i]; GateItem& it = gitems[i]; it = GateItem{};
+        const GateDims& g = gd[i]; const ThetaRoute& r = g; GateItem& it = gitems[i]; it = GateItem{};
         it.GA1 = sF1.at(3 * i); it.GV1 = sF1.at(3 * i + 1); it.GW1 = sF1.at(3 * i + 2); it.GA2 = sF2.at(3 * i); it.GV2 = sF2.at(3 * i + 1); it.GW2 = sF2.at(3 * i + 2);
-        it.chol1 = mode[2 * i]; it.chol2 = mode[2 * i + 1]; it.n1 = g.n1; it.n2 = g.n2; it.d1 = g.d1; it.d2 = g.d2; it.chi = g.chi;
+        it.chol1 = mode[2 * i]; it.chol2 = mode[2 * i + 1]; it.n1 = r.n1; it.n2 = r.n2; it.d1 = g.d1; it.d2 = g.d2; it.chi = g.chi;
         it.gate = reinterpret_cast<const double*>(sGate.at(i));
-        if (lowrank_on && kappa[i] > 0) {
+        if (r.opsum) {
             it.kappa = kappa[i]; it.opA = reinterpret_cast<const double*>(sOp.at(2 * i)); it.opB = reinterpret_cast<const double*>(sOp.at(2 * i + 1));
             it.lowA = gA.at(i); it.lowB = gB.at(i);
-            if (low[i]) { it.lowG = gG.at(i); it.lowL = gL.at(i); if (lowq[i]) { it.lowW = sW.at(i); it.lowQ = gQ.at(i); } }
+        }
+        if (r.low) {
+            it.lowG = gG.at(i); it.lowL = gL.at(i);
+            if (r.lowq) { it.lowW = sW.at(i); it.lowQ = gQ.at(i); }
+            lows[i] = ThetaLowWs{sW.at(i), sB1.at(i), sG2.at(i), gL2c.at(i), gL2c.at(i) + r.nG2 * 16};
         }
         it.lam1 = (double*)gLam1.at(i); it.lam2 = (double*)gLam2.at(i); it.idx1 = (int*)gIdx1.at(i); it.idx2 = (int*)gIdx2.at(i);
         it.theta = gTh.at(i); it.thetaV = gTv.at(i); it.theta0 = gTh0.at(i);
-        it.maxdim = maxdim[i]; it.chi_cap = cap[i];
+        it.maxdim = maxdim[i]; it.chi_cap = r.cap;
         it.tau1 = tau[2 * i]; it.tau2 = tau[2 * i + 1];
         it.rk1 = mode[2 * i] == 2 ? (const int*)sRk.at(i) : nullptr; it.rk2 = mode[2 * i + 1] == 2 ? (const int*)sRk.at(i) + 1 : nullptr;
         it.info = (int*)dInfo.p + 8 * i; it.lowfail = (const int*)dFail.p + i; it.texp = (int*)dTexp.p + i;
@@ -1209,48 +1197,10 @@ void dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode, con
     for (Slots* s : {&sF1, &sF2, &sGate, &sOp, &sRk, &sW, &sB1, &sG2}) s->up();
     gLam1.up(lam1); gLam2.up(lam2); gIdx1.up(idx1); gIdx2.up(idx2); gTh.up(theta); gTh0.up(theta0); gTv.up(thetaV);
     gA.up(lowA); gB.up(lowB); gG.up(lowG); gL.up(lowL); gQ.up(lowQ); gL2c.up(lowL2c);
-    const GateItem* d_gitems = (const GateItem*)dI.p;
-    bool lowrank_on_batch = false; for (int i = 0; i < nitems; ++i) lowrank_on_batch = lowrank_on_batch || gitems[i].lowA;
-    // ---- run_theta ----
     std::vector<std::unique_ptr<DBuf>> keep;
-    auto upload_vec = [&](const void* p, size_t bytes) { keep.emplace_back(new DBuf(bytes)); keep.back()->up(p, bytes); return keep.back()->p; };
-    if (F32) launch_gate_theta<float>(nullptr, d_gitems, nitems); else launch_gate_theta<double>(nullptr, d_gitems, nitems);
-    if (stop_after >= 1 && lowrank_on_batch) { if (F32) launch_gate_theta_mm<float>(nullptr, d_gitems, nitems); else launch_gate_theta_mm<double>(nullptr, d_gitems, nitems); }
-    if (stop_after >= 2) {
-        std::vector<CholItem> lc, lc2; int kmax = 1;
-        std::vector<GateItem> g2, g3; std::vector<LowQr2Item> qi;
-        for (int q = 0; q < nitems; ++q) {
-            if (!gitems[q].lowG) continue;
-            const int K = gitems[q].kappa * gitems[q].chi; const size_t KK = (size_t)K * K;
-            int* fail1 = (int*)dFail.p + q;
-            lc.push_back(CholItem{gitems[q].lowG, const_cast<void*>(gitems[q].lowL), (K <= 96 || !F32) ? (void*)sW.at(q) : nullptr, K, fail1, !F32 ? 1e-12 : rank_tau(true, K)});
-            kmax = std::max(kmax, K);
-            if (!F32) {
-                int* fail2 = (int*)dFail.p + nitems + q;
-                char* L2 = gL2c.at(q); char* Lc = gL2c.at(q) + KK * 16;
-                lc2.push_back(CholItem{sG2.at(q), L2, nullptr, K, fail2, 1e-3});
-                GateItem a = gitems[q]; a.lowB = sB1.at(q); a.lowG = sG2.at(q); a.lowL = L2; g2.push_back(a);
-                GateItem b = gitems[q]; b.lowL = Lc; g3.push_back(b);
-                qi.push_back(LowQr2Item{gitems[q].lowB, sW.at(q), sB1.at(q), gitems[q].lowL, L2, Lc, gitems[q].info, gitems[q].d2, fail1, fail2});
-            }
-        }
-        if (!lc.empty()) {
-            const CholItem* dc = (const CholItem*)upload_vec(lc.data(), sizeof(CholItem) * lc.size()); launch_lowrank_g(nullptr, d_gitems, nitems);
-            if (kmax <= 96) launch_chol(nullptr, dc, (int)lc.size(), kmax); else launch_chol_packed(nullptr, dc, (int)lc.size(), kmax);
-            if (F32) launch_lowrank_m<float>(nullptr, d_gitems, nitems);
-            else {
-                const LowQr2Item* dq = (const LowQr2Item*)upload_vec(qi.data(), sizeof(LowQr2Item) * qi.size());
-                const GateItem* d2 = (const GateItem*)upload_vec(g2.data(), sizeof(GateItem) * g2.size()); const GateItem* d3 = (const GateItem*)upload_vec(g3.data(), sizeof(GateItem) * g3.size());
-                const CholItem* dc2 = (const CholItem*)upload_vec(lc2.data(), sizeof(CholItem) * lc2.size());
-                launch_lowrank_bw(nullptr, dq, (int)qi.size());
-                launch_lowrank_g(nullptr, d2, (int)g2.size());
-                if (kmax <= 96) launch_chol(nullptr, dc2, (int)lc2.size(), kmax); else launch_chol_packed(nullptr, dc2, (int)lc2.size(), kmax);
-                launch_lowrank_ll(nullptr, dq, (int)qi.size());
-                launch_lowrank_m<double>(nullptr, d3, (int)g3.size());
-            }
-        }
-    }
-    if (stop_after >= 3) { if (F32) launch_theta_scale<float>(nullptr, d_gitems, nitems); else launch_theta_scale<double>(nullptr, d_gitems, nitems); }
+    const DescUpload up{upload_dbuf, &keep};
+    if (F32) launch_theta_chain<float>(nullptr, (const GateItem*)dI.p, gitems, lows, (int*)dFail.p, (int*)dFail.p + nitems, up, stop_after);
+    else launch_theta_chain<double>(nullptr, (const GateItem*)dI.p, gitems, lows, (int*)dFail.p, (int*)dFail.p + nitems, up, stop_after);
     HIPCHK(hipDeviceSynchronize());
     sW.down("lowW"); sB1.down("lowB1"); sG2.down("lowG2");
     gLam1.down(lam1, "lam1"); gLam2.down(lam2, "lam2"); gIdx1.down(idx1, "idx1"); gIdx2.down(idx2, "idx2"); gTh.down(theta, "theta"); gTh0.down(theta0, "theta0"); gTv.down(thetaV, "thetaV");
@@ -1270,11 +1220,11 @@ void dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in,
     Slots sTh, sTv, sLam1, sLam2, sIdx1, sIdx2, sW1, sW2; Guarded gS((size_t)guard * 8), gX1(guard * esz), gX2(guard * esz);
     size_t i1 = 0, i2 = 0;
     for (int i = 0; i < nitems; ++i) {
-        const GateDims g = gd[i] = gate_dims("dbg_gate_finish", dims, i);
+        const GateDims g = gd[i] = gate_dims("dbg_gate_finish", F32, dims, i);
         const int r1 = info_in[4 * i], r2 = info_in[4 * i + 1], wide = info_in[4 * i + 2], K = info_in[4 * i + 3];
         if (r1 < 1 || r1 > g.n1 || r2 < 1 || r2 > g.n2) throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: 1 <= r <= n");
         const int Mr = r1 * g.d1, Nc = r2 * g.d2, ncol = std::min(Mr, Nc);
-        if ((wide != 0) != (Mr < Nc) || K < 0 || K > ncol || (K > 0 && wide) || chi_cap[i] < 1 || chi_cap[i] > std::min(g.Mr, g.Nc) || texp[i] < -120 || texp[i] > 120)
+        if ((wide != 0) != (Mr < Nc) || K < 0 || K > ncol || (K > 0 && wide) || chi_cap[i] < 1 || chi_cap[i] > g.cap || texp[i] < -120 || texp[i] > 120)
             throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: inconsistent info / chi_cap / texp");
         for (int a = 0; a < r1; ++a) if (idx1[i1 + a] < 0 || idx1[i1 + a] >= g.n1) throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: idx1 out of range");
         for (int c = 0; c < r2; ++c) if (idx2[i2 + c] < 0 || idx2[i2 + c] >= g.n2) throw Err(TNQS_ERR_INVALID, "dbg_gate_finish: idx2 out of range");
@@ -1336,9 +1286,9 @@ void dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV
     DBuf dR(4 * (size_t)nitems), dRk(4 * (size_t)nitems); up_ints(dR, r, nitems); if (stage) up_ints(dRk, rk, nitems);
     std::vector<Qr2RinvItem> ri(nitems); std::vector<Qr2ComposeItem> ci(nitems);
     for (int i = 0; i < nitems; ++i) {
-        ri[i] = Qr2RinvItem{sW.at(i), (const double*)sLam.at(i), (const int*)sIdx.at(i), (const int*)dR.p + i, n[i], gX.at(i)};
-        ci[i] = Qr2ComposeItem{sA2.at(i), sV2.at(i), gX.at(i), sV.at(i), (const double*)sLam.at(i), (const int*)sIdx.at(i), (const int*)dR.p + i, n[i], stage ? tau[i] : 0.0,
-                               gGV.at(i), gGW.at(i), (int*)dRk.p + i};
+        const Qr2Site q{sW.at(i), sV.at(i), (const double*)sLam.at(i), (const int*)sIdx.at(i), (const int*)dR.p + i, n[i], gX.at(i)};
+        ri[i] = q.rinv();
+        ci[i] = q.compose(sA2.at(i), sV2.at(i), stage ? tau[i] : 0.0, gGV.at(i), gGW.at(i), (int*)dRk.p + i);
     }
     DBuf dRi(sizeof(Qr2RinvItem) * nitems), dCi(sizeof(Qr2ComposeItem) * nitems);
     dRi.up(ri.data(), sizeof(Qr2RinvItem) * nitems); dCi.up(ci.data(), sizeof(Qr2ComposeItem) * nitems);
@@ -1368,18 +1318,13 @@ void dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, voi
     std::vector<SmallSvdItem> si; std::vector<JacobiItem> sji;
     for (int i = 0; i < nitems; ++i) {
         const int d = shape[4 * i], lo = shape[4 * i + 1], cb = shape[4 * i + 2], hi = shape[4 * i + 3];
-        si.push_back(SmallSvdItem{sSrc.at(i), sM.at(i), gA.at(i), gV.at(i), d, lo, cb, hi});
-        sji.push_back(JacobiItem{sM.at(i), nullptr, d * cb, lo * hi, nullptr});
+        small_svd_items(sSrc.at(i), sM.at(i), gA.at(i), gV.at(i), d, lo, cb, hi, si, sji);
     }
     DBuf dS(sizeof(SmallSvdItem) * nitems), dJ(sizeof(JacobiItem) * nitems);
     dS.up(si.data(), sizeof(SmallSvdItem) * nitems); dJ.up(sji.data(), sizeof(JacobiItem) * nitems);
     sSrc.up(); sM.up(); gA.up(GA); gV.up(GV);
     const SmallSvdItem* ds = (const SmallSvdItem*)dS.p; const JacobiItem* dj = (const JacobiItem*)dJ.p;
-    // engine_gates.cpp launch_small_svd
-    if (dtype == TNQS_C64) launch_small_svd_prepare<float>(nullptr, ds, nitems); else launch_small_svd_prepare<double>(nullptr, ds, nitems);
-    size_t lds = 0; for (auto& j : sji) lds = std::max(lds, jacobi_lds_bytes(j.m, j.n, false, 16));
-    launch_jacobi<double>(nullptr, dj, nitems, 60, jacobi_lds(lds), mmax_of(sji));
-    launch_small_svd_finish(nullptr, ds, nitems);
+    if (dtype == TNQS_C64) launch_small_svd<float>(nullptr, ds, dj, sji); else launch_small_svd<double>(nullptr, ds, dj, sji);
     HIPCHK(hipDeviceSynchronize());
     sM.down("M"); gA.down(GA, "GA"); gV.down(GV, "GV");
 }

@@ -383,8 +383,7 @@ template <class T> struct BpLevelBatch {
             const Buf& mb = u.incoming(m.src, j, m.t);
             if (mb) si.M[j] = mb->p;                 // unset message = identity: nothing to absorb
         }
-        si.mfma = (c.sd.n % 256) == 0;
-        for (int j = 0; j < c.sd.z; ++j) if (c.sd.chi[j] != 16) si.mfma = 0;
+        si.mfma = bp_small_site_mfma_form(c.sd.z, c.sd.chi.data(), c.sd.n) ? 1 : 0;
         small_items.push_back(si); small_msg.push_back((int)msgs.size()); small_max = std::max(small_max, (int)c.sd.n);
         m.route = Route::Small;
     }

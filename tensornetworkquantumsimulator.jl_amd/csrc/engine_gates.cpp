@@ -247,13 +247,6 @@ struct GateBook {
     }
 };
 
-// R = Sigma U^dagger of sites with fewer fibers than columns, from the SVD of the n x N matricised psi~ (f64): three dependent launches on `st`
-template <class T> static void launch_small_svd(hipStream_t st, const SmallSvdItem* ds, const JacobiItem* dj, const std::vector<JacobiItem>& sji) {
-    launch_small_svd_prepare<T>(st, ds, (int)sji.size());
-    size_t lds = 0; for (auto& j : sji) lds = std::max(lds, jacobi_lds_bytes(j.m, j.n, false, 16));
-    launch_jacobi<double>(st, dj, (int)sji.size(), 60, jacobi_lds(lds), mmax_of(sji));
-    launch_small_svd_finish(st, ds, (int)sji.size());
-}
 // eigen factorisation of Hermitian f64 matrices G = V Lambda V^dagger by the Jacobi kernel, V starting from the identity (env_prepare with msg == null: H := I, V := I)
 template <class T> static void launch_eigen_from_identity(State* s, const EnvItem* di, const JacobiItem* dj, const std::vector<JacobiItem>& ji) {
     size_t lds = 0; for (auto& j : ji) lds = std::max(lds, jacobi_lds_bytes(j.n, j.n, true, 16));
@@ -289,7 +282,7 @@ template <class T> struct TwoSiteBatch {
     ReadBack rb{0, 0, 0}; Buf d_rb, d_texp; const char* st_all = nullptr;               // st_all: the staged copy of d_rb
     std::vector<int> h_flags, h_cholfail, hinfo, info; std::vector<double> hterr, terr;
     std::vector<GateWS> ws; std::vector<int> pg; int npg = 0;                  // pg: gates this rank takes part in
-    std::vector<GateItem> gitems; const GateItem* d_gitems = nullptr; bool lowrank_on_batch = false; int cap_max = 1; size_t x2_max = 0;
+    std::vector<GateItem> gitems; const GateItem* d_gitems = nullptr; std::vector<ThetaLowWs> lows; int cap_max = 1; size_t x2_max = 0;
     ReadRoute route = ReadRoute::two_trips;
     FiberPass spec_plan;                                        // the epilogue pass planned before the read-back (plan_epilogue)
     std::vector<const double*> Sptr; Buf S_keep;
@@ -399,13 +392,11 @@ template <class T> struct TwoSiteBatch {
         for (size_t q = 0; q < own_idx.size(); ++q) gauged_of[own_idx[q]] = chains[q].result;
     }
 
-    // the small-SVD items of site i (its n x N matricised psi~ goes to a fresh M); debug.cpp dbg_small_svd fills the same two items
+    // the small-SVD items of site i (its n x N matricised psi~ goes to a fresh M)
     void add_small_svd(size_t i, std::vector<SmallSvdItem>& si, std::vector<JacobiItem>& sji) {
-        const int n = nof(i); const size_t Nout = sj[i].sd.n / (size_t)n;
-        Buf M = dalloc(s, (size_t)n * Nout * 16); s->keepalive.push_back(M);
         const SD& sd = sj[i].sd; const int b = sj[i].bleg;
-        si.push_back(SmallSvdItem{gauged_of[i], M->p, GA[i]->p, GV[i]->p, sd.d, (int)(sd.pre(b) / sd.d), sd.chi[b], (int)sd.post(b)});
-        sji.push_back(JacobiItem{M->p, nullptr, n, (int)Nout, nullptr});
+        Buf M = dalloc(s, sd.n * 16); s->keepalive.push_back(M);
+        small_svd_items(gauged_of[i], M->p, GA[i]->p, GV[i]->p, sd.d, (int)(sd.pre(b) / sd.d), sd.chi[b], (int)sd.post(b), si, sji);
     }
 
     // ---- 2b. sites with fewer fibers than columns (corners, low bond dimensions) are factorised without a Gram matrix, by a one-sided Jacobi of
@@ -538,28 +529,14 @@ template <class T> struct TwoSiteBatch {
     }
 
     // ---- 4. theta = gate . (R1 R2), SVD, truncation, X1 / X2  (simple_update.jl:51-59): the per-gate workspaces and GateItems -------------
-    // (debug.cpp dbg_gate_theta / dbg_gate_finish fill GateItems by the same rules for the kernel-level tests: keep the two in step)
     void gate_items() {
-        ws.resize(ng); gitems.resize(pg.size());
-        for (int gi = 0; gi < ng; ++gi) {
-            GateWS& w = ws[gi];
-            const SiteJob& a = sj[2 * gi]; const SiteJob& b = sj[2 * gi + 1];
-            int chi = a.sd.chi[a.bleg];
-            w.n1 = a.sd.d * chi; w.n2 = b.sd.d * chi; w.chi = chi;
-            int Mr = w.n1 * a.sd.d, Nc = w.n2 * b.sd.d;
-            // theta is at most 512 x 512 (d^2 chi <= 512: chi <= 128 for qubits); up to 256 rows everything has an LDS or MFMA-preprocessed route, beyond
-            // that the factorisations run in the global-memory Jacobi kernel (8 rows per lane)
-            if (Mr > 512 || Nc > 512) throw Err(TNQS_ERR_UNSUPPORTED, "two-site gate: d^2*chi > 512 is not supported by the theta SVD kernels");
-            int cap = std::min(Mr, Nc); if (ao.maxdim > 0) cap = std::min(cap, ao.maxdim);
-            w.cap = cap; cap_max = std::max(cap_max, cap);
-            x2_max = std::max(x2_max, (size_t)w.n2 * b.sd.d * cap * esz);
-        }
+        ws.resize(ng); gitems.resize(pg.size()); lows.assign(pg.size(), ThetaLowWs{});
         // gate matrices and their operator-sum factors, one upload.  ComplexF64 takes the low-rank route as well (round 4): B is orthogonalised by
         // CholeskyQR2 (kernels.hpp LowQr2Item), and the 128 x 64 factor of a chi = 32 gate fits the LDS-resident Jacobi where the 128 x 128 theta
         // (256 KiB) ran in the global-memory kernel
         const bool lowrank_on = use_lowrank();
         std::vector<char> raw;
-        std::vector<size_t> off(pg.size()), offA(pg.size(), 0), offB(pg.size(), 0); std::vector<int> kappa(pg.size(), 0);
+        std::vector<size_t> off(pg.size()), offA(pg.size(), 0), offB(pg.size(), 0); std::vector<int> kappa(ng, 0);
         for (size_t q = 0; q < pg.size(); ++q) {
             const Gate2& g2 = gates[pg[q]];
             const int d1 = s->d[g2.v1], d2 = s->d[g2.v2], dd = d1 * d2;
@@ -568,9 +545,18 @@ template <class T> struct TwoSiteBatch {
             raw.insert(raw.end(), p, p + (size_t)dd * dd * 16);
             if (!lowrank_on) continue;
             std::vector<std::complex<double>> fa, fb;
-            kappa[q] = operator_sum(g2.mat, d1, d2, fa, fb);
+            kappa[pg[q]] = operator_sum(g2.mat, d1, d2, fa, fb);
             offA[q] = raw.size(); raw.insert(raw.end(), reinterpret_cast<const char*>(fa.data()), reinterpret_cast<const char*>(fa.data()) + fa.size() * 16);
             offB[q] = raw.size(); raw.insert(raw.end(), reinterpret_cast<const char*>(fb.data()), reinterpret_cast<const char*>(fb.data()) + fb.size() * 16);
+        }
+        std::vector<ThetaRoute> routes(ng);
+        for (int gi = 0; gi < ng; ++gi) {
+            GateWS& w = ws[gi];
+            const SiteJob& a = sj[2 * gi]; const SiteJob& b = sj[2 * gi + 1];
+            const ThetaRoute& r = routes[gi] = theta_route(F32, a.sd.d, b.sd.d, a.sd.chi[a.bleg], kappa[gi], ao.maxdim);
+            w.n1 = r.n1; w.n2 = r.n2; w.chi = a.sd.chi[a.bleg];
+            w.cap = r.cap; cap_max = std::max(cap_max, r.cap);
+            x2_max = std::max(x2_max, (size_t)r.Nc * r.cap * esz);
         }
         const char* d_gm = pg.empty() ? nullptr : upload(s, raw);
         // the per-gate workspaces (sixteen small buffers per gate, all of them dead at the end of the batch) are views into a few 4 MiB slabs: ~1100 pool round
@@ -586,7 +572,7 @@ template <class T> struct TwoSiteBatch {
             int gi = pg[q];
             GateWS& w = ws[gi]; GateItem& it = gitems[q];
             const SiteJob& a = sj[2 * gi]; const SiteJob& b = sj[2 * gi + 1];
-            int Mr = w.n1 * a.sd.d, Nc = w.n2 * b.sd.d, cap = w.cap;
+            const ThetaRoute& r = routes[gi]; const int Mr = r.Mr, Nc = r.Nc, cap = r.cap;
             // SVD of theta: the right factor is never accumulated from the rotations (in f32 its orthogonality degrades with the
             // rotation count, ~1e-5 at 150 columns) but recovered from an unrotated copy theta0: V = theta0^dagger (U S) S^-2
             w.lam1 = arena.get(w.n1 * 8); w.lam2 = arena.get(w.n2 * 8); w.idx1 = arena.get(w.n1 * 4); w.idx2 = arena.get(w.n2 * 4);
@@ -599,23 +585,19 @@ template <class T> struct TwoSiteBatch {
             it.n1 = w.n1; it.n2 = w.n2; it.d1 = a.sd.d; it.d2 = b.sd.d; it.chi = w.chi;
             it.gate = reinterpret_cast<const double*>(d_gm + off[q]);
             it.kappa = 0; it.opA = it.opB = nullptr; it.lowA = it.lowB = it.lowG = nullptr; it.lowL = nullptr; it.lowfail = nullptr; it.lowW = nullptr; it.lowQ = nullptr;
-            // the operator-sum factors A ((r1 d1) x K), B ((r2 d2) x K), K = kappa chi: theta = A B^T is formed from them (gate_theta_mm_kernel);
-            // the low-rank route of the theta SVD (lowG / lowL) only where it can apply -- K below the theta columns and chol_kernel's size
-            const int K = kappa[q] * w.chi;
-            if (lowrank_on && kappa[q] > 0) {
-                w.lowA = arena.get((size_t)Mr * K * 16); w.lowB = arena.get((size_t)Nc * K * 16);
-                it.kappa = kappa[q]; it.opA = reinterpret_cast<const double*>(d_gm + offA[q]); it.opB = reinterpret_cast<const double*>(d_gm + offB[q]);
-                it.lowA = w.lowA->p; it.lowB = w.lowB->p; lowrank_on_batch = true;
-                const bool lds_fits = F32 || jacobi_lds(jacobi_lds_bytes(Mr, K, false, esz)) > 0;      // ComplexF64: only where it buys the LDS route
-                if (K < Nc && K <= 128 && cap <= K && Mr >= Nc && lds_fits) {
-                    w.lowG = arena.get((size_t)K * K * 16); w.lowL = arena.get((size_t)K * K * 16); w.lowW = arena.get((size_t)K * K * 16);
-                    it.lowG = w.lowG->p; it.lowL = w.lowL->p;
-                    // ComplexF32, factor of at most 128 x 64: the preconditioned SVD kernel builds V from Q = B L^-dagger (lowrank_m_kernel writes it)
-                    if (F32 && use_precond_svd() && theta_svd_pre_covers(Mr, K) && K <= 96) { w.lowQ = arena.get((size_t)Nc * K * 16); it.lowW = w.lowW->p; it.lowQ = w.lowQ->p; }
-                    if (!F32) {
-                        w.lowB1 = arena.get((size_t)Nc * K * 16); w.lowG2 = arena.get((size_t)K * K * 16); w.lowL2 = arena.get((size_t)K * K * 16); w.lowLc = arena.get((size_t)K * K * 16);
-                    }
-                }
+            // the operator-sum factors and the low-rank workspaces, where theta_route hands them out
+            if (r.opsum) {
+                w.lowA = arena.get(r.nA * 16); w.lowB = arena.get(r.nB * 16);
+                it.kappa = kappa[gi]; it.opA = reinterpret_cast<const double*>(d_gm + offA[q]); it.opB = reinterpret_cast<const double*>(d_gm + offB[q]);
+                it.lowA = w.lowA->p; it.lowB = w.lowB->p;
+            }
+            if (r.low) {
+                w.lowG = arena.get(r.nG * 16); w.lowL = arena.get(r.nG * 16); w.lowW = arena.get(r.nG * 16);
+                it.lowG = w.lowG->p; it.lowL = w.lowL->p;
+                if (r.lowq) { w.lowQ = arena.get(r.nQ * 16); it.lowW = w.lowW->p; it.lowQ = w.lowQ->p; }
+                if (!F32) { w.lowB1 = arena.get(r.nB1 * 16); w.lowG2 = arena.get(r.nG2 * 16); w.lowL2 = arena.get(r.nG2 * 16); w.lowLc = arena.get(r.nG2 * 16); }
+                auto ptr = [](const Buf& b) -> void* { return b ? b->p : nullptr; };
+                lows[q] = ThetaLowWs{w.lowW->p, ptr(w.lowB1), ptr(w.lowG2), ptr(w.lowL2), ptr(w.lowLc)};
             }
             it.lam1 = (double*)w.lam1->p; it.lam2 = (double*)w.lam2->p; it.idx1 = (int*)w.idx1->p; it.idx2 = (int*)w.idx2->p;
             it.theta = w.theta->p; it.thetaV = w.thetaV->p; it.theta0 = w.theta0->p; it.X1 = w.X1->p; it.X2 = w.X2->p; it.S = (double*)w.S->p;
@@ -636,44 +618,11 @@ template <class T> struct TwoSiteBatch {
         d_gitems = upload(s, gitems);       // (read again after the host synchronisations of the batch: a device copy, not upload_small)
     }
 
-    // (debug.cpp dbg_gate_theta issues the same launches in the same order)
     void run_theta() {
         HIPCHK(hipMemsetAsync(d_rb->p, 0, rb.terr, s->stream));       // info and both low-rank failure flag arrays (contiguous)
         ProfScope ps(s, TNQS_PROF_SMALL, 0, 0);
-        launch_gate_theta<T>(s->stream, d_gitems, npg);
-        if (lowrank_on_batch) launch_gate_theta_mm<T>(s->stream, d_gitems, npg);        // theta = A B^T on the f64 matrix cores (gates with operator-sum factors)
-        std::vector<CholItem> lc, lc2; int kmax = 1;
-        std::vector<GateItem> g2, g3; std::vector<LowQr2Item> qi;
-        for (int q = 0; q < npg; ++q) {
-            if (!gitems[q].lowG) continue;
-            const int K = gitems[q].kappa * gitems[q].chi; GateWS& w = ws[pg[q]];
-            int* fail1 = dev<int>(rb.low) + q;
-            // ComplexF32: tau at the f32 noise floor.  ComplexF64: 1e-12 on the pivots of pass 1 keeps kappa(B) <= 1e6, where the second pass restores
-            // orthogonality to eps; anything worse falls back to the SVD of the full theta
-            lc.push_back(CholItem{gitems[q].lowG, const_cast<void*>(gitems[q].lowL), (K <= 96 || !F32) ? w.lowW->p : nullptr, K, fail1, !F32 ? 1e-12 : rank_tau(true, K)});
-            kmax = std::max(kmax, K);
-            if (!F32) {
-                int* fail2 = dev<int>(rb.low2) + q;      // ComplexF64: second CholeskyQR pass of the low-rank route
-                lc2.push_back(CholItem{w.lowG2->p, w.lowL2->p, nullptr, K, fail2, 1e-3});      // G2 is the identity up to kappa(G1) eps: a pivot below 1e-3 means pass 1 was not good enough
-                GateItem a = gitems[q]; a.lowB = w.lowB1->p; a.lowG = w.lowG2->p; a.lowL = w.lowL2->p; g2.push_back(a);
-                GateItem b = gitems[q]; b.lowL = w.lowLc->p; g3.push_back(b);
-                qi.push_back(LowQr2Item{w.lowB->p, w.lowW->p, w.lowB1->p, gitems[q].lowL, w.lowL2->p, w.lowLc->p, gitems[q].info, gitems[q].d2, fail1, fail2});
-            }
-        }
-        if (!lc.empty()) {
-            const CholItem* dc = upload_small(s, lc); launch_lowrank_g(s->stream, d_gitems, npg);
-            if (kmax <= 96) launch_chol(s->stream, dc, (int)lc.size(), kmax); else launch_chol_packed(s->stream, dc, (int)lc.size(), kmax);      // ComplexF32: only L is used here
-            if (F32) launch_lowrank_m<T>(s->stream, d_gitems, npg);
-            else {
-                const LowQr2Item* dq = upload_small(s, qi); const GateItem* d2 = upload_small(s, g2); const GateItem* d3 = upload_small(s, g3); const CholItem* dc2 = upload_small(s, lc2);
-                launch_lowrank_bw(s->stream, dq, (int)qi.size());                       // B1 = B L1^-dagger
-                launch_lowrank_g(s->stream, d2, (int)g2.size());                        // G2 = B1^dagger B1
-                if (kmax <= 96) launch_chol(s->stream, dc2, (int)lc2.size(), kmax); else launch_chol_packed(s->stream, dc2, (int)lc2.size(), kmax);
-                launch_lowrank_ll(s->stream, dq, (int)qi.size());                       // Lc = L1 L2 (+ pass-2 failure -> the gate's flag)
-                launch_lowrank_m<T>(s->stream, d3, (int)g3.size());                     // theta[:, :K] = A conj(Lc)
-            }
-        }
-        launch_theta_scale<T>(s->stream, d_gitems, npg);       // theta (or M) and theta0 to O(1), exponent kept per gate for gate_finish
+        const DescUpload up{[](void* st, const void* p, size_t bytes) { return upload_small_bytes(static_cast<State*>(st), p, bytes); }, s};
+        launch_theta_chain<T>(s->stream, d_gitems, gitems, lows, dev<int>(rb.low), dev<int>(rb.low2), up);
     }
 
     // SVD of theta (rotated in place to U Sigma), recovery of V from the unrotated copy, truncation and X1 / X2.  `dims` = the ranks
@@ -750,7 +699,7 @@ template <class T> struct TwoSiteBatch {
     // so R = R2 R1 is as accurate as a Householder R.  
     // Sharded: the owner of a site forms Q1 and its Gram matrix, one more all-gather (same slots as the first Gram exchange, issued
     // by every rank whether or not it has a flagged site -- it is a collective) hands it to the partner rank, and both compose the
-    // same factor from the same inputs.  (debug.cpp dbg_qr2 fills Qr2RinvItem / Qr2ComposeItem as this does.)
+    // same factor from the same inputs.
     void second_pass() {
         std::vector<size_t> rs; std::vector<int> rq;
         for (int q = 0; q < npg; ++q) for (int side = 0; side < 2; ++side) {
@@ -760,11 +709,12 @@ template <class T> struct TwoSiteBatch {
         if (!sharded && rs.empty()) return;
         const size_t m = rs.size();
         std::vector<Buf> X1(m), Q1(m), G2(m), V2(m), GVn(m), GWn(m); Buf d_rk = dalloc(s, std::max<size_t>(1, m) * sizeof(int));
-        std::vector<Qr2RinvItem> ri; std::vector<FiberItem> fi; std::vector<GramJob> gj; std::vector<size_t> own_k;
+        std::vector<Qr2Site> qs; std::vector<Qr2RinvItem> ri; std::vector<FiberItem> fi; std::vector<GramJob> gj; std::vector<size_t> own_k;
         for (size_t k = 0; k < m; ++k) {
             const size_t i = rs[k]; const int q = rq[k]; const bool second = (i & 1) != 0; const int n = nof(i); const size_t nn = (size_t)n * n;
             X1[k] = dalloc(s, nn * 16); V2[k] = dalloc(s, nn * 16); GVn[k] = dalloc(s, nn * 16); GWn[k] = dalloc(s, nn * 16);
-            ri.push_back(Qr2RinvItem{GW[i]->p, second ? gitems[q].lam2 : gitems[q].lam1, second ? gitems[q].idx2 : gitems[q].idx1, gitems[q].info + (second ? 1 : 0), n, X1[k]->p});
+            qs.push_back(Qr2Site{GW[i]->p, GV[i]->p, second ? gitems[q].lam2 : gitems[q].lam1, second ? gitems[q].idx2 : gitems[q].idx1, gitems[q].info + (second ? 1 : 0), n, X1[k]->p});
+            ri.push_back(qs[k].rinv());
             if (sj[i].owned) { own_k.push_back(k); Q1[k] = dalloc(s, sj[i].sd.n * esz); }
         }
         for (size_t k : own_k) {
@@ -800,11 +750,7 @@ template <class T> struct TwoSiteBatch {
         const EnvItem* di = upload(s, idn); const JacobiItem* dj = upload(s, ji);
         launch_eigen_from_identity<T>(s, di, dj, ji);
         std::vector<Qr2ComposeItem> ci;
-        for (size_t k = 0; k < m; ++k) {
-            const size_t i = rs[k]; const int q = rq[k]; const bool second = (i & 1) != 0; const int n = nof(i);
-            ci.push_back(Qr2ComposeItem{G2[k]->p, V2[k]->p, X1[k]->p, GV[i]->p, second ? gitems[q].lam2 : gitems[q].lam1, second ? gitems[q].idx2 : gitems[q].idx1,
-                                        gitems[q].info + (second ? 1 : 0), n, rank_tau(false, n), GVn[k]->p, GWn[k]->p, reinterpret_cast<int*>(d_rk->p) + k});
-        }
+        for (size_t k = 0; k < m; ++k) ci.push_back(qs[k].compose(G2[k]->p, V2[k]->p, rank_tau(false, qs[k].n), GVn[k]->p, GWn[k]->p, reinterpret_cast<int*>(d_rk->p) + k));
         { const Qr2ComposeItem* d = upload(s, ci); ProfScope ps(s, TNQS_PROF_SMALL, 0, 0); launch_qr2_compose(s->stream, d, (int)m); }
         for (size_t k = 0; k < m; ++k) {
             const size_t i = rs[k]; GateItem& it = gitems[rq[k]];

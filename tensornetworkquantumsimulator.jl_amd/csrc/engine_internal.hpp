@@ -7,6 +7,7 @@
 //   gate_schedule.cpp apply_gates: validation of the gate list, the step schedule (GateSchedule; host code, no device call)
 //   engine_runahead.cpp  deferred verification: checks, snapshots, the driver that runs a GateSchedule ahead of the device (RunAhead)
 //   engine_gates.cpp  apply_gates, one- and two-site gate batches, truncate
+//   gate_theta.cpp    the theta phase of a gate batch: route rule (theta_route; no device call), launch chain, small-SVD and second-pass items
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
 //   engine_loops.cpp  loop corrections: transfer matrices of simple cycles, ring products, traces (batched)
@@ -168,17 +169,18 @@ template <class Item> const Item* upload(State* s, const std::vector<Item>& v) {
 // happens after the stream has been synchronised (drained / sync / wrap below) -- by then every kernel that reads them has run.  Hence: only for
 // arrays whose kernels are ALL launched before the next host synchronisation of the phase (the GateItem array of a batch is read again after the
 // read-back of the ranks in the two-trip flow: it keeps its device copy).
-template <class Item> const Item* upload_small(State* s, const std::vector<Item>& v) {
-    if (v.empty()) return nullptr;
-    const size_t bytes = v.size() * sizeof(Item);
+inline const void* upload_small_bytes(State* s, const void* p, size_t bytes) {
     HostArena& ar = s->arena;
     if (!ar.base) ar = acquire_arena();
     const size_t aligned = (bytes + 255) & ~size_t(255);
     if (aligned > ar.cap) throw Err(TNQS_ERR_UNSUPPORTED, "descriptor batch too large");
     if (ar.off + aligned > ar.cap) { drain_for_arena_reuse(s); ar.off = 0; s->prof->chain = false; }
     char* h = ar.base + ar.off; ar.off += aligned;
-    std::memcpy(h, v.data(), bytes);
-    return reinterpret_cast<const Item*>(h);
+    std::memcpy(h, p, bytes);
+    return h;
+}
+template <class Item> const Item* upload_small(State* s, const std::vector<Item>& v) {
+    return v.empty() ? nullptr : static_cast<const Item*>(upload_small_bytes(s, v.data(), v.size() * sizeof(Item)));
 }
 
 struct ProfScope {
@@ -253,6 +255,34 @@ inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 int operator_sum(const double* mat, int d1, int d2, std::vector<std::complex<double>>& fa, std::vector<std::complex<double>>& fb);
 void exchange(State* s, size_t bytes_per_rank);                       // sharding.cpp
 void check_exchange(const State* s, size_t bytes_per_rank);           // call BEFORE enqueuing anything that writes into s->exch
+
+// ---- the theta phase of a two-site gate (gate_theta.cpp): TwoSiteBatch (engine_gates.cpp) and the kernel-level entry points (debug.cpp) run the same code --------
+// What a gate of operator-Schmidt rank kappa (0: no operator-sum factors) on a bond of dimension chi is offered, and the element counts (complex128) of its low-rank
+// workspaces, 0 where one is not handed out: nA = lowA (Mr K), nB = lowB (Nc K); low-rank route: nG = lowG, lowL, lowW each (K K); its preconditioned SVD (ComplexF32):
+// nQ = lowQ (Nc K); its second CholeskyQR pass (ComplexF64): nB1 = lowB1 (Nc K), nG2 = lowG2, lowL2, lowLc each (K K).  Host code, no device call; d^2 chi > 512 throws
+struct ThetaRoute { int n1, n2, Mr, Nc, cap, K; bool opsum, low, lowq; size_t nA, nB, nG, nQ, nB1, nG2; };
+ThetaRoute theta_route(bool F32, int d1, int d2, int chi, int kappa, int maxdim);
+struct ThetaLowWs { void *lowW, *lowB1, *lowG2, *lowL2, *lowLc; };      // a low-rank gate's workspaces that no GateItem field names (lowB1 .. lowLc: ComplexF64)
+// where the chain's own descriptor arrays go: the engine's pinned arena (upload_small) or a plain device allocation -- a function pointer, no heap traffic per call
+struct DescUpload {
+    const void* (*fn)(void* ctx, const void* p, size_t bytes); void* ctx;
+    template <class Item> const Item* vec(const std::vector<Item>& v) const { return v.empty() ? nullptr : static_cast<const Item*>(fn(ctx, v.data(), v.size() * sizeof(Item))); }
+};
+// gate_theta -> gate_theta_mm -> lowrank_g -> chol / chol_packed -> lowrank_m (ComplexF64: -> lowrank_bw -> lowrank_g -> chol -> lowrank_ll -> lowrank_m) -> theta_scale over
+// the gates of `items` (d_items: their device copy; ws[q]: of gate q, read where items[q].lowG is set).  d_fail1 / d_fail2: one zeroed failure flag per gate for the two
+// Cholesky passes.  last_stage: 0 gate_theta, 1 gate_theta_mm, 2 the low-rank block, 3 theta_scale (the engine always runs all of it)
+template <class T> void launch_theta_chain(hipStream_t st, const GateItem* d_items, const std::vector<GateItem>& items, const std::vector<ThetaLowWs>& ws,
+                                           int* d_fail1, int* d_fail2, DescUpload up, int last_stage = 3);
+// R = Sigma U^dagger of a site with fewer fibers than columns, from the SVD of the n x N matricised psi~ (f64; src [d][low][chi_b][hi], n = d chi_b, N = low hi, M: n N
+// complex128 of scratch): the two items of the site, appended, and the three dependent launches on `st`
+void small_svd_items(const void* src, void* M, void* GA, void* GV, int d, int low, int chi_b, int hi, std::vector<SmallSvdItem>& si, std::vector<JacobiItem>& sji);
+template <class T> void launch_small_svd(hipStream_t st, const SmallSvdItem* ds, const JacobiItem* dj, const std::vector<JacobiItem>& sji);
+// a site of the second factorisation pass: its first-pass factor (GW, GV, lam, idx, *r kept columns, n x n) and where X1 = R1^+ goes -> the items of qr2_rinv / qr2_compose
+struct Qr2Site {
+    const void *GW, *GV; const double* lam; const int* idx; const int* r; int n; void* X1;
+    Qr2RinvItem rinv() const { return Qr2RinvItem{GW, lam, idx, r, n, X1}; }
+    Qr2ComposeItem compose(const void* A2, const void* V2, double tau, void* GVout, void* GWout, int* rk) const { return Qr2ComposeItem{A2, V2, X1, GV, lam, idx, r, n, tau, GVout, GWout, rk}; }
+};
 
 
 

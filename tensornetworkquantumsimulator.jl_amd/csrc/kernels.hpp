@@ -55,6 +55,11 @@ inline bool bp_small_site_covers(int d, int z, const int* chi, size_t nelem) {
     for (int k = 0; k < z; ++k) if (chi[k] > 32) return false;
     return true;
 }
+// the matrix-core form of the kernel (SmallMsgItem::mfma): every leg 16-dimensional, the element count a multiple of 256
+inline bool bp_small_site_mfma_form(int z, const int* chi, size_t nelem) {
+    for (int k = 0; k < z; ++k) if (chi[k] != 16) return false;
+    return nelem % 256 == 0;
+}
 void launch_bp_small_site(hipStream_t s, const SmallMsgItem* d_items, int nitems, int max_elems);
 struct JacobiItem {       // one-sided Jacobi on A (m x n, col-major, ld = m); V (n x n) accumulates the rotations (null: not wanted)
     void* A; void* V; int m; int n; int* sweeps_out;
