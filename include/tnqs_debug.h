@@ -225,6 +225,39 @@ int tnqs_dbg_inner_gram(int dtype, int nitems, const int* shape, const void* X, 
  * guard, ..., guard as above.  rows or cols outside 1..64: TNQS_ERR_UNSUPPORTED, nothing is written */
 int tnqs_dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols, const int* nchunks, const void* partials, const void* old_msg, const int* has_old,
                             const int* normalize, void* new_msg, double* diff_out, double* sum_out, int guard);
+/* inner_scalar_kernel<T>, ONE launch over nitems vertex / edge scalars of the form network.  Item i: m_i, mr_i of rows[i] x cols[i] numbers [a + rows b], the items one after the
+ * other (a slot for every item, read only where present[2 i] / present[2 i + 1] != 0 -- 0 hands the kernel a null pointer, i.e. the rectangular delta); rawsum[2 i, 2 i + 1]
+ * (has_rawsum[i] == 0: a null pointer); normalize[i]; scale_a[i], scale_b[i] (has_scale[2 i], [2 i + 1] == 0: a null pointer).  out_re_im[2 i, 2 i + 1] = sum_ab m_i[a, b] mr_i[a, b],
+ * times rawsum_i where that is given, normalize[i] != 0 and it is not exactly zero, times the scale factors given.  out_re_im: guard, item 0 (one complex128), guard, ..., guard
+ * (guard counts complex128).  rows or cols outside 1..64: TNQS_ERR_UNSUPPORTED, nothing is written */
+int tnqs_dbg_inner_scalar(int dtype, int nitems, const int* rows, const int* cols, const void* m, const void* mr, const int* present, const double* rawsum, const int* has_rawsum,
+                          const int* normalize, const double* scale_a, const double* scale_b, const int* has_scale, double* out_re_im, int guard);
+/* ---- sampling (csrc/kernels_sample.hip), launched as csrc/engine_sample.cpp launches them ----
+ * site_prob_partial_kernel<T> on one site tensor of n = d k elements (site index fastest) and T = the tensor with its messages absorbed: partial holds `guard` doubles, the raw
+ * nblocks x 16 array (partial[16 b + s] = workgroup b's share of diag[s] = Re sum_l T[s, l] conj(psi[s, l]); slots s >= d are not written), `guard` doubles; it goes up as the
+ * caller filled it and comes back whole.  nblocks == 0: the engine's plan_site_prob; *nblocks_out (may be NULL) = the workgroups used.  partial == NULL: only *nblocks_out is
+ * filled (HOST ONLY) */
+int tnqs_dbg_site_prob(int dtype, int n, int d, const void* tabs, const void* psi, int nblocks, double* partial, int guard, int* nblocks_out);
+/* site_draw_kernel, one launch per item as the engine launches one per step.  Item i: partials_i (nblocks[i] x 16 doubles, the items one after the other), d[i], neg_tol[i], the
+ * uniform uniform[i] or, where use_counter[i] != 0, the counter-based one of counter[3 i .. 3 i + 2] = (seed, sample, step) (the kernel then gets a null uniform); draw[i].
+ * p_out: 16 doubles per item of which the kernel writes d[i]; x_out, px_out: one number per item (left as they were where draw[i] == 0); each laid out as guard, item 0, guard, ...,
+ * guard (elements of its own type), up as filled and back whole.  status_out[i]: the item's own status word, cleared before its launch (1: tr rho zero / negative / not finite,
+ * 2: a diagonal entry below -neg_tol tr) */
+int tnqs_dbg_site_draw(int nitems, const int* nblocks, const int* d, const double* partials, const double* neg_tol, const double* uniform, const int* use_counter,
+                       const uint64_t* counter, const int* draw, double* p_out, int* x_out, double* px_out, int* status_out, int guard);
+/* site_project_kernel<T>: out[i] = psi[x + d i], i < nout (psi: nout d numbers); x_on_device != 0: x goes through device memory and the kernel's host argument is one that clamps
+ * to another index; x outside 0 .. d - 1 is handed over as it is (the kernel clamps).  out: guard, nout numbers, guard */
+int tnqs_dbg_site_project(int dtype, int nout, int d, const void* psi, int x, int x_on_device, void* out, int guard);
+/* ---- the ComplexF32 d = 2 one-site gate with normalisation (csrc/kernels_util.hip: site1_c64_kernel, norm_factor_kernel, scale_kernel<T>) ----
+ * ONE launch of site1_c64_kernel over nitems tensors of npairs[i] (s = 0, 1) pairs, the items one after the other in `in`; gates: per item the 2 x 2 gate as the C ABI takes it
+ * (column-major G[s' + 2 s], 8 doubles re/im), packed into the kernel's item by the function the engine packs it with; nbx workgroups per item (the engine: 64).  out: guard, item 0,
+ * guard, ..., guard (complex64).  normalize != 0: partials (guard doubles, nitems nbx norm partials [item][workgroup], guard doubles) are written and ONE launch of norm_factor_kernel
+ * leaves factors (guard, 1 / sqrt(sum of item 0's partials), guard, ..., guard); normalize == 0: the kernel gets a null pointer and both arrays come back as they went up */
+int tnqs_dbg_site1(int nitems, const int* npairs, const void* in, const double* gates, int nbx, int normalize, void* out, double* partials, double* factors, int guard);
+/* norm_factor_kernel, ONE launch: factors_i = 1 / sqrt(sum of item i's npart[i] >= 0 partials), 1 where the sum is not positive; factors: guard, item 0 (one double), guard, ... */
+int tnqs_dbg_norm_factor(int nitems, const int* npart, const double* partials, double* factors, int guard);
+/* scale_kernel<T>, ONE launch: dst_i = src_i * (T)factor[i], len[i] numbers per item (any length); the factors are read from device memory as a pending scale factor is */
+int tnqs_dbg_scale(int dtype, int nitems, const int* len, const void* src, const double* factor, void* dst, int guard);
 /* tnqs_inner_bp with the bound on a batch's chain workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of messages it ran */
 int tnqs_dbg_inner_bp_ws(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, int64_t workspace_bytes, int* nbatches_out);
 #ifdef __cplusplus

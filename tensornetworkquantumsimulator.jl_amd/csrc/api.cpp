@@ -256,6 +256,15 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                  void dbg_inner_gram(int dtype, int nitems, const int* shape, const void* X, const void* Y, void* out, int max_chunks, int* nchunks_out, int guard, int* route);
                  void dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols, const int* nchunks, const void* partials, const void* old_msg, const int* has_old,
                                          const int* normalize, void* new_msg, double* diff, double* sum, int guard);
+                 void dbg_inner_scalar(int dtype, int nitems, const int* rows, const int* cols, const void* m, const void* mr, const int* present, const double* rawsum, const int* has_rawsum,
+                                       const int* normalize, const double* scale_a, const double* scale_b, const int* has_scale, double* out, int guard);
+                 void dbg_site_prob(int dtype, int n, int d, const void* tabs, const void* psi, int nblocks, double* partial, int guard, int* nblocks_out);
+                 void dbg_site_draw(int nitems, const int* nblocks, const int* d, const double* partials, const double* neg_tol, const double* uniform, const int* use_counter,
+                                    const unsigned long long* counter, const int* draw, double* p_out, int* x_out, double* px_out, int* status_out, int guard);
+                 void dbg_site_project(int dtype, int nout, int d, const void* psi, int x, int x_on_device, void* out, int guard);
+                 void dbg_site1(int nitems, const int* npairs, const void* in, const double* gates, int nbx, int normalize, void* out, double* partials, double* factors, int guard);
+                 void dbg_norm_factor(int nitems, const int* npart, const double* partials, double* factors, int guard);
+                 void dbg_scale(int dtype, int nitems, const int* len, const void* src, const double* factor, void* dst, int guard);
                  double dbg_pending_scale(State* s, int v); }
 extern "C" {
 int tnqs_dbg_default_sequence(tnqs_handle h, int* src, int* dst, int cap, int* n_out) {
@@ -414,6 +423,27 @@ int tnqs_dbg_inner_gram(int dtype, int nitems, const int* shape, const void* X, 
 int tnqs_dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols, const int* nchunks, const void* partials, const void* old_msg, const int* has_old,
                             const int* normalize, void* new_msg, double* diff_out, double* sum_out, int guard_elems) {
     return guard([&] { dbg_inner_finalize(dtype, nitems, rows, cols, nchunks, partials, old_msg, has_old, normalize, new_msg, diff_out, sum_out, guard_elems); });
+}
+int tnqs_dbg_inner_scalar(int dtype, int nitems, const int* rows, const int* cols, const void* m, const void* mr, const int* present, const double* rawsum, const int* has_rawsum,
+                          const int* normalize, const double* scale_a, const double* scale_b, const int* has_scale, double* out_re_im, int guard_elems) {
+    return guard([&] { dbg_inner_scalar(dtype, nitems, rows, cols, m, mr, present, rawsum, has_rawsum, normalize, scale_a, scale_b, has_scale, out_re_im, guard_elems); });
+}
+int tnqs_dbg_site_prob(int dtype, int n, int d, const void* tabs, const void* psi, int nblocks, double* partial, int guard_elems, int* nblocks_out) {
+    return guard([&] { dbg_site_prob(dtype, n, d, tabs, psi, nblocks, partial, guard_elems, nblocks_out); });
+}
+int tnqs_dbg_site_draw(int nitems, const int* nblocks, const int* d, const double* partials, const double* neg_tol, const double* uniform, const int* use_counter,
+                       const uint64_t* counter, const int* draw, double* p_out, int* x_out, double* px_out, int* status_out, int guard_elems) {
+    return guard([&] { dbg_site_draw(nitems, nblocks, d, partials, neg_tol, uniform, use_counter, reinterpret_cast<const unsigned long long*>(counter), draw, p_out, x_out, px_out, status_out, guard_elems); });
+}
+int tnqs_dbg_site_project(int dtype, int nout, int d, const void* psi, int x, int x_on_device, void* out, int guard_elems) {
+    return guard([&] { dbg_site_project(dtype, nout, d, psi, x, x_on_device, out, guard_elems); });
+}
+int tnqs_dbg_site1(int nitems, const int* npairs, const void* in, const double* gates, int nbx, int normalize, void* out, double* partials, double* factors, int guard_elems) {
+    return guard([&] { dbg_site1(nitems, npairs, in, gates, nbx, normalize, out, partials, factors, guard_elems); });
+}
+int tnqs_dbg_norm_factor(int nitems, const int* npart, const double* partials, double* factors, int guard_elems) { return guard([&] { dbg_norm_factor(nitems, npart, partials, factors, guard_elems); }); }
+int tnqs_dbg_scale(int dtype, int nitems, const int* len, const void* src, const double* factor, void* dst, int guard_elems) {
+    return guard([&] { dbg_scale(dtype, nitems, len, src, factor, dst, guard_elems); });
 }
 int tnqs_dbg_inner_bp_ws(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, int64_t workspace_bytes, int* nbatches_out) {
     return guard([&] { if (workspace_bytes < 1) throw Err(TNQS_ERR_INVALID, "dbg_inner_bp_ws: the workspace bound must be positive");

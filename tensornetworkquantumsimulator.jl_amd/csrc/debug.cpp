@@ -1395,4 +1395,162 @@ void dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* cols,
     if (diff) dD.down(diff, sizeof(double) * nitems);
     if (sum) dS.down(sum, sizeof(double) * 2 * nitems);
 }
+// ONE launch_inner_scalar<T> over nitems vertex / edge scalars, the descriptors filled as engine_inner.cpp (inner_bp) fills them: present[2 i], [2 i + 1]: m_i, mr_i
+// (0: a null pointer = the rectangular delta); has_rawsum[i], has_scale[2 i], [2 i + 1]: 0 hands the kernel a null pointer
+void dbg_inner_scalar(int dtype, int nitems, const int* rows, const int* cols, const void* m, const void* mr, const int* present, const double* rawsum, const int* has_rawsum,
+                      const int* normalize, const double* scale_a, const double* scale_b, const int* has_scale, double* out, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !rows || !cols || !m || !mr || !present || !rawsum || !has_rawsum || !normalize || !scale_a || !scale_b ||
+        !has_scale || !out || guard < 0)
+        throw Err(TNQS_ERR_INVALID, "dbg_inner_scalar: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sM, sR, sSum, sSc; Guarded gO((size_t)guard * 16);
+    for (int i = 0; i < nitems; ++i) {
+        if (rows[i] < 1 || cols[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_inner_scalar: rows, cols >= 1");
+        if (!inner_gram_covers(rows[i], cols[i])) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_inner_scalar: rows, cols <= 64");
+        const size_t mb = (size_t)rows[i] * cols[i] * esz;
+        sM.add(mb); sR.add(mb); sSum.add(16); sSc.add(8); sSc.add(8); gO.add(16);
+    }
+    need_gpu();
+    sM.alloc(); sR.alloc(); sSum.alloc(); sSc.alloc(); gO.alloc();
+    put_all(sM, m); put_all(sR, mr); put_all(sSum, rawsum);
+    std::vector<InnerScalarItem> si(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        sSc.put(2 * i, scale_a + i); sSc.put(2 * i + 1, scale_b + i);
+        si[i] = InnerScalarItem{present[2 * i] ? sM.at(i) : nullptr, present[2 * i + 1] ? sR.at(i) : nullptr, rows[i], cols[i], has_rawsum[i] ? (const double*)sSum.at(i) : nullptr,
+                                normalize[i], has_scale[2 * i] ? (const double*)sSc.at(2 * i) : nullptr, has_scale[2 * i + 1] ? (const double*)sSc.at(2 * i + 1) : nullptr, (double*)gO.at(i)};
+    }
+    DBuf dI(sizeof(InnerScalarItem) * nitems);
+    sM.up(); sR.up(); sSum.up(); sSc.up(); gO.up(out); dI.up(si.data(), sizeof(InnerScalarItem) * nitems);
+    if (dtype == TNQS_C64) launch_inner_scalar<float>(nullptr, (const InnerScalarItem*)dI.p, nitems); else launch_inner_scalar<double>(nullptr, (const InnerScalarItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gO.down(out, "out");
+}
+
+// ---- sampling (kernels_sample.hip), launched as engine_sample.cpp launches them ------------------------------------------------------------------------------------
+// site_prob_partial_kernel<T> on one site tensor of n = d k elements: the raw nblocks x 16 partial array between guard bands of `guard` doubles.  nblocks == 0: the
+// engine's plan_site_prob.  partial == NULL: only *nblocks_out is filled (HOST ONLY)
+void dbg_site_prob(int dtype, int n, int d, const void* tabs, const void* psi, int nblocks, double* partial, int guard, int* nblocks_out) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || n < 1 || d < 1 || d > 16 || n % d || nblocks < 0 || nblocks > 4096 || guard < 0 || (partial && (!tabs || !psi)))
+        throw Err(TNQS_ERR_INVALID, "dbg_site_prob: bad arguments");
+    const int nb = nblocks ? nblocks : plan_site_prob((size_t)n, d);
+    if (nblocks_out) *nblocks_out = nb;
+    if (!partial) return;
+    need_gpu();
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sT, sP; Guarded gP((size_t)guard * 8);
+    sT.add((size_t)n * esz); sP.add((size_t)n * esz); gP.add((size_t)nb * 16 * 8);
+    sT.alloc(); sP.alloc(); gP.alloc();
+    sT.put(0, tabs); sP.put(0, psi);
+    sT.up(); sP.up(); gP.up(partial);
+    if (dtype == TNQS_C64) launch_site_prob_partial<float>(nullptr, sT.at(0), sP.at(0), (size_t)n, d, nb, (double*)gP.at(0));
+    else launch_site_prob_partial<double>(nullptr, sT.at(0), sP.at(0), (size_t)n, d, nb, (double*)gP.at(0));
+    HIPCHK(hipDeviceSynchronize());
+    gP.down(partial, "partial");
+}
+// site_draw_kernel, one launch per item (the engine launches one per step): partials: nblocks[i] x 16 doubles per item, one item after the other; use_counter[i] == 0: the
+// uniform is uniform[i], else counter-based from counter[3 i .. 3 i + 2] = (seed, sample, step) and the kernel gets a null uniform.  p_out: 16 doubles per item (the kernel
+// writes d[i]), x_out, px_out: one number per item, all three between guard bands of `guard` elements; status_out[i]: the item's own status word, cleared before its launch
+void dbg_site_draw(int nitems, const int* nblocks, const int* d, const double* partials, const double* neg_tol, const double* uniform, const int* use_counter,
+                   const unsigned long long* counter, const int* draw, double* p_out, int* x_out, double* px_out, int* status_out, int guard) {
+    if (nitems < 1 || !nblocks || !d || !partials || !neg_tol || !uniform || !use_counter || !counter || !draw || !p_out || !x_out || !px_out || !status_out || guard < 0)
+        throw Err(TNQS_ERR_INVALID, "dbg_site_draw: bad arguments");
+    Slots sPart, sU; Guarded gP((size_t)guard * 8), gX((size_t)guard * 4), gPx((size_t)guard * 8);
+    for (int i = 0; i < nitems; ++i) {
+        if (nblocks[i] < 1 || d[i] < 1 || d[i] > 16) throw Err(TNQS_ERR_INVALID, "dbg_site_draw: nblocks >= 1, 1 <= d <= 16");
+        sPart.add((size_t)nblocks[i] * 16 * 8); sU.add(8); gP.add(16 * 8); gX.add(4); gPx.add(8);
+    }
+    need_gpu();
+    sPart.alloc(); sU.alloc(); gP.alloc(); gX.alloc(); gPx.alloc();
+    put_all(sPart, partials); put_all(sU, uniform);
+    DBuf dSt(sizeof(int) * nitems);
+    HIPCHK(hipMemset(dSt.p, 0, sizeof(int) * nitems));
+    sPart.up(); sU.up(); gP.up(p_out); gX.up(x_out); gPx.up(px_out);
+    for (int i = 0; i < nitems; ++i)
+        launch_site_draw(nullptr, (const double*)sPart.at(i), nblocks[i], d[i], neg_tol[i], use_counter[i] ? nullptr : (const double*)sU.at(i), counter[3 * i], counter[3 * i + 1],
+                         counter[3 * i + 2], draw[i] != 0, (double*)gP.at(i), (int*)gX.at(i), (double*)gPx.at(i), (int*)dSt.p + i);
+    HIPCHK(hipDeviceSynchronize());
+    gP.down(p_out, "p_out"); gX.down(x_out, "x_out"); gPx.down(px_out, "px_out");
+    dSt.down(status_out, sizeof(int) * nitems);
+}
+// site_project_kernel<T>: out[i] = psi[x + d i], i < nout; x_on_device != 0: x goes through device memory and the host argument is one that clamps to another index
+void dbg_site_project(int dtype, int nout, int d, const void* psi, int x, int x_on_device, void* out, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nout < 1 || d < 1 || d > 16 || (long long)nout * d > INT_MAX / 2 || !psi || !out || guard < 0)
+        throw Err(TNQS_ERR_INVALID, "dbg_site_project: bad arguments");
+    need_gpu();
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sP, sX; Guarded gO((size_t)guard * esz);
+    sP.add((size_t)nout * d * esz); sX.add(4); gO.add((size_t)nout * esz);
+    sP.alloc(); sX.alloc(); gO.alloc();
+    sP.put(0, psi); sX.put(0, &x);
+    sP.up(); sX.up(); gO.up(out);
+    const int* dx = x_on_device ? (const int*)sX.at(0) : nullptr;
+    const int xh = x_on_device ? (x <= 0 ? INT_MAX : -1) : x;
+    if (dtype == TNQS_C64) launch_site_project<float>(nullptr, sP.at(0), gO.at(0), (size_t)nout, d, dx, xh); else launch_site_project<double>(nullptr, sP.at(0), gO.at(0), (size_t)nout, d, dx, xh);
+    HIPCHK(hipDeviceSynchronize());
+    gO.down(out, "out");
+}
+
+// ---- the ComplexF32 d = 2 one-site gate with normalisation (kernels_util.hip), set up as apply_one_site_batch / norm_and_replace / materialize_scale set it up ----------
+// ONE launch_site1_c64 over nitems tensors of npairs[i] (s = 0, 1) pairs; gates: 8 doubles per item, column-major G[s' + 2 s] re/im as the C ABI takes them, packed by
+// pack_site1_gate.  normalize != 0: the kernel leaves nbx norm partials per item in `partials` (nitems nbx doubles between two guard bands) and ONE launch_norm_factor
+// turns them into `factors` (one double per item between guard bands, 256-byte slots on the device); normalize == 0: the kernel gets a null pointer, both stay as they were
+void dbg_site1(int nitems, const int* npairs, const void* in, const double* gates, int nbx, int normalize, void* out, double* partials, double* factors, int guard) {
+    if (nitems < 1 || !npairs || !in || !gates || nbx < 1 || nbx > 65535 || !out || !partials || !factors || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_site1: bad arguments");
+    Slots sIn; Guarded gO((size_t)guard * 8), gPart((size_t)guard * 8), gF((size_t)guard * 8);
+    for (int i = 0; i < nitems; ++i) {
+        if (npairs[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_site1: npairs >= 1");
+        sIn.add((size_t)npairs[i] * 16); gO.add((size_t)npairs[i] * 16); gF.add(8);
+    }
+    gPart.add((size_t)nitems * nbx * 8);
+    need_gpu();
+    sIn.alloc(); gO.alloc(); gPart.alloc(); gF.alloc();
+    put_all(sIn, in);
+    std::vector<Site1Item> items(nitems); std::vector<NormFactorItem> nf(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        Site1Item it{}; it.in = sIn.at(i); it.out = gO.at(i); it.npairs = (size_t)npairs[i];
+        pack_site1_gate(gates + 8 * (size_t)i, it.g);
+        items[i] = it;
+        nf[i] = NormFactorItem{(const double*)gPart.at(0) + (size_t)i * nbx, nbx, (double*)gF.at(i)};
+    }
+    DBuf dI(sizeof(Site1Item) * nitems), dN(sizeof(NormFactorItem) * nitems);
+    sIn.up(); gO.up(out); gPart.up(partials); gF.up(factors);
+    dI.up(items.data(), sizeof(Site1Item) * nitems); dN.up(nf.data(), sizeof(NormFactorItem) * nitems);
+    launch_site1_c64(nullptr, (const Site1Item*)dI.p, nitems, nbx, normalize ? (double*)gPart.at(0) : nullptr);
+    if (normalize) launch_norm_factor(nullptr, (const NormFactorItem*)dN.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gO.down(out, "out"); gPart.down(partials, "partials"); gF.down(factors, "factors");
+}
+// ONE launch_norm_factor: item i has npart[i] partials (one item after the other); factors: one double per item between guard bands
+void dbg_norm_factor(int nitems, const int* npart, const double* partials, double* factors, int guard) {
+    if (nitems < 1 || !npart || !partials || !factors || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_norm_factor: bad arguments");
+    Slots sP; Guarded gF((size_t)guard * 8);
+    for (int i = 0; i < nitems; ++i) { if (npart[i] < 0) throw Err(TNQS_ERR_INVALID, "dbg_norm_factor: npart >= 0"); sP.add((size_t)npart[i] * 8); gF.add(8); }
+    need_gpu();
+    sP.alloc(); gF.alloc();
+    put_all(sP, partials);
+    std::vector<NormFactorItem> nf(nitems);
+    for (int i = 0; i < nitems; ++i) nf[i] = NormFactorItem{(const double*)sP.at(i), npart[i], (double*)gF.at(i)};
+    DBuf dN(sizeof(NormFactorItem) * nitems);
+    sP.up(); gF.up(factors); dN.up(nf.data(), sizeof(NormFactorItem) * nitems);
+    launch_norm_factor(nullptr, (const NormFactorItem*)dN.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gF.down(factors, "factors");
+}
+// ONE launch_scale<T>: dst_i = src_i * (T)factor[i], len[i] numbers per item, the factor read from device memory as the pending scale factor is
+void dbg_scale(int dtype, int nitems, const int* len, const void* src, const double* factor, void* dst, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || nitems < 1 || !len || !src || !factor || !dst || guard < 0) throw Err(TNQS_ERR_INVALID, "dbg_scale: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots sS, sF; Guarded gD((size_t)guard * esz);
+    for (int i = 0; i < nitems; ++i) { if (len[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_scale: len >= 1"); sS.add((size_t)len[i] * esz); sF.add(8); gD.add((size_t)len[i] * esz); }
+    need_gpu();
+    sS.alloc(); sF.alloc(); gD.alloc();
+    put_all(sS, src); put_all(sF, factor);
+    std::vector<ScaleItem> items(nitems);
+    for (int i = 0; i < nitems; ++i) items[i] = ScaleItem{sS.at(i), gD.at(i), (size_t)len[i], (const double*)sF.at(i)};
+    DBuf dI(sizeof(ScaleItem) * nitems);
+    sS.up(); sF.up(); gD.up(dst); dI.up(items.data(), sizeof(ScaleItem) * nitems);
+    if (dtype == TNQS_C64) launch_scale<float>(nullptr, (const ScaleItem*)dI.p, nitems); else launch_scale<double>(nullptr, (const ScaleItem*)dI.p, nitems);
+    HIPCHK(hipDeviceSynchronize());
+    gD.down(dst, "dst");
+}
 }  // namespace tnqs

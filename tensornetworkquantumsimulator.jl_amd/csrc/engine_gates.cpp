@@ -134,10 +134,7 @@ template <class T> static void apply_one_site_batch(State* s, const std::vector<
                 SD sd = site_dims(s, g1.v);
                 Site1Item it{}; Buf out = dalloc(s, sd.n * esz);
                 it.in = s->site[g1.v]->p; it.out = out->p; it.npairs = sd.n / 2;
-                // column-major G[s' + 2 s]: g00 = mat[0], g10 = mat[1], g01 = mat[2], g11 = mat[3]
-                const double* m = g1.mat;
-                it.g[0] = (float)m[0]; it.g[1] = (float)m[1]; it.g[2] = (float)m[4]; it.g[3] = (float)m[5];
-                it.g[4] = (float)m[2]; it.g[5] = (float)m[3]; it.g[6] = (float)m[6]; it.g[7] = (float)m[7];
+                pack_site1_gate(g1.mat, it.g);
                 verts.push_back(g1.v); outs.push_back(out); tb.push_back((int)items.size() * NBX); nt.push_back(NBX);
                 items.push_back(it);
                 bytes += 2.0 * sd.n * esz; flops += 8.0 * sd.n * 2;

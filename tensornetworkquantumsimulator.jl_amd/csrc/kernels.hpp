@@ -166,6 +166,12 @@ void launch_qr2_rinv(hipStream_t s, const Qr2RinvItem* d_items, int nitems);
 void launch_qr2_compose(hipStream_t s, const Qr2ComposeItem* d_items, int nitems);
 
 struct Site1Item { const void* in; void* out; float g[8]; size_t npairs; };   // d = 2 one-site gate: g = (g00, g01, g10, g11) re/im
+// the gate as the C ABI takes it (column-major G[s' + 2 s] as (re, im) doubles: g00 = mat[0], g10 = mat[1], g01 = mat[2], g11 = mat[3]) into the row-major g of the item:
+// the one packing of the engine (apply_one_site_batch) and of tnqs_dbg_site1
+inline void pack_site1_gate(const double* m, float* g) {
+    g[0] = (float)m[0]; g[1] = (float)m[1]; g[2] = (float)m[4]; g[3] = (float)m[5];
+    g[4] = (float)m[2]; g[5] = (float)m[3]; g[6] = (float)m[6]; g[7] = (float)m[7];
+}
 struct DiagItem { void* out; const double* S; int chi; };          // dense diag(S) message
 struct ScaleItem { const void* src; void* dst; size_t n; const double* factor; };      // dst = src * (*factor)
 struct NormFactorItem { const double* norm_partials; int npart; double* factor; };      // *factor = 1/sqrt(sum partials)  (1 when the sum is not positive)
