@@ -188,6 +188,20 @@ int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int3
  * TNQS_ERR_INVALID (before any device work): a bad vertex, consecutive vertices that are not adjacent, a repeated vertex, a chord, a length below 2, a null output;
  * TNQS_ERR_UNSUPPORTED: sharded handles, an inner vertex of degree above 7, chi_a^2 chi_b^2 above INT_MAX / 4, a bond beyond the edge kernel's LDS, d_p0 above 4. */
 int tnqs_rdm_paths(tnqs_handle h, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out_rho);
+/* Entanglement spectra of bonds from the BP messages in one call (the reference's renyi_entropy(bp_cache, e; alpha), src/entanglement.jl:73-86, up to the eigenvalues).
+ * For request i = (u, v) with m1 = message u -> v and m2 = message v -> u (layout of tnqs_get_message):
+ *   r = m2^{1/2} from the Hermitian eigen decomposition of m2 in f64 whatever the handle's type, an eigenvalue x with |x| < cutoff replaced by 0, cutoff = 10 eps of the
+ *   handle's real type (1.1920929e-6 / 2.220446e-15, absolute; pseudo_sqrt_inv_sqrt, src/utils.jl:18-26);  rho = r m1^T r;  spectrum = eigenvalues of rho / tr rho.
+ * out_spectra: request i receives chi_i doubles (tnqs_bond_dim), one request after the other: descending, signed, summing to 1, UNFILTERED (the reference's renyi_entropy drops
+ * |lambda| <= 10 eps before the logarithm; that is left to the caller).  edge_u == NULL or edge_v == NULL: every edge in tnqs_create order as (src, dst), n_edges is not read
+ * then; an empty call passes lists with n_edges = 0.  Both orientations and repeats are allowed and each is computed as listed: the root is taken of the message TOWARDS the
+ * first listed vertex ((u, v) and (v, u) have the same spectrum up to rounding).  All arithmetic is complex128 / f64 on the device from the stored messages, one workgroup per
+ * request and one launch per stage over all requests of the call (workspace: 64 chi^2 bytes per request; each eigen stage is one launch of the LDS-resident Jacobi over the
+ * bonds with chi <= 70 and one of the global-memory Jacobi over the rest); the call ends with one read-back.  The handle is not changed.
+ * TNQS_ERR_INVALID (before any device work): a bad vertex, a pair that is not an edge, a null output with work to do; TNQS_ERR_UNSUPPORTED: sharded handles, chi > 256;
+ * TNQS_ERR_NUMERIC: an eigenvalue of m2 at or below -cutoff (the reference's DomainError: square root of a negative real), or a trace of rho that is not positive and finite
+ * (tnqs_last_error says which). */
+int tnqs_bond_spectra(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_spectra);
 /* all-vertex <op_v>: ops is nv consecutive d x d matrices; out is nv complex128 */
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out_re_im);
 

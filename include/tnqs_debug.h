@@ -172,6 +172,14 @@ int tnqs_dbg_rdm_paths_ws(tnqs_handle h, int npaths, const int32_t* path_len, co
 /* tnqs_rdm_edges with the bound on a batch's chain workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of ends it ran */
 int tnqs_dbg_rdm_edges_ws(tnqs_handle h, int n_edges, const int32_t* eu, const int32_t* ev, double* out,
                           int64_t workspace_bytes, int* nbatches_out);
+/* ---- bond entanglement spectra (csrc/kernels_spectrum.hip, csrc/engine_spectra.cpp) ----
+ * stages A-D of tnqs_bond_spectra over nitems bonds of different chi in ONE launch per stage, set up and sized exactly as the engine does (env_prepare<T>, jacobi<double> with V,
+ * bond_rho_kernel<T>, jacobi<double> on W, bond_spectrum_finish_kernel; each Jacobi stage: the LDS-resident kernel over the items whose f64 matrix with V fits, chi <= 70, the global-memory one over the rest).
+ * m1 / m2: the items' chi[i] x chi[i] messages u -> v / v -> u one after the other, column-major, in the dtype (0 c64, 1 c128); present[2 i] / present[2 i + 1] = 0 hands the
+ * kernels a null pointer for m1 / m2 (the identity; the slot is not read).  The cutoff is 10 eps of the dtype's real type.  out (double): `guard` elements, item 0 (chi[0]
+ * eigenvalues of rho / tr rho, descending), `guard` elements, item 1, ..., `guard` elements -- it goes up as the caller filled it and comes back whole; flags_out: one int per
+ * item, bit 1: an eigenvalue of m2 at or below -cutoff, bit 2: tr rho not positive and finite.  chi > 256: TNQS_ERR_UNSUPPORTED, nothing is written */
+int tnqs_dbg_bond_spectrum(int dtype, int nitems, const int* chi, const void* m1, const void* m2, const int* present, double* out, int* flags_out, int guard);
 /* the pending real scale factor of the site tensor of v (a normalising gate only records 1/||psi_v||; the tensor the reference holds is the stored one times it): 1 when none is pending */
 int tnqs_dbg_pending_scale(tnqs_handle h, int v, double* factor);
 /* ---- the gate path's per-gate small algebra (csrc/kernels_theta.hip and the small_svd_* kernels of csrc/kernels_svd.hip; dtype 0 c64 = T float, 1 c128 = T double).  ONE launch

@@ -93,6 +93,7 @@ _SIGS = {
     "tnqs_expect_1site": ([H, C.c_int, _DP, _DP], C.c_int),
     "tnqs_rdm_edges": ([H, C.c_int, _I32P, _I32P, _DP], C.c_int),
     "tnqs_rdm_paths": ([H, C.c_int, _I32P, _I32P, _DP], C.c_int),
+    "tnqs_bond_spectra": ([H, C.c_int, _I32P, _I32P, _DP], C.c_int),
     "tnqs_inner_bp": ([H, H, C.POINTER(BpOpts), _DP, C.POINTER(C.c_int), _DP], C.c_int),
     "tnqs_expect_all": ([H, _DP, _DP], C.c_int),
     "tnqs_expect_region": ([H, C.c_int, _I32P, _I32P, _DP, _DP], C.c_int),

@@ -14,6 +14,7 @@ reference repo):
   sample(psi, nsamples; alg = "bp")                                       src/sampling.jl:3-46
   norm_sqr / norm (alg = "bp", "loopcorrections"), loopcorrected_partitionfunction   src/norm_sqr.jl:10-18,62-78, src/MessagePassing/loopcorrection.jl:3-14
   inner / log_inner (alg = "bp")                                          src/inner.jl:65-69, src/Forms/bilinearform.jl:16-25
+  bond_spectra / bond_entropies / renyi_entropy / von_neumann_... / second_renyi_entanglement_entropy   src/entanglement.jl:21-29,73-159 (alg = "bp")
 Every flop runs in libtnqs_hip.so; this file only marshals arguments through the C ABI (include/tnqs.h)."""
 from __future__ import annotations
 
@@ -737,6 +738,141 @@ def rdm(bpc: BeliefPropagationCache, v) -> np.ndarray:
     L.check(L.lib.tnqs_rdm_1site(bpc._h, bpc.graph.index[v], out.ctypes.data_as(C.POINTER(C.c_double))))
     out = np.ascontiguousarray(out)
     return out / np.trace(out)
+
+
+def _entropy_threshold(dtype) -> float:
+    """10 eps of the real type of `dtype`: the reference's filter on the eigenvalues of a density matrix (entanglement.jl:26)"""
+    dt = np.dtype(dtype)
+    real = np.float32 if dt in (np.dtype(np.float32), np.dtype(np.complex64)) else np.float64
+    return 10.0 * float(np.finfo(real).eps)
+
+
+def _check_alpha(alpha) -> float:
+    if isinstance(alpha, (bool, complex, np.complexfloating)) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not alpha >= 0:
+        raise L.TnqsArgumentError(f"renyi_entropy: the Renyi index must be real and >= 0 (received {alpha!r})")
+    return float(alpha)
+
+
+def _renyi_from_spectrum(lam, alpha: float, threshold: float) -> float:
+    """renyi_entropy on eigenvalues (entanglement.jl:26-28): those with |lambda| <= threshold are dropped; alpha = 1: -sum lambda log lambda, otherwise
+    log(sum lambda^alpha) / (1 - alpha).  A kept negative eigenvalue under a logarithm or a non-integer power is Julia's DomainError"""
+    lam = np.asarray(lam, dtype=np.float64)
+    lam = lam[np.abs(lam) > threshold]
+    if alpha == 1.0:
+        if np.any(lam < 0):
+            raise L.TnqsDomainError("renyi_entropy: log of a negative eigenvalue of the density matrix")
+        return float(-np.sum(lam * np.log(lam)))
+    if alpha != int(alpha) and np.any(lam < 0):
+        raise L.TnqsDomainError("renyi_entropy: non-integer power of a negative eigenvalue of the density matrix")
+    s = float(np.sum(lam ** (int(alpha) if alpha == int(alpha) else alpha)))
+    if s < 0:
+        raise L.TnqsDomainError("renyi_entropy: log of a negative sum of eigenvalue powers")
+    with np.errstate(divide="ignore"):
+        return float(np.log(s) / (1.0 - alpha))
+
+
+def _bond_spectra_raw(bpc: BeliefPropagationCache, edges) -> Tuple[list, List[np.ndarray]]:
+    """tnqs_bond_spectra: the spectra of `edges` (None: every edge of the graph) in request order, one device call"""
+    g = bpc.graph
+    req = list(g.edges) if edges is None else [tuple(e) for e in edges]
+    for e in req:
+        if len(e) != 2 or e[0] not in g.index or e[1] not in g.index or e[1] not in g.neighbors(e[0]):
+            raise L.TnqsArgumentError(f"{e!r} is not an edge of the graph: a bond spectrum belongs to two adjacent vertices")
+    if not req:
+        return [], []
+    chis = [bpc.bond_dim(a, b) for (a, b) in req]
+    out = np.zeros(sum(chis), dtype=np.float64)
+    if edges is None:
+        up, vp = None, None
+    else:
+        _u, up = L.i32([g.index[a] for (a, b) in req])
+        _v, vp = L.i32([g.index[b] for (a, b) in req])
+    L.check(L.lib.tnqs_bond_spectra(bpc._h, len(req), up, vp, out.ctypes.data_as(C.POINTER(C.c_double))))
+    offs = np.concatenate([[0], np.cumsum(chis)])
+    return req, [out[offs[i]:offs[i + 1]].copy() for i in range(len(req))]
+
+
+def bond_spectra(bpc: BeliefPropagationCache, edges=None) -> Dict:
+    """entanglement spectra of bonds from the BP messages, all in one device call: {(u, v): lambda} with lambda the eigenvalues of rho / tr rho,
+    rho = sqrt(m_vu) m_uv^T sqrt(m_vu) (entanglement.jl:73-86), as a float64 array of chi entries -- descending, summing to 1, UNFILTERED.  edges = None: every edge of the
+    graph; (v, u) and repeats are computed as listed (a repeated key keeps its last answer; bond_entropies keeps all).  Exact on trees (the Schmidt spectrum squared)"""
+    req, spec = _bond_spectra_raw(bpc, edges)
+    return dict(zip(req, spec))
+
+
+def bond_entropies(bpc: BeliefPropagationCache, alpha=1, edges=None) -> np.ndarray:
+    """Renyi entropies of order alpha (1: von Neumann) of the listed bonds (None: every edge of the graph, in its order), in request order, from ONE device call;
+    the eigenvalues with |lambda| <= 10 eps(real type of the state) are dropped on the host as the reference drops them"""
+    a = _check_alpha(alpha)
+    _req, spec = _bond_spectra_raw(bpc, edges)
+    if not spec:
+        return np.zeros(0, dtype=np.float64)
+    thr = _entropy_threshold(bpc.dtype)
+    return np.array([_renyi_from_spectrum(lam, a, thr) for lam in spec], dtype=np.float64)
+
+
+def renyi_entropy(x, where=None, alpha=None, alg: str = "bp", normalize: bool = True, cache_update_kwargs: Optional[dict] = None, device: int = 0) -> float:
+    """renyi_entropy of the reference (src/entanglement.jl):
+      renyi_entropy(rho, alpha, normalize=True)     rho a square numpy matrix (:21-29), on the host: eigenvalues of the Hermitian matrix rho (/ tr rho), those with
+                                                    |lambda| <= 10 eps(real dtype of rho) dropped
+      renyi_entropy(bpc, (u, v), alpha)             the bond formula from the two messages of the edge (:73-86), on the device (bond_spectra)
+      renyi_entropy(bpc, [v] | [u, w], alpha)       entropy of the reduced density matrix of one vertex or of a pair of vertices, adjacent or not (:135-138; rdm,
+                                                    rdm_edges, rdm_pairs); longer lists are not supported
+      renyi_entropy(psi, ..., alpha)                a TensorNetworkState: a cache is built on `device` and updated with cache_update_kwargs (default
+                                                    default_bp_update_kwargs) first (:110-114)
+    alpha real and >= 0 (1: von Neumann).  Only alg = "bp"."""
+    if isinstance(x, np.ndarray):
+        if alpha is None:                              # renyi_entropy(rho, alpha)
+            where, alpha = None, where
+        a = _check_alpha(alpha)
+        if x.ndim != 2 or x.shape[0] != x.shape[1]:
+            raise L.TnqsArgumentError(f"renyi_entropy: a density matrix is square (received shape {x.shape})")
+        rho = x if np.issubdtype(x.dtype, np.inexact) else x.astype(np.float64)
+        thr = _entropy_threshold(rho.dtype)
+        if normalize:
+            rho = rho / np.trace(rho)
+        lam = np.linalg.eigvalsh(rho, UPLO="U")                                    # Hermitian(rho): the upper triangle
+        return _renyi_from_spectrum(lam, a, thr)
+    if alg != "bp":
+        raise L.TnqsError(f'renyi_entropy: algorithm choice not supported; supported on the HIP path: "bp" (received {alg!r})')
+    a = _check_alpha(alpha)
+    if not isinstance(x, (TensorNetworkState, BeliefPropagationCache)):
+        raise TypeError("renyi_entropy: expected a matrix, a TensorNetworkState or a BeliefPropagationCache")
+    g = x.graph
+    if isinstance(where, tuple):
+        if len(where) != 2 or where[0] not in g.index or where[1] not in g.index or where[1] not in g.neighbors(where[0]):
+            raise L.TnqsArgumentError(f"renyi_entropy: {where!r} is not an edge of the graph")
+    elif isinstance(where, list):
+        if len(where) not in (1, 2) or any(v not in g.index for v in where) or len(set(where)) != len(where):
+            raise L.TnqsArgumentError(f"renyi_entropy: only single vertices and pairs of vertices are supported, got {where!r}")
+    else:
+        raise L.TnqsArgumentError("renyi_entropy: `where` is an edge (a 2-tuple of adjacent vertices) or a list of one or two vertices")
+    if isinstance(x, TensorNetworkState):
+        bpc = BeliefPropagationCache(x, device=device)
+        bpc = update(bpc, **(bpc.default_bp_update_kwargs() if cache_update_kwargs is None else cache_update_kwargs))
+    else:
+        bpc = x
+    thr = _entropy_threshold(bpc.dtype)
+    if isinstance(where, tuple):
+        return _renyi_from_spectrum(_bond_spectra_raw(bpc, [where])[1][0], a, thr)
+    if len(where) == 1:
+        rho = rdm(bpc, where[0])
+    elif where[1] in g.neighbors(where[0]):
+        rho = rdm_edges(bpc, [tuple(where)])[tuple(where)]
+    else:
+        rho = rdm_pairs(bpc, [tuple(where)])[tuple(where)]
+    # reduced_density_matrix(...; normalize = false) then renyi_entropy(...; normalize = true): the filter sees the state's real type
+    return _renyi_from_spectrum(np.linalg.eigvalsh(rho, UPLO="U"), a, thr)
+
+
+def von_neumann_entanglement_entropy(*args, **kwargs) -> float:
+    """renyi_entropy with alpha = 1 (entanglement.jl:159)"""
+    return renyi_entropy(*args, **kwargs, alpha=1)
+
+
+def second_renyi_entanglement_entropy(*args, **kwargs) -> float:
+    """renyi_entropy with alpha = 2 (entanglement.jl:149)"""
+    return renyi_entropy(*args, **kwargs, alpha=2)
 
 
 def _collect_observable(obs, g):

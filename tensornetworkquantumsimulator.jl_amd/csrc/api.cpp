@@ -138,6 +138,9 @@ int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, cons
 int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_rho) {
     return guard([&] { rdm_edges(S(h), n_edges, edge_u, edge_v, out_rho); });
 }
+int tnqs_bond_spectra(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_spectra) {
+    return guard([&] { bond_spectra(S(h), n_edges, edge_u, edge_v, out_spectra); });
+}
 int tnqs_rdm_paths(tnqs_handle h, int npaths, const int32_t* path_len, const int32_t* path_verts, double* out_rho) {
     return guard([&] { rdm_paths(S(h), npaths, path_len, path_verts, out_rho); });
 }
@@ -241,6 +244,7 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                                    const double* scale_u, const double* scale_v, void* out, int guard);
                  void dbg_edge_rdm_mixed(int ptype_u, int ptype_v, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u,
                                          const void* partial_v, const double* scale_u, const double* scale_v, void* out, int guard);
+                 void dbg_bond_spectrum(int dtype, int nitems, const int* chi, const void* m1, const void* m2, const int* present, double* out, int* flags_out, int guard);
                  void dbg_path_apply(int ptype_in, int dtype, int nitems, const int* d, const int* chi_a, const int* chi_b, const int* nchunks_in, const int* ksplit, const void* L_in, const void* T,
                                      const double* scale, void* L_out, int guard);
                  int dbg_operator_sum(const void* gate, int d1, int d2, void* fa_out, void* fb_out);
@@ -378,6 +382,9 @@ int tnqs_dbg_rdm_edges_ws(tnqs_handle h, int n_edges, const int32_t* eu, const i
 int tnqs_dbg_edge_rdm_mixed(int ptype_u, int ptype_v, int nitems, const int* du, const int* dv, const int* chi, const int* nchunks_u, const int* nchunks_v, const void* partial_u,
                             const void* partial_v, const double* scale_u, const double* scale_v, void* out, int guard_elems) {
     return guard([&] { dbg_edge_rdm_mixed(ptype_u, ptype_v, nitems, du, dv, chi, nchunks_u, nchunks_v, partial_u, partial_v, scale_u, scale_v, out, guard_elems); });
+}
+int tnqs_dbg_bond_spectrum(int dtype, int nitems, const int* chi, const void* m1, const void* m2, const int* present, double* out, int* flags_out, int guard_elems) {
+    return guard([&] { dbg_bond_spectrum(dtype, nitems, chi, m1, m2, present, out, flags_out, guard_elems); });
 }
 int tnqs_dbg_path_apply(int ptype_in, int dtype, int nitems, const int* d, const int* chi_a, const int* chi_b, const int* nchunks_in, const int* ksplit, const void* L_in, const void* T,
                         const double* scale, void* L_out, int guard_elems) {

@@ -1048,6 +1048,44 @@ void dbg_edge_rdm(int ptype, int nitems, const int* du, const int* dv, const int
                   const double* scale_u, const double* scale_v, void* out, int guard) {
     dbg_edge_rdm_mixed(ptype, ptype, nitems, du, dv, chi, nchunks_u, nchunks_v, partial_u, partial_v, scale_u, scale_v, out, guard);
 }
+// bond entanglement spectra (kernels_spectrum.hip), stages A-D over nitems bonds of different chi exactly as engine_spectra.cpp runs them (fill_bond_spec_items,
+// launch_bond_spectra_stages): m1 / m2 hold the items' chi x chi messages one after the other in the state's type, present[2 i], present[2 i + 1] = 0 hands the kernels a
+// null pointer for m1 / m2 (identity); the cutoff follows from the dtype.  out: chi[i] doubles per item between guard bands of `guard` doubles; flags_out: one int per item
+// (bit 1: a message eigenvalue <= -cutoff, bit 2: trace not positive and finite)
+void dbg_bond_spectrum(int dtype, int nitems, const int* chi, const void* m1, const void* m2, const int* present, double* out, int* flags_out, int guard) {
+    need_gpu();
+    post_check("dbg_bond_spectrum", dtype, nitems, chi, guard);
+    if (!m1 || !m2 || !present || !out || !flags_out) throw Err(TNQS_ERR_INVALID, "dbg_bond_spectrum: bad arguments");
+    const size_t esz = dtype == TNQS_C64 ? 8 : 16;
+    Slots s1, s2, sH, sV, sW, sV2; Guarded gO((size_t)guard * 8);
+    for (int i = 0; i < nitems; ++i) {
+        const size_t nn = (size_t)chi[i] * chi[i];
+        s1.add(nn * esz); s2.add(nn * esz); gO.add((size_t)chi[i] * 8);
+        for (Slots* s : {&sH, &sV, &sW, &sV2}) s->add(nn * 16);
+    }
+    for (Slots* s : {&s1, &s2, &sH, &sV, &sW, &sV2}) s->alloc();
+    gO.alloc();
+    put_all(s1, m1); put_all(s2, m2);
+    DBuf dTr(8 * (size_t)nitems), dFlag(sizeof(int) * (size_t)nitems);
+    HIPCHK(hipMemset(dFlag.p, 0, sizeof(int) * (size_t)nitems));
+    std::vector<BondSpecBufs> bufs(nitems);
+    for (int i = 0; i < nitems; ++i)
+        bufs[i] = BondSpecBufs{present[2 * i] ? s1.at(i) : nullptr, present[2 * i + 1] ? s2.at(i) : nullptr, sH.at(i), sV.at(i), sW.at(i), sV2.at(i),
+                               (double*)dTr.p + i, (double*)gO.at(i), chi[i], (int*)dFlag.p + i};
+    std::vector<EnvItem> ei; std::vector<JacobiItem> j1, j2; std::vector<BondSpecItem> items;
+    const BondSpecLaunch L = fill_bond_spec_items(bufs, bond_spectrum_cutoff(dtype), ei, j1, j2, items);
+    DBuf dE(sizeof(EnvItem) * nitems), dJ1(sizeof(JacobiItem) * nitems), dJ2(sizeof(JacobiItem) * nitems), dI(sizeof(BondSpecItem) * nitems);
+    for (Slots* s : {&s1, &s2, &sH, &sV, &sW, &sV2}) s->up();
+    gO.up(out);
+    dE.up(ei.data(), sizeof(EnvItem) * nitems); dJ1.up(j1.data(), sizeof(JacobiItem) * nitems); dJ2.up(j2.data(), sizeof(JacobiItem) * nitems);
+    dI.up(items.data(), sizeof(BondSpecItem) * nitems);
+    if (dtype == TNQS_C64) launch_bond_spectra_stages<float>(nullptr, (const EnvItem*)dE.p, (const JacobiItem*)dJ1.p, (const JacobiItem*)dJ2.p, (const BondSpecItem*)dI.p, L);
+    else launch_bond_spectra_stages<double>(nullptr, (const EnvItem*)dE.p, (const JacobiItem*)dJ1.p, (const JacobiItem*)dJ2.p, (const BondSpecItem*)dI.p, L);
+    HIPCHK(hipDeviceSynchronize());
+    for (Slots* s : {&sH, &sV, &sW, &sV2}) s->down("the bond-spectrum workspace");
+    gO.down(out, "out");
+    dFlag.down(flags_out, sizeof(int) * (size_t)nitems);
+}
 // path_apply_kernel<P, T> (kernels_rdm.hip), ONE launch over nitems (environment, transfer matrix) pairs set up as engine_paths.cpp sets them up: L_in holds the items'
 // nchunks_in[i] chunks of (d chi_a)^2 numbers of type P one after the other, T the items' chi_b^2 x chi_a^2 matrices of the state's type, scale one double per item (0: a
 // null pointer), L_out ksplit[i] chunks of (d chi_b)^2 complex128 per item between guard bands of `guard` elements; ksplit[i] = 0: as plan_path_apply chooses

@@ -14,6 +14,7 @@
 //   engine_rdm.cpp    two-site reduced density matrices of bonds (batched chains + Grams, one contraction kernel)
 //   engine_paths.cpp  two-site reduced density matrices of the ends of paths (environments, transfer matrices, the sweep along the path)
 //   engine_inner.cpp  overlap of two states: BP on the bilinear form (rectangular messages, mode products that change a leg's dimension, form scalars)
+//   engine_spectra.cpp  entanglement spectra of bonds from the two messages (batched eigen problems, one read-back)
 //   sharding.cpp      exchange step (RCCL or host callback)
 // and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
@@ -26,6 +27,7 @@
 //   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, antiprojector, trace
 //   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs), environment through a transfer matrix (path RDMs)
 //   kernels_inner.hip  overlap of two states: rectangular two-operand Gram (f32 / f64 matrix cores), bilinear message epilogue, form scalars
+//   kernels_spectrum.hip  bond entanglement spectra: W = D V^dagger m1^T V D from a message's eigen factorisation, signed sorted spectrum
 #pragma once
 #include "engine.hpp"
 #include "kernels.hpp"
@@ -394,6 +396,18 @@ char* ring_alloc(State* s, size_t bytes);
 void post_check(State* s, char* stage, const void* dsrc, size_t bytes, int kind, int cur_step, int iters_done, std::function<bool(State*)> eval);
 // drop every pending check unevaluated (the stream has been drained, a snapshot is about to be put back)
 void drop_checks(State* s);
+
+// ---- bond entanglement spectra (engine_spectra.cpp), shared with tnqs_dbg_bond_spectrum ----------------------------------------------------------------------------
+// the buffers of one request: m1, m2 in the state's type (null = identity); H, V, W, V2: n x n complex128 scratch; trace: one double; out: n doubles; flag: one int
+struct BondSpecBufs { const void* m1; const void* m2; void* H; void* V; void* W; void* V2; double* trace; double* out; int n; int* flag; };
+double bond_spectrum_cutoff(int dtype);                  // 10 eps of the state's real type (absolute)
+const char* bond_spectrum_flag_message(int flag);        // flag bit 1: message eigenvalue <= -cutoff; bit 2: trace not positive and finite
+// layout of a call's descriptor arrays: the first nfit items fit the LDS-resident f64 Jacobi with V (largest n: nmax_fit), the rest take the global-memory kernel (nmax_rest)
+struct BondSpecLaunch { int nitems, nfit, nmax_fit, nmax_rest; };
+BondSpecLaunch fill_bond_spec_items(std::vector<BondSpecBufs> b, double cutoff, std::vector<EnvItem>& ei, std::vector<JacobiItem>& j1, std::vector<JacobiItem>& j2,
+                                    std::vector<BondSpecItem>& items);
+template <class T> void launch_bond_spectra_stages(hipStream_t st, const EnvItem* d_env, const JacobiItem* d_j1, const JacobiItem* d_j2, const BondSpecItem* d_items,
+                                                   const BondSpecLaunch& L);
 
 // Executes a GateSchedule AHEAD of the device: a batch whose outcome is predictable and an update expected to converge in one sweep are enqueued without waiting
 // for their results, the state in front of every unverified step is remembered, and a step whose check fails is run again the careful way from that state.

@@ -192,6 +192,13 @@ struct SymGaugeItem { const void* AX; const void* VX; const void* AY; const void
                       void* Ce; void* Ce0; void* Vsvd; void* Xs; void* Xd; double* S; int n; double reg; int* flag; };
 template <class T> void launch_symg_build(hipStream_t s, const SymGaugeItem* d_items, int nitems);
 template <class T> void launch_symg_finish(hipStream_t s, const SymGaugeItem* d_items, int nitems);
+// entanglement spectrum of a bond (kernels_spectrum.hip; entanglement.jl:73-86), n = chi <= 256.  m1: the message u -> v in the state's type (null = identity); A, V: the
+// f64 Jacobi factorisation (A = H V, V) of the Hermitian part of the message v -> u.  bond_rho: D = f(Rayleigh quotients) (0 when |x| < cutoff, else sqrt(x);
+// x <= -cutoff: *flag |= 1), T1 = m1^T V (scratch; may be A's buffer), W = D V^dagger T1 D Hermitised, *trace = tr W, V2 = I.  After a Jacobi factorisation of W with V2
+// (W := W V2), bond_spectrum_finish: out[0 .. n) = the signed Rayleigh quotients of W over *trace, descending; a trace that is not positive and finite: *flag |= 2.
+struct BondSpecItem { const void* m1; const void* A; const void* V; void* T1; void* W; void* V2; double* trace; double* out; int n; double cutoff; int* flag; };
+template <class T> void launch_bond_rho(hipStream_t s, const BondSpecItem* d_items, int nitems);
+void launch_bond_spectrum_finish(hipStream_t s, const BondSpecItem* d_items, int nitems);
 // sharded gate batches: the (chi', status, truncerr | S | X2) record of a gate packed into its exchange slot, and the 32-byte
 // headers of all records gathered into one contiguous array (one launch each instead of three copies per gate)
 struct RecordPackItem { void* dst; const int* info; const double* terr; const double* S; int nS; const void* X2; long long x2_words; long long x2_off; };
