@@ -70,8 +70,9 @@ int tnqs_dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* 
 int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const int* both, const void* X, const void* Y, const void* M,
                            void* out_y, void* out_x, int spw);
 /* the tall route of the ComplexF32 theta SVD (Cholesky-QR preprocessing, Jacobi on R, A J, polishing sweeps where the pivot collapsed) on nitems matrices
- * A_i (m[i] x n[i], 2 <= n <= 128, n <= m <= 256): A_i <- U Sigma (columns); chol_fail[i]: a Cholesky pivot was refused; polished[i]: the polishing sweeps
- * ran on the item; sweeps[i]: sweeps of the Jacobi on R (each output array may be NULL) */
+ * A_i (m[i] x n[i], 2 <= n <= 128, n <= m <= 512): A_i <- U Sigma (columns); chol_fail[i]: a Cholesky pivot was refused; polished[i]: the polishing sweeps
+ * ran on the item; sweeps[i]: sweeps of the Jacobi on R (each output array may be NULL).  (m > 256 is where svd_batch sends a ComplexF32 theta of more than 256 rows whose
+ * n x n triangle fits the LDS, e.g. 260 x 12: the tall_* kernels walk the rows in blocks and hold up to the 512 rows of a theta; the polishing launch is then jacobi_kernel<float, 8>) */
 int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fail, int* polished, int* sweeps);
 /* the whole BP message of a small site (kernels_bp.hip bp_small_site_kernel<1024>): ONE launch over nitems (site, outgoing leg) pairs, sized by the largest item as
  * the engine sizes it.  Item i is a site tensor [d[i]][chi_0]..[chi_{z[i]-1}] (column-major) with the outgoing leg jo[i]; chi, present: the items' legs one after
@@ -210,6 +211,27 @@ int tnqs_dbg_gate_theta(int dtype, int nitems, const int* dims, const int* mode,
 int tnqs_dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in, const int* texp, const void* theta, const void* thetaV, const double* lam1, const double* lam2,
                          const int* idx1, const int* idx2, const void* GW1, const void* GW2, const int* maxdim, const double* cutoff, const int* normalize, const int* chi_cap,
                          double* S, int* info_out, double* truncerr, void* X1, void* X2, int guard);
+/* the SVD stage between the two (csrc/gate_svd.cpp launch_theta_svd_stage, the function TwoSiteBatch::svd_and_finish calls): the gates' JacobiItems, svd_batch (theta_svd_pre_kernel,
+ * jacobi_lds_kernel, jacobi_kernel, the tall route), then the recovery of V -- ONE call over nitems gates.  dyn = 0: the static regime, the kernels get the dimensions from the host
+ * and nothing is offered to theta_svd_pre_kernel; dyn = 1: the run-ahead regime, the kernels read `info` on the device, every launch is sized from the bounds and the ComplexF32 gates
+ * are offered to theta_svd_pre_kernel by the engine's rules -- refused with TNQS_ERR_UNSUPPORTED where a bound fails the engine's one_trip rule (theta within the LDS-resident
+ * Jacobi, at most 256 rows).  Per item: dims = (d1, d2, n1, n2) with the bounds n_s = d_s chi (n_s d_s > 512: TNQS_ERR_UNSUPPORTED); info: 8 ints, uploaded as given, of which
+ * (r1, r2) = info[0], [1] with 1 <= r_s <= n_s and info[7] = the columns of the low-rank factor alive on the device (0: none) are read -- the SVD runs on the m x ncol matrix with
+ * m = max(r1 d1, r2 d2), nfull = min(r1 d1, r2 d2), ncol = info[7] or nfull (a wide theta is stored as its adjoint); K: the columns the host expects of the low-rank route (0: none);
+ * has_q / Q: the gate has the orthonormal factor Q of theta = M Q^T -- Q holds, for the items with has_q only, n2 d2 K complex128 numbers each, the (r2 d2) x K matrix at their start;
+ * rank_bounds: the rank each site CAN have (two per item; times d_s they decide the offer of theta as it stands); cap: the bond dimension cap (0: none).  recover_form: 0 the engine's
+ * rule (ComplexF32: recover_v_mfma_kernel), 1 recover_v_kernel<T, 8>.  theta (in: the m x ncol matrix, out: U Sigma), theta0 (the m x nfull theta; comes back as it went) and
+ * thetaV (out: V, nfull x ncol) hold max(n1 d1, n2 d2) * min(n1 d1, n2 d2) numbers of T per item (thetaV: max(..)^2) -- sized from the BOUNDS, as the engine's workspaces are, the
+ * matrix at the start of its slot with the leading dimension m (thetaV: nfull) -- laid out as guard, item 0, guard, ..., guard; they go up as filled and come back whole.
+ * sweeps_out[i] (may be NULL): info[4] after the launches.  route_out[i] (may be NULL): which kernel factorises the item, decided on the host from the same item and predicates.
+ * theta == NULL: only route_out is filled (HOST ONLY) */
+#define TNQS_DBG_ROUTE_SVD_PRE_LOWRANK 10   /* theta_svd_pre_kernel<512> on the low-rank factor, V through Q */
+#define TNQS_DBG_ROUTE_SVD_PRE_THETA 11     /* theta_svd_pre_kernel<512> on theta itself */
+#define TNQS_DBG_ROUTE_SVD_LDS 12           /* jacobi_lds_kernel<T, RQ>, V recovered */
+#define TNQS_DBG_ROUTE_SVD_GLOBAL 13        /* jacobi_kernel<T, 4 / 8>, V recovered */
+#define TNQS_DBG_ROUTE_SVD_TALL 14          /* svd_tall (Cholesky-QR route, ComplexF32), V recovered */
+int tnqs_dbg_theta_svd_stage(int dtype, int dyn, int nitems, const int* dims, const int* info, const int* K, const int* has_q, const void* Q, const int* rank_bounds, const int* cap,
+                             int recover_form, void* theta, void* theta0, void* thetaV, int* sweeps_out, int* route_out, int guard);
 /* the second factorisation pass: qr2_rinv_kernel (stage 0: X1 = R1^+ only; GV, A2, V2, tau, GVout, GWout, rk may be NULL), then qr2_compose_kernel (stage 1: both, X1 formed on the
  * device).  Per item n x n complex128 matrices: first-pass GW, GV, lam (n doubles), idx (n ints), r; the eigen pair (A2 = G2 V2, V2) of the second Gram matrix; tau.  Outputs X1,
  * GVout, GWout (n x n complex128) and rk.  n > 256: TNQS_ERR_UNSUPPORTED */

@@ -254,6 +254,8 @@ namespace tnqs { void dbg_default_sequence(const Graph& g, std::vector<int>& src
                  void dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in, const int* texp, const void* theta, const void* thetaV, const double* lam1, const double* lam2,
                                       const int* idx1, const int* idx2, const void* GW1, const void* GW2, const int* maxdim, const double* cutoff, const int* normalize, const int* chi_cap,
                                       double* S, int* info_out, double* truncerr, void* X1, void* X2, int guard);
+                 void dbg_theta_svd_stage(int dtype, int dyn, int nitems, const int* dims, const int* info, const int* K, const int* has_q, const void* Q, const int* rank_bounds,
+                                          const int* cap, int recover_form, void* theta, void* theta0, void* thetaV, int* sweeps_out, int* route_out, int guard);
                  void dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,
                               void* X1, void* GVout, void* GWout, int* rk, int guard);
                  void dbg_small_svd(int dtype, int nitems, const int* shape, const void* src, void* GA, void* GV, int guard);
@@ -416,6 +418,10 @@ int tnqs_dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info
                          const int* idx1, const int* idx2, const void* GW1, const void* GW2, const int* maxdim, const double* cutoff, const int* normalize, const int* chi_cap,
                          double* S, int* info_out, double* truncerr, void* X1, void* X2, int guard_elems) {
     return guard([&] { dbg_gate_finish(dtype, nitems, dims, info_in, texp, theta, thetaV, lam1, lam2, idx1, idx2, GW1, GW2, maxdim, cutoff, normalize, chi_cap, S, info_out, truncerr, X1, X2, guard_elems); });
+}
+int tnqs_dbg_theta_svd_stage(int dtype, int dyn, int nitems, const int* dims, const int* info, const int* K, const int* has_q, const void* Q, const int* rank_bounds, const int* cap,
+                             int recover_form, void* theta, void* theta0, void* thetaV, int* sweeps_out, int* route_out, int guard_elems) {
+    return guard([&] { dbg_theta_svd_stage(dtype, dyn, nitems, dims, info, K, has_q, Q, rank_bounds, cap, recover_form, theta, theta0, thetaV, sweeps_out, route_out, guard_elems); });
 }
 int tnqs_dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,
                  void* X1, void* GVout, void* GWout, int* rk, int guard_elems) {

@@ -622,7 +622,7 @@ void dbg_svd_tall(int nitems, const int* m, const int* n, void* A, int* chol_fai
     need_gpu();
     if (nitems < 1 || !m || !n || !A) throw Err(TNQS_ERR_INVALID, "dbg_svd_tall: bad arguments");
     for (int i = 0; i < nitems; ++i)
-        if (n[i] < 2 || n[i] > 128 || m[i] < n[i] || m[i] > 256) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_svd_tall: 2 <= n <= 128, n <= m <= 256");
+        if (n[i] < 2 || n[i] > 128 || m[i] < n[i] || m[i] > 512) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_svd_tall: 2 <= n <= 128, n <= m <= 512");
     std::vector<size_t> off; cat_offsets(nitems, off, [&](int i) { return (size_t)m[i] * n[i]; });
     int dev = 0; HIPCHK(hipGetDevice(&dev));
     std::unique_ptr<State> s(state_create(1, 0, nullptr, nullptr, nullptr, TNQS_C64, dev));
@@ -1297,6 +1297,63 @@ void dbg_gate_finish(int dtype, int nitems, const int* dims, const int* info_in,
     gS.down(S, "S"); gX1.down(X1, "X1"); gX2.down(X2, "X2");
     dInfo.down(hinfo.data(), 32 * (size_t)nitems); dTerr.down(truncerr, 8 * (size_t)nitems);
     for (int i = 0; i < nitems; ++i) { info_out[2 * i] = hinfo[8 * i + 2]; info_out[2 * i + 1] = hinfo[8 * i + 3]; }
+}
+// TwoSiteBatch::svd_and_finish up to and including the recovery of V: launch_theta_svd_stage (gate_svd.cpp) once over nitems gates.  dims: (d1, d2, n1, n2) per item, the
+// bounds n_s = d_s chi every buffer and (dyn) every launch is sized from; info: the 8 ints per item the device holds (r1, r2, -, -, -, -, -, K alive), which are also the host
+// dims of the static regime.  theta == NULL: only route_out is filled (host only)
+void dbg_theta_svd_stage(int dtype, int dyn, int nitems, const int* dims, const int* info, const int* K, const int* has_q, const void* Q, const int* rank_bounds, const int* cap,
+                         int recover_form, void* theta, void* theta0, void* thetaV, int* sweeps_out, int* route_out, int guard) {
+    if ((dtype != TNQS_C64 && dtype != TNQS_C128) || dyn < 0 || dyn > 1 || nitems < 1 || !dims || !info || !K || !has_q || !rank_bounds || !cap || recover_form < 0 || recover_form > 1 ||
+        guard < 0 || (theta && (!theta0 || !thetaV))) throw Err(TNQS_ERR_INVALID, "dbg_theta_svd_stage: bad arguments");
+    static_assert(ThetaSvdPreLow == TNQS_DBG_ROUTE_SVD_PRE_LOWRANK && ThetaSvdPreTheta == TNQS_DBG_ROUTE_SVD_PRE_THETA && ThetaSvdLds == TNQS_DBG_ROUTE_SVD_LDS &&
+                  ThetaSvdGlobal == TNQS_DBG_ROUTE_SVD_GLOBAL && ThetaSvdTall == TNQS_DBG_ROUTE_SVD_TALL, "theta_svd_route returns the header's values");
+    const bool F32 = dtype == TNQS_C64; const size_t esz = F32 ? 8 : 16;
+    std::vector<ThetaSvdGate> sg(nitems); std::vector<int> MrB(nitems), NcB(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        const int d1 = dims[4 * i], d2 = dims[4 * i + 1], n1 = dims[4 * i + 2], n2 = dims[4 * i + 3]; const int* h = info + 8 * i;
+        if (d1 < 1 || d2 < 1 || n1 < 1 || n2 < 1) throw Err(TNQS_ERR_INVALID, "dbg_theta_svd_stage: d1, d2, n1, n2 >= 1");
+        if ((long long)n1 * d1 > 512 || (long long)n2 * d2 > 512) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_theta_svd_stage: d^2*chi > 512 is not supported by the theta SVD kernels");
+        MrB[i] = std::max(n1 * d1, n2 * d2); NcB[i] = std::min(n1 * d1, n2 * d2);
+        const int Mr = h[0] * d1, Nc = h[1] * d2;
+        if (h[0] < 1 || h[0] > n1 || h[1] < 1 || h[1] > n2) throw Err(TNQS_ERR_INVALID, "dbg_theta_svd_stage: 1 <= r <= n");
+        if (K[i] < 0 || K[i] > NcB[i] || cap[i] < 0 || rank_bounds[2 * i] < 1 || rank_bounds[2 * i + 1] < 1) throw Err(TNQS_ERR_INVALID, "dbg_theta_svd_stage: K, cap or rank bound out of range");
+        // a low-rank factor alive on the device: the one the host expected, of a theta that is not wide, with no more columns than its Q has rows
+        if (h[7] < 0 || (h[7] > 0 && (h[7] != K[i] || Mr < Nc || h[7] > Nc))) throw Err(TNQS_ERR_INVALID, "dbg_theta_svd_stage: inconsistent info[7]");
+        if (has_q[i] && (K[i] < 1 || n1 * d1 < n2 * d2 || (theta && !Q))) throw Err(TNQS_ERR_INVALID, "dbg_theta_svd_stage: Q needs K >= 1 and a theta whose bounds are not wide");
+        // the run-ahead regime: what theta_svd()'s one_trip asks of the bounds
+        if (dyn && !(jacobi_lds(jacobi_lds_bytes(MrB[i], NcB[i], false, esz)) > 0 && MrB[i] <= 256))
+            throw Err(TNQS_ERR_UNSUPPORTED, "dbg_theta_svd_stage: the run-ahead regime needs every theta within the LDS-resident Jacobi at its bounds");
+        sg[i] = ThetaSvdGate{nullptr, nullptr, nullptr, d1, d2, n1, n2, nullptr, K[i], nullptr, rank_bounds[2 * i] * d1, rank_bounds[2 * i + 1] * d2, cap[i]};
+    }
+    if (route_out) {
+        static int stand_in;      // (the route reads no pointer, only whether the gate has a Q)
+        for (int i = 0; i < nitems; ++i) { ThetaSvdGate g = sg[i]; if (has_q[i]) g.lowQ = &stand_in; route_out[i] = theta_svd_route(F32, g, dyn ? nullptr : info + 8 * i, info + 8 * i); }
+    }
+    if (!theta) return;
+    need_gpu();
+    int dev = 0; HIPCHK(hipGetDevice(&dev));
+    std::unique_ptr<State> s(state_create(1, 0, nullptr, nullptr, nullptr, dtype, dev));
+    {
+        Slots sQ; Guarded gTh(guard * esz), gTh0(guard * esz), gTv(guard * esz);
+        for (int i = 0; i < nitems; ++i) {
+            const size_t mx = (size_t)MrB[i];
+            gTh.add((size_t)MrB[i] * NcB[i] * esz); gTh0.add((size_t)MrB[i] * NcB[i] * esz); gTv.add(mx * mx * esz);
+            sQ.add(has_q[i] ? (size_t)NcB[i] * K[i] * 16 : 0);
+        }
+        sQ.alloc(); gTh.alloc(); gTh0.alloc(); gTv.alloc();
+        { const char* p = (const char*)Q; for (int i = 0; i < nitems; ++i) if (has_q[i]) { sQ.put(i, p); p += sQ.len[i]; } }
+        DBuf dInfo(32 * (size_t)nitems); up_ints(dInfo, info, 8 * (size_t)nitems);
+        for (int i = 0; i < nitems; ++i) {
+            sg[i].theta = gTh.at(i); sg[i].theta0 = gTh0.at(i); sg[i].thetaV = gTv.at(i); sg[i].info = (int*)dInfo.p + 8 * i;
+            sg[i].lowQ = has_q[i] ? sQ.at(i) : nullptr;
+        }
+        sQ.up(); gTh.up(theta); gTh0.up(theta0); gTv.up(thetaV);
+        const bool mfma = recover_form == 0 && F32 && use_mfma();      // 0: the engine's rule
+        if (F32) launch_theta_svd_stage<float>(s.get(), sg, dyn ? nullptr : info, mfma); else launch_theta_svd_stage<double>(s.get(), sg, dyn ? nullptr : info, mfma);
+        HIPCHK(hipStreamSynchronize(s->stream));
+        sQ.down("Q"); gTh.down(theta, "theta"); gTh0.down(theta0, "theta0"); gTv.down(thetaV, "thetaV");
+        if (sweeps_out) { std::vector<int> h(8 * (size_t)nitems); dInfo.down(h.data(), 32 * (size_t)nitems); for (int i = 0; i < nitems; ++i) sweeps_out[i] = h[8 * i + 4]; }
+    }
 }
 // qr2_rinv_kernel (stage 0: X1 only), then qr2_compose_kernel (stage 1), as second_pass() runs them.  n x n complex128 matrices per item
 void dbg_qr2(int stage, int nitems, const int* n, const void* GW, const void* GV, const double* lam, const int* idx, const int* r, const void* A2, const void* V2, const double* tau,

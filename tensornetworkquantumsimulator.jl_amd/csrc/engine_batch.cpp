@@ -200,20 +200,26 @@ void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail_out, in
 //     (kernels_chi64.hip; the rotations that orthogonalise R's columns orthogonalise A's, delta only conditions R), followed by
 //     polishing sweeps of the global-memory kernel on A J (relative orthogonality of the small columns);
 //   * anything else: the global-memory kernel.
+template <class T> SvdList svd_batch_list(const JacobiItem& j, bool with_v, size_t esz) {
+    const size_t cap = 160 * 1024 - 2048;
+    static const bool force_global = [] { const char* e = std::getenv("TNQS_JACOBI_GLOBAL"); return e && e[0] == '1'; }();
+    if (j.n < 1 || j.m < 1) return SvdList::none;
+    if (!force_global && jacobi_lds_bytes(j.m, j.n, with_v, esz) <= cap && std::max(j.m, j.n) <= 256) return SvdList::fit;
+    // (the tall_* kernels of kernels_chi64.hip walk the rows in blocks: any m up to the 512 rows of a theta -- 260 x 12 is tested)
+    if (!force_global && std::is_same<T, float>::value && !with_v && !j.V && use_mfma() && use_chi64() && j.m >= j.n && j.n <= 128 && j.n >= 2 &&
+        jacobi_lds_bytes(j.n, j.n, false, esz) <= cap) return SvdList::tall;
+    return SvdList::rest;
+}
 template <class T> void svd_batch(State* s, const std::vector<JacobiItem>& all, bool with_v) {
     const size_t esz = s->esz();
-    const size_t cap = 160 * 1024 - 2048;
     std::vector<JacobiItem> fit, tall, rest, pre;
-    static const bool force_global = [] { const char* e = std::getenv("TNQS_JACOBI_GLOBAL"); return e && e[0] == '1'; }();
     for (auto& j : all) {
-        if (j.n < 1 || j.m < 1) continue;
+        const SvdList l = svd_batch_list<T>(j, with_v, esz);
+        if (l == SvdList::none) continue;
         // a low-rank theta the caller offers to the preconditioned kernel (JacobiItem::pre): that kernel takes it when the dimensions found on the device
         // fit; the item stays in the lists below as well, whose kernels skip it in that case
         if (j.pre) pre.push_back(j);
-        if (!force_global && jacobi_lds_bytes(j.m, j.n, with_v, esz) <= cap && std::max(j.m, j.n) <= 256) fit.push_back(j);
-        else if (!force_global && std::is_same<T, float>::value && !with_v && !j.V && use_mfma() && use_chi64() && j.m >= j.n && j.n <= 128 && j.n >= 2 &&
-                 jacobi_lds_bytes(j.n, j.n, false, esz) <= cap) tall.push_back(j);
-        else rest.push_back(j);
+        (l == SvdList::fit ? fit : l == SvdList::tall ? tall : rest).push_back(j);
     }
     if (!pre.empty()) {
         const JacobiItem* d = upload_small(s, pre);
@@ -282,6 +288,8 @@ template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& job
 
 template void run_chains<float>(State*, std::vector<Chain>&, int, int);
 template void run_chains<double>(State*, std::vector<Chain>&, int, int);
+template SvdList svd_batch_list<float>(const JacobiItem&, bool, size_t);
+template SvdList svd_batch_list<double>(const JacobiItem&, bool, size_t);
 template void svd_batch<float>(State*, const std::vector<JacobiItem>&, bool);
 template void svd_batch<double>(State*, const std::vector<JacobiItem>&, bool);
 template void run_grams<float, float>(State*, std::vector<GramJob>&, int);

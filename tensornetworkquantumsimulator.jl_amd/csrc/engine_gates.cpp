@@ -626,38 +626,14 @@ template <class T> struct TwoSiteBatch {
     // read back from the device, or null: the kernels read them from the gates' info arrays themselves (JacobiItem::dyn) and the
     // host sizes the launches with upper bounds
     void svd_and_finish(const int* dims) {
-        std::vector<JacobiItem> ji; std::vector<int> ncfull;
+        std::vector<ThetaSvdGate> sg;
+        auto rub = [&](size_t i) { const int n = nof(i); return (int)std::min<size_t>((size_t)n, sj[i].sd.n / (size_t)n); };      // the rank a site CAN have (fewer fibers than columns: a corner)
         for (int q = 0; q < npg; ++q) {
-            int gi = pg[q];
-            JacobiItem j{};
-            if (dims) {
-                int Mr, Nc, ncolJ; theta_dims(dims + 8 * q, gitems[q].d1, gitems[q].d2, Mr, Nc, ncolJ);
-                j = JacobiItem{ws[gi].theta->p, ws[gi].thetaV->p, Mr, ncolJ, gitems[q].info + 4};
-                ncfull.push_back(Nc);
-            } else {
-                const int Mr = std::max(ws[gi].n1 * gitems[q].d1, ws[gi].n2 * gitems[q].d2), Nc = std::min(ws[gi].n1 * gitems[q].d1, ws[gi].n2 * gitems[q].d2);
-                j = JacobiItem{ws[gi].theta->p, ws[gi].thetaV->p, Mr, Nc, gitems[q].info + 4, gitems[q].info, gitems[q].d1, gitems[q].d2,
-                               gitems[q].lowG ? gitems[q].kappa * gitems[q].chi : 0};      // low-rank route expected: K columns
-                // offered to theta_svd_pre_kernel, which decides on the device: the low-rank factor with its Q (2), or theta as it stands when the ranks the
-                // sites CAN have (a site with fewer fibers than columns: a corner) keep it within 128 x 64 (1) -- those gates took 12-13 plain sweeps on 128 rows
-                // and were what a colour batch of a small lattice waited for
-                if (F32 && use_precond_svd()) {
-                    auto rub = [&](size_t i) { const int n = nof(i); return (int)std::min<size_t>((size_t)n, sj[i].sd.n / (size_t)n); };
-                    const int a1 = rub(2 * (size_t)gi) * gitems[q].d1, a2 = rub(2 * (size_t)gi + 1) * gitems[q].d2;
-                    if (gitems[q].lowQ) { j.QB = gitems[q].lowQ; j.Vout = ws[gi].thetaV->p; j.pre = 2; }
-                    else if (theta_svd_pre_covers(std::max(a1, a2), std::min(a1, a2))) { j.Vout = ws[gi].thetaV->p; j.pre = 1; }
-                    j.cap = ws[gi].cap;
-                }
-                ncfull.push_back(Nc);
-            }
-            j.V = nullptr;          // V is never accumulated from the rotations: recovered below
-            ji.push_back(j);
+            const int gi = pg[q]; const GateItem& it = gitems[q];
+            sg.push_back(ThetaSvdGate{ws[gi].theta->p, ws[gi].theta0->p, ws[gi].thetaV->p, it.d1, it.d2, ws[gi].n1, ws[gi].n2, it.info, it.lowG ? it.kappa * it.chi : 0, it.lowQ,
+                                      rub(2 * (size_t)gi) * it.d1, rub(2 * (size_t)gi + 1) * it.d2, ws[gi].cap});
         }
-        { ProfScope ps(s, TNQS_PROF_JACOBI, 0, 0); svd_batch<T>(s, ji, false); }
-        std::vector<RecoverItem> rv;
-        for (int q = 0; q < npg; ++q) rv.push_back(RecoverItem{ws[pg[q]].theta0->p, ws[pg[q]].theta->p, ws[pg[q]].thetaV->p, ji[q].m, ncfull[q], ji[q].n, ji[q].dyn, ji[q].dm, ji[q].dn, ji[q].pre});
-        const RecoverItem* dr = upload_small(s, rv);
-        { ProfScope ps(s, TNQS_PROF_JACOBI, 0, 0); { int nmax = 1; for (int nc : ncfull) nmax = std::max(nmax, nc); if (F32 && use_mfma()) launch_recover_v_mfma(s->stream, dr, npg, nmax); else launch_recover_v<T>(s->stream, dr, npg, nmax); } }
+        launch_theta_svd_stage<T>(s, sg, dims, F32 && use_mfma());      // gate_svd.cpp
         { ProfScope ps(s, TNQS_PROF_SMALL, 0, 0); launch_gate_finish<T>(s->stream, d_gitems, npg); }
     }
 

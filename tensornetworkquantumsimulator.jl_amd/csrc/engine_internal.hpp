@@ -358,6 +358,22 @@ struct TransferVertex { int v, ja, jb, ca, cb; SD sd; Buf phi, psi, T; };
 template <class T> void build_transfer_matrices(State* s, const std::vector<TransferVertex*>& lvs, const char* who);
 template <class T> void svd_batch(State* s, const std::vector<JacobiItem>& all, bool with_v);
 void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail = nullptr, int* d_polish_sweeps = nullptr);     // svd_batch's Cholesky-QR route (ComplexF32, no V)
+// the launch of svd_batch an item is put into, decided from the sizes the host knows (upper bounds where JacobiItem::dyn is set); none: an empty matrix
+enum class SvdList { none, fit, tall, rest };      // LDS-resident Jacobi, Cholesky-QR route (svd_tall), global-memory Jacobi
+template <class T> SvdList svd_batch_list(const JacobiItem& j, bool with_v, size_t esz);
+// ---- the SVD stage of a two-site gate (gate_svd.cpp): TwoSiteBatch::svd_and_finish (engine_gates.cpp) and dbg_theta_svd_stage (debug.cpp) run the same code --------
+// One gate: theta (in: the matrix the SVD runs on, out: U Sigma), theta0 (the unrotated full theta), thetaV (out: V), all on the device; the bounds n_s = d_s chi; the
+// device info array (GateItem::info; info[4] receives the sweep count); K = the columns of the low-rank factor the host expects (kappa chi, 0: no low-rank route); lowQ =
+// the orthonormal factor Q of that route (null: none); a1, a2 = (rank a site CAN have) * d of the two sites, behind the pre = 1 offer; cap = the bond dimension cap
+struct ThetaSvdGate { void* theta; const void* theta0; void* thetaV; int d1, d2, n1, n2; int* info; int K; const void* lowQ; int a1, a2, cap; };
+// svd_batch over the gates' items, then the recovery of V (recover_mfma: recover_v_mfma_kernel, else recover_v_kernel<T, 8>).  dims = the gates' info arrays on the host
+// (8 ints per gate), or null: the kernels read them on the device (JacobiItem::dyn), the launches are sized from the bounds and the ComplexF32 gates are offered to
+// theta_svd_pre_kernel by the rules above (K, lowQ, a1, a2 and cap are read in that case only)
+template <class T> void launch_theta_svd_stage(State* s, const std::vector<ThetaSvdGate>& gates, const int* dims, bool recover_mfma);
+// which kernel factorises the gate, from the same item and the same predicates on the host -- info: the 8 ints the device holds (dims where dims is given).  The values
+// of TNQS_DBG_ROUTE_SVD_* (include/tnqs_debug.h)
+enum { ThetaSvdNone = 0, ThetaSvdPreLow = 10, ThetaSvdPreTheta = 11, ThetaSvdLds = 12, ThetaSvdGlobal = 13, ThetaSvdTall = 14 };
+int theta_svd_route(bool F32, const ThetaSvdGate& g, const int* dims, const int* info);
 // optimistic: (apply_gates, a tolerance given) return after ENQUEUING the first sweep with its verdict left as a Check (engine.hpp); iters_before: sweeps this
 // update has already run (the continuation after a verdict turned out negative)
 template <class T> void bp_update_t(State* s, const tnqs_bp_opts* o, int* niter_out, double* diff_out, bool optimistic = false, int iters_before = 0);
