@@ -7,7 +7,7 @@ OUT=../libtnqs_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result ${EXTRA_FLAGS:-}"
 mkdir -p build
 # an object is stale when its source, any header here or the C ABI header is newer than it
-stale() { local d; [ -f "$2" ] || return 0; for d in "$1" *.hpp ../../include/tnqs.h; do [ "$d" -nt "$2" ] && return 0; done; return 1; }
+stale() { local d; [ -f "$2" ] || return 0; for d in "$1" *.hpp ../../include/tnqs.h ../../include/tnqs_debug.h; do [ "$d" -nt "$2" ] && return 0; done; return 1; }
 objs=(); pids=()
 for f in *.hip *.cpp; do
   o=build/${f%.*}.o; objs+=("$o")

@@ -194,7 +194,7 @@ static std::vector<Gate2> absorb_pending(const State* s, const std::vector<Gate2
 
 // the gate as an operator sum g = sum_k a_k (x) b_k: O[(s1',s1),(s2',s2)] = g[(s1' s2'),(s1 s2)] factorised by elimination with complete pivoting
 // (exact rank factorisation).  Returns kappa, the operator Schmidt rank (2 for Rzz / Rxx / CNOT / CPHASE, 4 for SWAP); fa gets the kappa columns a_k
-// (d1^2 each), fb the kappa rows b_k (d2^2 each).  (Declared in engine_internal.hpp: debug.cpp dbg_gate_theta / dbg_operator_sum call it too.)
+// (d1^2 each), fb the kappa rows b_k (d2^2 each).  (Declared in engine_internal.hpp: debug_gate.cpp tnqs_dbg_gate_theta / tnqs_dbg_operator_sum call it too.)
 int operator_sum(const double* mat, int d1, int d2, std::vector<std::complex<double>>& fa, std::vector<std::complex<double>>& fb) {
     const int dd = d1 * d2, na = d1 * d1, nb = d2 * d2;
     std::vector<std::complex<double>> O((size_t)na * nb);

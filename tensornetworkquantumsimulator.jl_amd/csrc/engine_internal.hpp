@@ -16,6 +16,8 @@
 //   engine_inner.cpp  overlap of two states: BP on the bilinear form (rectangular messages, mode products that change a leg's dimension, form scalars)
 //   engine_spectra.cpp  entanglement spectra of bonds from the two messages (batched eigen problems, one read-back)
 //   sharding.cpp      exchange step (RCCL or host callback)
+//   api.cpp           the extern "C" boundary of include/tnqs.h (api_guard.hpp: the exception guard every entry point runs in)
+//   debug_*.cpp       the kernel-level test entry points of include/tnqs_debug.h, one file per kernel family: svd, fiber, plane, bp, gate, obs, sample (debug_util.hpp)
 // and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
 //   kernels_bp.hip     message epilogue, small-site message, rescale,    kernels_x3.hip     the same on the bf16 matrix cores (three-way split)
@@ -77,7 +79,7 @@ TNQS_SWITCH(speculation_on, !envflag("TNQS_NO_SPECULATION"))     // apply_gates 
 // TNQS_JACOBI_GLOBAL=1: every Jacobi factorisation in the global-memory kernel (the route matrices beyond the LDS take);
 // tunables: TNQS_ARENA_KB (pinned staging arena; tests of its overflow path), TNQS_BP_WS_MB (workspace bound of a BP sub-batch), TNQS_BP_CACHE_MB, TNQS_RCCL_LIB (sharding.cpp),
 //           TNQS_FORCE_EXCHANGE (a one-rank RCCL handle takes the sharded path); diagnostics: TNQS_HOST_TIMING, TNQS_DEBUG_SWEEPS.
-// The kernel-level entry points of include/tnqs_debug.h (debug.cpp) read TNQS_DBG_* themselves and are not part of the hot path.
+// The kernel-level entry points of include/tnqs_debug.h (debug_*.cpp) read TNQS_DBG_* themselves and are not part of the hot path.
 // TNQS_BP_CACHE_MB: bound on the partial products kept across BP levels (MiB, default 49152)
 inline size_t bp_cache_budget() { static const size_t v = [] { const char* e = std::getenv("TNQS_BP_CACHE_MB"); return (e ? (size_t)std::atoll(e) : (size_t)49152) << 20; }(); return v; }
 inline size_t bp_ws_budget() { static const size_t v = [] { const char* e = std::getenv("TNQS_BP_WS_MB"); return (e ? (size_t)std::atoll(e) : (size_t)24576) << 20; }(); return v; }
@@ -257,8 +259,13 @@ inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 int operator_sum(const double* mat, int d1, int d2, std::vector<std::complex<double>>& fa, std::vector<std::complex<double>>& fb);
 void exchange(State* s, size_t bytes_per_rank);                       // sharding.cpp
 void check_exchange(const State* s, size_t bytes_per_rank);           // call BEFORE enqueuing anything that writes into s->exch
+// host-only helpers of the kernel-level entry points (debug_bp.cpp, debug_gate.cpp): the default BP order as (src, dst) vertex pairs, with the level of every message
+// (bp_schedule.cpp), and the graph of a handle without the handle (engine_core.cpp)
+void dbg_default_sequence(const Graph& g, std::vector<int>& src, std::vector<int>& dst);
+void dbg_default_sequence_graph(const Graph& g, std::vector<int>& src, std::vector<int>& dst, std::vector<int>& level);
+std::shared_ptr<Graph> dbg_make_graph(int nv, int ne, const int32_t* es, const int32_t* ed);
 
-// ---- the theta phase of a two-site gate (gate_theta.cpp): TwoSiteBatch (engine_gates.cpp) and the kernel-level entry points (debug.cpp) run the same code --------
+// ---- the theta phase of a two-site gate (gate_theta.cpp): TwoSiteBatch (engine_gates.cpp) and the kernel-level entry points (debug_gate.cpp) run the same code --------
 // What a gate of operator-Schmidt rank kappa (0: no operator-sum factors) on a bond of dimension chi is offered, and the element counts (complex128) of its low-rank
 // workspaces, 0 where one is not handed out: nA = lowA (Mr K), nB = lowB (Nc K); low-rank route: nG = lowG, lowL, lowW each (K K); its preconditioned SVD (ComplexF32):
 // nQ = lowQ (Nc K); its second CholeskyQR pass (ComplexF64): nB1 = lowB1 (Nc K), nG2 = lowG2, lowL2, lowLc each (K K).  Host code, no device call; d^2 chi > 512 throws
@@ -361,7 +368,7 @@ void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail = nullp
 // the launch of svd_batch an item is put into, decided from the sizes the host knows (upper bounds where JacobiItem::dyn is set); none: an empty matrix
 enum class SvdList { none, fit, tall, rest };      // LDS-resident Jacobi, Cholesky-QR route (svd_tall), global-memory Jacobi
 template <class T> SvdList svd_batch_list(const JacobiItem& j, bool with_v, size_t esz);
-// ---- the SVD stage of a two-site gate (gate_svd.cpp): TwoSiteBatch::svd_and_finish (engine_gates.cpp) and dbg_theta_svd_stage (debug.cpp) run the same code --------
+// ---- the SVD stage of a two-site gate (gate_svd.cpp): TwoSiteBatch::svd_and_finish (engine_gates.cpp) and tnqs_dbg_theta_svd_stage (debug_gate.cpp) run the same code --------
 // One gate: theta (in: the matrix the SVD runs on, out: U Sigma), theta0 (the unrotated full theta), thetaV (out: V), all on the device; the bounds n_s = d_s chi; the
 // device info array (GateItem::info; info[4] receives the sweep count); K = the columns of the low-rank factor the host expects (kappa chi, 0: no low-rank route); lowQ =
 // the orthonormal factor Q of that route (null: none); a1, a2 = (rank a site CAN have) * d of the two sites, behind the pre = 1 offer; cap = the bond dimension cap

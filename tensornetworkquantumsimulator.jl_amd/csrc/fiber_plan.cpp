@@ -1,7 +1,7 @@
 // fiber_plan.cpp -- which fiber GEMM kernel a pass launches (host code, no device call): the one place that decides between the generic tiled kernel, the f32
 // matrix-core tiles, the register-direct kernels and the f64 matrix cores, and lays the items out for the kernel chosen.  The per-kernel layout functions
 // (plan_fiber_gemm, plan_rowgemm, plan_fiber_gemm_f64) stay next to their kernels; the engine's runner (engine_batch.cpp FiberPass) and the debug entry points
-// (debug.cpp) launch what this returns through launch_fiber_route.
+// (debug_fiber.cpp) launch what this returns through launch_fiber_route.
 //
 //   route    taken when                                                                        kernel
 //   RowGemm  f32, use_mfma, rowgemm_covers(item), D == rg_D, K == 32 or (K == 64 and           mfma_rowgemm_kernel<KB, NB, D> / x3_rowgemm64_kernel

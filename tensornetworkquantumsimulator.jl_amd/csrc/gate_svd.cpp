@@ -1,5 +1,5 @@
 // gate_svd.cpp -- the SVD stage of a two-site gate batch (simple_update.jl:53-59): the JacobiItem of every gate, svd_batch, and the recovery of V from the unrotated
-// theta.  engine_gates.cpp (TwoSiteBatch::svd_and_finish) and the kernel-level entry point of debug.cpp (dbg_theta_svd_stage) both run THIS code.
+// theta.  engine_gates.cpp (TwoSiteBatch::svd_and_finish) and the kernel-level entry point of debug_gate.cpp (tnqs_dbg_theta_svd_stage) both run THIS code.
 #include "engine_internal.hpp"
 
 namespace tnqs {

@@ -1,6 +1,6 @@
 // gate_theta.cpp -- the theta phase of a two-site gate batch (simple_update.jl:51-59): which route a gate is offered and what it is given to work in (theta_route;
 // host code, no device call), the launch chain from the Gram factors to the scaled theta (launch_theta_chain), and the item fills / launch sequences of the small-SVD
-// route and of the second factorisation pass.  engine_gates.cpp (TwoSiteBatch) and the kernel-level entry points of debug.cpp both run THIS code.
+// route and of the second factorisation pass.  engine_gates.cpp (TwoSiteBatch) and the kernel-level entry points of debug_gate.cpp both run THIS code.
 #include "engine_internal.hpp"
 
 namespace tnqs {

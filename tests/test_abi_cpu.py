@@ -46,6 +46,53 @@ def test_library_exports_every_declared_debug_symbol():
         assert hasattr(lib, name), f"{name} declared in include/tnqs_debug.h but not exported"
 
 
+def declared_debug_symbols():
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tnqs_debug.h")).read(), flags=re.S)
+    return set(re.findall(r"\b(tnqs_dbg_[a-z0-9_]+)\s*\(", src))
+
+
+def test_library_exports_nothing_but_the_declared_symbols():
+    """the other direction: every tnqs_* function the library defines is declared in include/tnqs.h or include/tnqs_debug.h, so a leftover or misspelt definition of
+    an entry point (each is defined in one place, checked against its header by the compiler) does not go unnoticed"""
+    import subprocess
+    import tnqs_amd as tn
+    out = subprocess.run(["nm", "-D", "--defined-only", tn.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (tnqs_\w+)$", out, flags=re.M))
+    decl = declared_symbols() | declared_debug_symbols()
+    assert len(exported) >= 100
+    assert exported == decl, (sorted(exported - decl), sorted(decl - exported))
+
+
+def test_one_error_string_for_every_translation_unit():
+    """the entry points of include/tnqs.h and include/tnqs_debug.h are defined in different source files and share ONE thread-local error string: tnqs_last_error()
+    returns the message of the call that failed last on this thread, whichever file defines it"""
+    import ctypes
+    import tnqs_amd as tn
+    lib = ctypes.CDLL(tn.LIB_PATH)
+    lib.tnqs_last_error.restype = ctypes.c_char_p
+    INVALID, HIP = -1, -3      # TNQS_ERR_INVALID, TNQS_ERR_HIP (include/tnqs.h)
+    shape = (ctypes.c_int * 6)(2, 4, 4, 4, 2, 4)
+    nlaunches = ctypes.c_int(-7)
+    rc = lib.tnqs_dbg_fiber_plan(3, 0, 1, 1, 1, shape, None, 0, ctypes.byref(nlaunches), None)      # use = 3: a host-only debug entry with a bad argument
+    assert rc == INVALID and nlaunches.value == -7
+    assert lib.tnqs_last_error() == b"tnqs_dbg_fiber_plan: bad arguments"
+    dtype = ctypes.c_int(-7)
+    rc = lib.tnqs_scalartype(None, ctypes.byref(dtype))      # an entry of include/tnqs.h replaces the message
+    assert rc == INVALID and dtype.value == -7
+    assert lib.tnqs_last_error() == b"null handle"
+    count = ctypes.c_int(0)
+    assert lib.tnqs_device_count(ctypes.byref(count)) == 0
+    assert lib.tnqs_last_error() == b"null handle"      # a call that succeeds leaves it alone
+    if count.value == 0:      # a device entry without a device: the refusal comes from the debug layer's own check
+        chi = (ctypes.c_int * 1)(2)
+        S = (ctypes.c_double * 2)(1.0, 2.0)
+        out = (ctypes.c_float * 8)()
+        rc = lib.tnqs_dbg_diag(0, 1, chi, S, out, 0)
+        assert rc == HIP
+        assert b"no HIP device available" in lib.tnqs_last_error()
+        assert not any(out)
+
+
 def test_no_cpu_fallback():
     import torch
     import tnqs_amd as tn
