@@ -290,6 +290,35 @@ int tnqs_dbg_norm_factor(int nitems, const int* npart, const double* partials, d
 int tnqs_dbg_scale(int dtype, int nitems, const int* len, const void* src, const double* factor, void* dst, int guard);
 /* tnqs_inner_bp with the bound on a batch's chain workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of messages it ran */
 int tnqs_dbg_inner_bp_ws(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, int64_t workspace_bytes, int* nbatches_out);
+/* ---- the ComplexF64 kernels of csrc/kernels_f64.hip as the engine launches them: ONE launch over items of different sizes.  The items' arrays are passed one after
+ * the other; on the device every sub-array starts at a multiple of 256 bytes; each output with a `guard` is laid out as guard, item 0, guard, ..., guard (elements of
+ * its own type), goes up as the caller filled it and comes back whole.  Nothing is refused for its shape: a launch the matrix-core kernel does not take runs on the
+ * generic vector kernel, as in the engine, and *route_out says so */
+#define TNQS_DBG_ROUTE_FIBER_GENERIC 15      /* fiber_gemm_kernel<double, 8> (generic vector kernel) */
+#define TNQS_DBG_ROUTE_FIBER_F64_PLAIN 16    /* mfma_fiber_gemm_f64_kernel<NBLK, KS, false>: D = Do = 1, no norm partials */
+#define TNQS_DBG_ROUTE_FIBER_F64_GENERAL 17  /* mfma_fiber_gemm_f64_kernel<NBLK, KS, true> */
+#define TNQS_DBG_ROUTE_GRAM_GENERIC 18       /* gram_kernel<double, double, 4> (generic vector kernel) */
+#define TNQS_DBG_ROUTE_GRAM_F64IN 19         /* mfma_gram_f64in_kernel */
+/* ONE ComplexF64 fiber pass planned by plan_fiber_pass(items, nitems, fiber_rules(use, f32 = false, use_mfma, true), 16) and launched through launch_fiber_route<double>,
+ * as FiberPass::launch<double> launches it.  use: 0 single-leg stage of a mode-product chain (every item needs D = Do = 1 and want_norm = 0, as the engine's have), 1 gate
+ * epilogue.  shape: (D, PA, K, PB, Do, No) per item, item i as in tnqs_dbg_rowgemm: in_i (D K) x fibers, X_i (D K) x (Do No), out_i (Do No) x fibers, complex128.
+ * tpw > 0 sets the tiles per workgroup of the f64 kernel (FiberRules::f64_tpw), tpw <= 0 takes the rule's value.  partials: guard doubles, one double per workgroup of
+ * the launch, guard doubles; item i's norm is the sum of its slots wg_begin_out[i] .. wg_begin_out[i] + nwg_out[i] - 1, written only where want_norm[i] != 0 (the chain
+ * launch is handed the array as well, so that a write shows).  inst_out: (NBLK, KS, GEN) of the instantiation launched, zeros on the generic route.  route_out, inst_out,
+ * wg_begin_out, nwg_out may be NULL.  in == NULL: only these four are filled (HOST ONLY, no device is touched) */
+int tnqs_dbg_fiber_pass_c128(int use, int use_mfma, int nitems, const int* shape, const int* want_norm, const void* in, const void* X, void* out, double* partials, int tpw,
+                             int guard, int* route_out, int* inst_out, int* wg_begin_out, int* nwg_out);
+/* ONE ComplexF64 Gram launch (launch_gram_route<double, double>) followed by launch_reduce<double, double> over all items; route (gram_route), tiles and chunks set up as
+ * run_grams<double, double> sets them up.  shape: (D, PA, K, PB) per item; same[i] != 0: Y_i = X_i with the same device pointer (the item's slot in Y is not read; Y may be
+ * NULL when every item is `same`).  out_i[p + KK q] = sum_{(a,b)} X_i[p,(a,b)] conj(Y_i[q,(a,b)]), KK = D K, complex128, guarded.  The partials are guarded on the device as
+ * well; a touched guard there is an error return.  max_chunks <= 0: the engine's chunking, else at most that many chunks per item; nchunks_out[i] (may be NULL): the chunks
+ * item i was summed from.  route_out (may be NULL): TNQS_DBG_ROUTE_GRAM_F64IN or TNQS_DBG_ROUTE_GRAM_GENERIC.  X == NULL: only route_out and nchunks_out are filled (HOST ONLY) */
+int tnqs_dbg_gram_c128(int use_mfma, int nitems, const int* shape, const int* same, const void* X, const void* Y, void* out, int max_chunks, int* nchunks_out, int guard,
+                       int* route_out);
+/* the Gram route rule itself (csrc/kernels.hip gram_route, the function run_grams, tnqs_dbg_gram and tnqs_dbg_gram_c128 ask), from values alone: dtype 0 c64, 1 c128; acc64:
+ * accumulation in double; has_m: the jobs carry a matrix to absorb; all_same: X == Y on every job; all_f64in: every job has 4 <= D K <= 64 and carries no matrix; the two
+ * switches.  *route_out: 0 generic, 1 Mfma32, 2 Mfma64, 3 Fused32, 4 F64x64, 5 F64x128, 6 F64In, 7 Gauge64, 8 Gauge32 (the order of GramRoute).  HOST ONLY */
+int tnqs_dbg_gram_route(int dtype, int acc64, int has_m, int all_same, int all_f64in, int kkmax, int use_mfma, int use_chi64, int* route_out);
 #ifdef __cplusplus
 }
 #endif

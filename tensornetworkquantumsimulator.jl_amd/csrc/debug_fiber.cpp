@@ -57,10 +57,12 @@ extern "C" int tnqs_dbg_gram(int dtype, int D, int PA, int K, int PB, const void
         DBuf dX(nin * esz), dY(same ? 1 : nin * esz); DevItems<GramItem> dI(1); DevItems<ReduceItem> dR(1);
         dX.up(X, nin * esz); if (!same) dY.up(Y, nin * esz);
         GramItem it{}; it.X = dX.p; it.Y = same ? dX.p : dY.p; it.D = D; it.PA = PA; it.K = K; it.PB = PB;
-        const bool mf = use_mfma && dtype == TNQS_C64 && !acc64 && KK <= 32;
-        const bool mf64 = use_mfma && dtype == TNQS_C64 && acc64 && same && KK <= 64 && KK >= 16;
-        const bool mfz = use_mfma && dtype == TNQS_C128 && gram_f64in_covers(D, K);           // kernels_f64.hip
-        const GramRoute r = mfz ? GramRoute::F64In : mf64 ? GramRoute::F64x64 : mf ? GramRoute::Mfma32 : GramRoute::Generic;
+        // the engine's rule (gram_route, kernels.hip) on this one item, except where the tests of this entry ask for a kernel the rule would not give it: with f32
+        // accumulation Mfma32 below the rule's floor of D K = 8 as well and the vector kernel for 32 < D K <= 64; the vector kernel for 64 < D K <= 128 with f64
+        // accumulation (Mfma64 and F64x128 have their own entry, tnqs_dbg_gram_mfma)
+        GramRoute r = gram_route(dtype == TNQS_C64, acc64 || dtype == TNQS_C128, false, same, gram_f64in_covers(D, K), (size_t)KK, use_mfma != 0, true);
+        if (use_mfma && dtype == TNQS_C64 && !acc64) r = KK <= 32 ? GramRoute::Mfma32 : GramRoute::Generic;
+        if (r == GramRoute::F64x128) r = GramRoute::Generic;
         const int TR = gram_tile_rows(r, KK, esz);
         tile_params(PA, PB, TR, it.TA, it.TB, it.nta, it.ntb);
         const char* e = std::getenv("TNQS_DBG_GRAM_CHUNKS");
@@ -222,5 +224,111 @@ extern "C" int tnqs_dbg_gram_mfma(int nitems, const int* shape, const void* X, c
         HIPCHK(hipDeviceSynchronize());
         dO.down(out, oo[nitems] * asz);
         if (route) *route = f64 ? (all128 ? TNQS_DBG_ROUTE_F64_SHARED : TNQS_DBG_ROUTE_F64) : (mfma_use_x3() ? TNQS_DBG_ROUTE_X3 : TNQS_DBG_ROUTE_F32);
+    });
+}
+
+// ---- the ComplexF64 kernels of kernels_f64.hip as the engine launches them: items of different sizes in ONE launch, nothing refused for its shape (a launch
+// the matrix-core kernel does not take runs on the generic vector kernel, as in the engine; *route says which) ----
+
+// ONE ComplexF64 fiber pass: planned by plan_fiber_pass under the engine's rules of the use (tpw > 0: f64_tpw forced), launched through launch_fiber_route<double>
+// as FiberPass::launch<double> does.  in == NULL: the plan alone (route, instantiation, workgroups per item), no device call
+extern "C" int tnqs_dbg_fiber_pass_c128(int use, int use_mfma, int nitems, const int* shape, const int* want_norm, const void* in, const void* X, void* out, double* partials,
+                                        int tpw, int guard_elems, int* route, int* inst, int* wg_begin, int* nwg) {
+    return guard([&] {
+        if (use < 0 || use > 1 || nitems < 1 || !shape || !want_norm || guard_elems < 0 || (in && (!X || !out || !partials))) throw Err(TNQS_ERR_INVALID, "dbg_fiber_pass_c128: bad arguments");
+        std::vector<FiberItem> items(nitems);
+        for (int i = 0; i < nitems; ++i) {
+            const int* q = shape + 6 * i; for (int k = 0; k < 6; ++k) if (q[k] < 1) throw Err(TNQS_ERR_INVALID, "dbg_fiber_pass_c128: bad shape");
+            if ((long long)q[0] * q[1] * q[2] * q[3] > INT_MAX / 16 || (long long)q[4] * q[1] * q[5] * q[3] > INT_MAX / 16 || (long long)q[0] * q[2] * q[4] * q[5] > INT_MAX / 16)
+                throw Err(TNQS_ERR_INVALID, "dbg_fiber_pass_c128: bad shape");
+            // a chain stage has no site index and no norm (site_fiber_item(sd, leg, false, chi, false)): the plain kernel ignores both
+            if (use == 0 && (q[0] != 1 || q[4] != 1 || want_norm[i])) throw Err(TNQS_ERR_INVALID, "dbg_fiber_pass_c128: a chain stage has D = Do = 1 and no norm");
+            FiberItem& it = items[i]; it = FiberItem{}; it.D = q[0]; it.PA = q[1]; it.K = q[2]; it.PB = q[3]; it.Do = q[4]; it.No = q[5]; it.want_norm = want_norm[i] ? 1 : 0;
+        }
+        FiberRules r = fiber_rules(use == 0 ? FiberUse::Chain : FiberUse::Epilogue, /*f32=*/false, use_mfma != 0, true); if (tpw > 0) r.f64_tpw = tpw;
+        const std::vector<FiberLaunch> plan = plan_fiber_pass(items.data(), nitems, r, 16);
+        if (plan.size() != 1 || (int)plan[0].items.size() != nitems || (plan[0].route != FiberRoute::F64 && plan[0].route != FiberRoute::Generic) || plan[0].wgs < 1)
+            throw Err(TNQS_ERR_HIP, "internal: dbg_fiber_pass_c128: a ComplexF64 pass is one launch");
+        const FiberLaunch& L = plan[0];
+        const bool f64 = L.route == FiberRoute::F64;
+        if (route) *route = !f64 ? TNQS_DBG_ROUTE_FIBER_GENERIC : L.general ? TNQS_DBG_ROUTE_FIBER_F64_GENERAL : TNQS_DBG_ROUTE_FIBER_F64_PLAIN;
+        if (inst) { int nb = 0, ks = 0; if (f64) fiber_gemm_f64_inst(L.KKmax, L.NNmax, &nb, &ks); inst[0] = nb; inst[1] = ks; inst[2] = f64 && L.general ? 1 : 0; }
+        for (int k = 0; k < nitems; ++k) { if (wg_begin) wg_begin[L.index[k]] = L.items[k].tile_begin; if (nwg) nwg[L.index[k]] = L.nwg[k]; }
+        if (!in) return;
+        need_gpu();
+        Slots sIn, sX; Guarded gO((size_t)guard_elems * 16), gP((size_t)guard_elems * 8);
+        for (const FiberItem& it : items) {
+            sIn.add((size_t)it.D * it.PA * it.K * it.PB * 16); sX.add((size_t)it.D * it.K * it.Do * it.No * 16); gO.add((size_t)it.Do * it.PA * it.No * it.PB * 16);
+        }
+        gP.add((size_t)L.wgs * 8);
+        alloc_all(sIn, sX, gO, gP); put_all(sIn, in); put_all(sX, X);
+        std::vector<FiberItem> li = L.items;
+        for (int k = 0; k < nitems; ++k) { const int i = L.index[k]; li[k].in = sIn.at(i); li[k].X = sX.at(i); li[k].out = gO.at(i); }
+        DevItems<FiberItem> dI(li);
+        up_all(sIn, sX); gO.up(out); gP.up(partials);
+        launch_fiber_route<double>(nullptr, L, dI.get(), (double*)gP.at(0));
+        HIPCHK(hipDeviceSynchronize());
+        gO.down(out, "out"); gP.down(partials, "the norm partials");
+    });
+}
+
+// ONE ComplexF64 Gram launch + the chunk sum, set up as run_grams<double, double> sets it up: route from gram_route, tiles from gram_tile_rows / tile_params, chunks
+// from plan_gram.  X == NULL: route and chunk counts alone, no device call
+extern "C" int tnqs_dbg_gram_c128(int use_mfma, int nitems, const int* shape, const int* same, const void* X, const void* Y, void* out, int max_chunks, int* nchunks_out,
+                                  int guard_elems, int* route) {
+    return guard([&] {
+        if (nitems < 1 || !shape || !same || guard_elems < 0 || (X && !out)) throw Err(TNQS_ERR_INVALID, "dbg_gram_c128: bad arguments");
+        std::vector<GramItem> items(nitems);
+        size_t KKmax = 1; bool all_same = true, f64in = true, all_full = true;
+        for (int i = 0; i < nitems; ++i) {
+            const int* q = shape + 4 * i;
+            if (q[0] < 1 || q[1] < 1 || q[2] < 1 || q[3] < 1 || (long long)q[0] * q[1] * q[2] * q[3] > INT_MAX / 16 || (long long)q[0] * q[2] > 4096) throw Err(TNQS_ERR_INVALID, "dbg_gram_c128: bad shape");
+            if (X && !same[i] && !Y) throw Err(TNQS_ERR_INVALID, "dbg_gram_c128: Y == NULL needs every item `same`");
+            GramItem& it = items[i]; it = GramItem{}; it.D = q[0]; it.PA = q[1]; it.K = q[2]; it.PB = q[3];
+            KKmax = std::max(KKmax, (size_t)q[0] * q[2]); all_same = all_same && same[i] != 0; f64in = f64in && gram_f64in_covers(q[0], q[2]); all_full = all_full && q[0] * q[2] == 64;
+        }
+        const GramRoute r = gram_route(/*f32=*/false, /*acc64=*/true, false, all_same, f64in, KKmax, use_mfma != 0, true);
+        if (r != GramRoute::F64In && r != GramRoute::Generic) throw Err(TNQS_ERR_HIP, "internal: dbg_gram_c128: route of a ComplexF64 Gram");
+        const int TR = gram_tile_rows(r, KKmax, 16);
+        for (GramItem& it : items) tile_params(it.PA, it.PB, TR, it.TA, it.TB, it.nta, it.ntb);
+        std::vector<int> npart(nitems);
+        const int chunks = plan_gram(items.data(), nitems, r, false, max_chunks, npart.data());
+        if (route) *route = r == GramRoute::F64In ? TNQS_DBG_ROUTE_GRAM_F64IN : TNQS_DBG_ROUTE_GRAM_GENERIC;
+        if (nchunks_out) std::copy(npart.begin(), npart.end(), nchunks_out);
+        if (!X) return;
+        need_gpu();
+        const size_t band = 256;                       // guard band behind every item's partials (and in front of the first), 0xff like the gaps
+        Slots sX, sY, sP(band); Guarded gO((size_t)guard_elems * 16);
+        for (int i = 0; i < nitems; ++i) {
+            const GramItem& it = items[i]; const size_t nin = (size_t)it.D * it.PA * it.K * it.PB, n2 = (size_t)it.D * it.K * it.D * it.K;
+            sX.add(nin * 16); sY.add(same[i] ? 0 : nin * 16); sP.add((size_t)npart[i] * n2 * 16); gO.add(n2 * 16);
+        }
+        alloc_all(sX, sY, sP, gO); put_all(sX, X);
+        std::vector<ReduceItem> ri(nitems); size_t yo = 0, eb = 0;
+        for (int i = 0; i < nitems; ++i) {
+            GramItem& it = items[i]; const size_t nin = (size_t)it.D * it.PA * it.K * it.PB; const int n2 = it.D * it.K * it.D * it.K;
+            if (!same[i]) sY.put(i, (const char*)Y + yo);
+            yo += nin * 16;
+            it.X = sX.at(i); it.Y = same[i] ? sX.at(i) : sY.at(i); it.partial = sP.at(i);
+            ri[i] = ReduceItem{sP.at(i), gO.at(i), n2, npart[i], 0, (int)eb}; eb += n2;
+        }
+        DevItems<GramItem> dI(items); DevItems<ReduceItem> dR(ri);
+        up_all(sX, sY, sP); gO.up(out);
+        launch_gram_route<double, double>(nullptr, r, dI.get(), nitems, chunks, TR, (int)KKmax, all_full);
+        launch_reduce<double, double>(nullptr, dR.get(), nitems, (int)eb);
+        HIPCHK(hipDeviceSynchronize());
+        sP.down("the Gram partials");
+        auto untouched = [&](size_t b0, size_t b1) { for (size_t b = b0; b < b1; ++b) if (sP.host[b] != (char)0xff) throw Err(TNQS_ERR_INVALID, "dbg: a kernel wrote outside an item of the Gram partials"); };
+        untouched(0, band);
+        for (int i = 0; i < nitems; ++i) untouched(sP.off[i] + sP.len[i], sP.off[i] + sP.len[i] + band);
+        gO.down(out, "out");
+    });
+}
+
+// HOST ONLY: gram_route (kernels.hip) on the values given
+extern "C" int tnqs_dbg_gram_route(int dtype, int acc64, int has_m, int all_same, int all_f64in, int kkmax, int use_mfma, int use_chi64, int* route) {
+    return guard([&] {
+        if (!is_dtype(dtype) || kkmax < 1 || !route) throw Err(TNQS_ERR_INVALID, "tnqs_dbg_gram_route: bad arguments");
+        *route = (int)gram_route(dtype == TNQS_C64, acc64 != 0, has_m != 0, all_same != 0, all_f64in != 0, (size_t)kkmax, use_mfma != 0, use_chi64 != 0);
     });
 }

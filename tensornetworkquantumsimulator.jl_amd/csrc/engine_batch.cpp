@@ -245,17 +245,10 @@ template <class T, class Acc> void run_grams(State* s, std::vector<GramJob>& job
     const size_t esz = s->esz();
     size_t KKmax = 1;
     for (auto& j : jobs) { j.KK = (j.keep_site ? j.sd.d : 1) * (j.leg >= 0 ? j.sd.chi[j.leg] : 1); KKmax = std::max<size_t>(KKmax, j.KK); }
-    constexpr bool f32 = std::is_same<T, float>::value, f32_acc64 = f32 && std::is_same<Acc, double>::value, acc32 = std::is_same<Acc, float>::value;
-    bool same = true, f64in = std::is_same<T, double>::value && use_mfma();
+    constexpr bool f32 = std::is_same<T, float>::value, acc64 = std::is_same<Acc, double>::value, f32_acc64 = f32 && acc64;
+    bool same = true, f64in = true;
     for (auto& j : jobs) { same = same && j.X == j.Y; f64in = f64in && j.M == nullptr && gram_f64in_covers(j.keep_site ? j.sd.d : 1, j.leg >= 0 ? j.sd.chi[j.leg] : 1); }
-    // M set: the BP Gram absorbs the first row leg (f32 accumulation, mfma_gram32_fused_kernel); the gate-path Gram (f64 accumulation)
-    // absorbs the last gauge leg (mfma_gauge_gram64_kernel; 16-dimensional legs: the wave-private mfma_gauge_gram32_kernel) -- a batch is one or the other
-    GramRoute r = GramRoute::Generic;
-    if (jobs[0].M) r = f32_acc64 ? (KKmax == 32 ? GramRoute::Gauge32 : GramRoute::Gauge64) : GramRoute::Fused32;
-    else if (f32_acc64 && use_mfma() && same && KKmax <= 64 && KKmax >= 16) r = GramRoute::F64x64;
-    else if (f32_acc64 && use_mfma() && use_chi64() && same && KKmax <= 128 && KKmax > 64) r = GramRoute::F64x128;
-    else if (f64in) r = GramRoute::F64In;          // ComplexF64 operands: tiles of 32 fibers through LDS, f64 matrix cores (kernels_f64.hip)
-    else if (f32 && acc32 && use_mfma() && KKmax <= (use_chi64() ? 64 : 32) && KKmax >= 8) r = KKmax <= 32 ? GramRoute::Mfma32 : GramRoute::Mfma64;
+    const GramRoute r = gram_route(f32, acc64, jobs[0].M != nullptr, same, f64in, KKmax, use_mfma(), use_chi64());      // (kernels.hip, next to gram_tile_rows)
     const bool gauge = r == GramRoute::Gauge32 || r == GramRoute::Gauge64;
     const int TR = gram_tile_rows(r, KKmax, esz);
     std::vector<GramItem> items; double bytes = 0, flops = 0; bool all_full = true;

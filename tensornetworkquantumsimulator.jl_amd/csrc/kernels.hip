@@ -196,6 +196,17 @@ template void launch_gram<float, float>(hipStream_t, const GramItem*, int, int, 
 template void launch_gram<float, double>(hipStream_t, const GramItem*, int, int, int, int);
 template void launch_gram<double, double>(hipStream_t, const GramItem*, int, int, int, int);
 
+// M set: the BP Gram absorbs the first row leg (f32 accumulation, mfma_gram32_fused_kernel); the gate-path Gram (f64 accumulation)
+// absorbs the last gauge leg (mfma_gauge_gram64_kernel; 16-dimensional legs: the wave-private mfma_gauge_gram32_kernel) -- a batch is one or the other
+GramRoute gram_route(bool f32, bool acc64, bool has_M, bool all_same, bool all_f64in, size_t KKmax, bool use_mfma, bool use_chi64) {
+    const bool f32_acc64 = f32 && acc64;
+    if (has_M) return f32_acc64 ? (KKmax == 32 ? GramRoute::Gauge32 : GramRoute::Gauge64) : GramRoute::Fused32;
+    if (f32_acc64 && use_mfma && all_same && KKmax <= 64 && KKmax >= 16) return GramRoute::F64x64;
+    if (f32_acc64 && use_mfma && use_chi64 && all_same && KKmax <= 128 && KKmax > 64) return GramRoute::F64x128;
+    if (!f32 && use_mfma && all_f64in) return GramRoute::F64In;          // ComplexF64 operands: tiles of 32 fibers through LDS, f64 matrix cores (kernels_f64.hip)
+    if (f32 && !acc64 && use_mfma && KKmax <= (use_chi64 ? 64u : 32u) && KKmax >= 8) return KKmax <= 32 ? GramRoute::Mfma32 : GramRoute::Mfma64;
+    return GramRoute::Generic;
+}
 int gram_tile_rows(GramRoute r, size_t KKmax, size_t esz) {
     const int tr = pick_TR(KKmax + 1, esz, 2);          // the generic kernel: two operand blocks in LDS
     return r == GramRoute::Generic ? tr : r == GramRoute::F64In ? 32 : 64;

@@ -257,6 +257,9 @@ template <class T, class Acc> void launch_gram(hipStream_t s, const GramItem* d_
 // the Gram kernel of a batch, decided once by the caller: generic tiled; f32 matrix cores up to 32 x 32 / 64 x 64; message fused on the first
 // row leg (32 x 32); f64 accumulation on the f64 matrix cores, 64 x 64 / 128 x 128; ComplexF64 operands; gauge leg fused, 32- / 16-dimensional legs
 enum class GramRoute { Generic, Mfma32, Mfma64, Fused32, F64x64, F64x128, F64In, Gauge64, Gauge32 };
+// the route of a batch, from values alone (run_grams and the debug entry points ask here): f32 / acc64: element type ComplexF32, accumulation in double;
+// has_M: the jobs carry a matrix to absorb; all_same: X == Y on every job; all_f64in: every job passes gram_f64in_covers and carries no M; the two switches
+GramRoute gram_route(bool f32, bool acc64, bool has_M, bool all_same, bool all_f64in, size_t KKmax, bool use_mfma, bool use_chi64);
 int gram_tile_rows(GramRoute r, size_t KKmax, size_t esz);       // TR: fibers per tile of the route
 // chunks of a batch whose tiles are set: min(max_chunks, tiles) per item (max_chunks <= 0: the engine's target of workgroups per launch; f32_acc64:
 // f32 data accumulated in f64); npart[i]: the partials item i leaves; returns the launch's chunks
@@ -487,6 +490,7 @@ bool launch_mfma_gram64_f64(hipStream_t s, const GramItem* d_items, int nitems, 
 // ComplexF64 mode products on the f64 matrix cores (kernels_f64.hip): one wave per tile of 16 fibers, FiberItem::tpw tiles per wave-quartet
 bool fiber_gemm_f64_covers(const FiberItem& it);
 int plan_fiber_gemm_f64(FiberItem* it, int n, int* nwg = nullptr, int tpw = 0);     // sets the tile grid too
+void fiber_gemm_f64_inst(int Kmax, int Nmax, int* nblk, int* ks);     // <NBLK, KS, *> of the kernel a launch with these maxima runs (the launcher and tnqs_dbg_fiber_pass_c128 ask here)
 void launch_mfma_fiber_gemm_f64(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, int Kmax, int Nmax, double* d_norm_partials, bool general);
 bool gram_f64in_covers(int D, int K);          // ComplexF64 Gram over tiles of 32 fibers (one partial per chunk)
 void launch_mfma_gram_f64in(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks);

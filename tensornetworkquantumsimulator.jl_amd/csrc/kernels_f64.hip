@@ -136,9 +136,13 @@ template <int NBLK, int KS, bool GEN> static void launch_one(hipStream_t s, cons
 }
 // Kmax / Nmax: largest contracted / produced index (D K, Do No) among the items; d_norm_partials: one double per workgroup (FiberItem::want_norm);
 // general: some item has D != 1, Do != 1 or wants its norm
+// the instantiation <NBLK, KS, *> a launch runs: the smallest whose 16 NBLK rows of X^T and 4 KS k-steps hold the largest item
+void fiber_gemm_f64_inst(int Kmax, int Nmax, int* nblk, int* ks) {
+    *nblk = Nmax <= 16 ? 1 : (Nmax <= 32 ? 2 : 4); *ks = Kmax <= 16 ? 4 : (Kmax <= 32 ? 8 : 16);
+}
 void launch_mfma_fiber_gemm_f64(hipStream_t s, const FiberItem* d_items, int nitems, int total_wgs, int Kmax, int Nmax, double* d_norm_partials, bool general) {
     if (total_wgs <= 0) return;
-    const int nblk = Nmax <= 16 ? 1 : (Nmax <= 32 ? 2 : 4), ks = Kmax <= 16 ? 4 : (Kmax <= 32 ? 8 : 16);
+    int nblk, ks; fiber_gemm_f64_inst(Kmax, Nmax, &nblk, &ks);
     const size_t lds = (size_t)16 * nblk * (((Kmax + 3) & ~3) + 1) * sizeof(zc);
 #define TNQS_F64(NB, KSV) if (nblk == NB && ks == KSV) { if (general) launch_one<NB, KSV, true>(s, d_items, nitems, total_wgs, lds, d_norm_partials); else launch_one<NB, KSV, false>(s, d_items, nitems, total_wgs, lds, d_norm_partials); }
     TNQS_F64(1, 4) TNQS_F64(1, 8) TNQS_F64(1, 16) TNQS_F64(2, 4) TNQS_F64(2, 8) TNQS_F64(2, 16) TNQS_F64(4, 4) TNQS_F64(4, 8) TNQS_F64(4, 16)

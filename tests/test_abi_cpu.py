@@ -41,7 +41,7 @@ def test_library_exports_every_declared_debug_symbol():
             "tnqs_dbg_symg_build", "tnqs_dbg_symg_finish", "tnqs_dbg_diag", "tnqs_dbg_cscale", "tnqs_dbg_fiber_plan",
             "tnqs_dbg_operator_sum", "tnqs_dbg_gate_theta", "tnqs_dbg_gate_finish", "tnqs_dbg_qr2", "tnqs_dbg_small_svd",
             "tnqs_dbg_site_prob", "tnqs_dbg_site_draw", "tnqs_dbg_site_project", "tnqs_dbg_site1", "tnqs_dbg_norm_factor", "tnqs_dbg_scale",
-            "tnqs_dbg_inner_scalar", "tnqs_dbg_theta_svd_stage"} <= decl
+            "tnqs_dbg_inner_scalar", "tnqs_dbg_theta_svd_stage", "tnqs_dbg_fiber_pass_c128", "tnqs_dbg_gram_c128", "tnqs_dbg_gram_route"} <= decl
     for name in sorted(decl):
         assert hasattr(lib, name), f"{name} declared in include/tnqs_debug.h but not exported"
 

@@ -66,7 +66,24 @@ def fiber_ref(x, X, D, PA, K, PB, Do, No):
     return out.transpose(3, 2, 1, 0).reshape(-1)                 # memory order: s' fastest, then a, n, b
 
 
-@pytest.mark.parametrize("dtype,mfma", [(0, 0), (1, 0), (0, 1), (1, 1)])       # (1, 1): ComplexF64 on the f64 matrix cores (kernels_f64.hip), shapes it covers
+def c128_routes(D, PA, K, PB, Do, No, same):
+    """what a single ComplexF64 item runs on with the matrix cores on, from the HOST ONLY modes of tnqs_dbg_fiber_pass_c128 (the epilogue's rules with 12 tiles per
+    workgroup, as tnqs_dbg_fiber_gemm plans) and tnqs_dbg_gram_c128 (gram_route, as tnqs_dbg_gram asks it): (fiber route, Gram route), TNQS_DBG_ROUTE_*"""
+    IP = C.POINTER(C.c_int)
+    fs = (C.c_int * 6)(D, PA, K, PB, Do, No); gs = (C.c_int * 4)(D, PA, K, PB); one = (C.c_int * 1)(1); sm = (C.c_int * 1)(int(same)); fr, gr = C.c_int(-1), C.c_int(-1)
+    lib.tnqs_dbg_fiber_pass_c128.argtypes = [C.c_int, C.c_int, C.c_int, IP, IP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, IP, IP, IP, IP]
+    lib.tnqs_dbg_gram_c128.argtypes = [C.c_int, C.c_int, IP, IP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, IP, C.c_int, IP]
+    assert lib.tnqs_dbg_fiber_pass_c128(1, 1, 1, fs, one, None, None, None, None, 12, 0, C.byref(fr), None, None, None) == 0, lib.tnqs_last_error()
+    assert lib.tnqs_dbg_gram_c128(1, 1, gs, sm, None, None, None, 0, None, 0, C.byref(gr)) == 0, lib.tnqs_last_error()
+    return fr.value, gr.value
+
+
+FIBER_GENERIC, FIBER_F64_GENERAL, GRAM_GENERIC, GRAM_F64IN = 15, 17, 18, 19      # TNQS_DBG_ROUTE_* (include/tnqs_debug.h)
+
+
+# (1, 1): ComplexF64 with the matrix cores on -- mfma_fiber_gemm_f64_kernel<.., true> (kernels_f64.hip) where 4 <= D K <= 64 and Do No <= 64, else the vector kernel
+# (the shapes with D K > 64 or D K < 4); which of the two is asserted below before the numbers
+@pytest.mark.parametrize("dtype,mfma", [(0, 0), (1, 0), (0, 1), (1, 1)])
 @pytest.mark.parametrize("D,PA,K,PB,Do,No", [(2, 64, 64, 8, 2, 64), (1, 128, 64, 16, 1, 64), (2, 4, 64, 70, 2, 40), (1, 64, 32, 64, 1, 32), (2, 32, 32, 32, 2, 32), (2, 128, 32, 4, 2, 17), (1, 2, 32, 200, 1, 32), (2, 16, 16, 70, 2, 5),
                                              (1, 2, 3, 5, 1, 3), (1, 100, 10, 7, 1, 10), (1, 1, 7, 130, 1, 7), (2, 9, 5, 4, 2, 3),
                                              (2, 1, 1, 1, 2, 1), (2, 300, 1, 1, 2, 1), (1, 64, 32, 33, 1, 32), (2, 16, 16, 16, 2, 16),
@@ -81,6 +98,8 @@ def test_fiber_gemm(dtype, mfma, D, PA, K, PB, Do, No):
     X = rnd(rng, D * K * Do * No, dt)
     out = np.zeros(Do * PA * No * PB, dtype=dt)
     n2 = C.c_double()
+    if dtype == 1 and mfma == 1:
+        assert c128_routes(D, PA, K, PB, Do, No, True)[0] == (FIBER_F64_GENERAL if 4 <= D * K <= 64 and Do * No <= 64 else FIBER_GENERIC)
     rc = lib.tnqs_dbg_fiber_gemm(dtype, D, PA, K, PB, Do, No, x.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p),
                                  out.ctypes.data_as(C.c_void_p), C.byref(n2), mfma)
     assert rc == 0, lib.tnqs_last_error()
@@ -90,7 +109,7 @@ def test_fiber_gemm(dtype, mfma, D, PA, K, PB, Do, No):
     assert abs(n2.value - np.sum(np.abs(ref) ** 2)) < 1e-5 * np.sum(np.abs(ref) ** 2)
 
 
-@pytest.mark.parametrize("dtype,acc64,mfma", [(0, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (0, 1, 1), (1, 1, 1)])       # (1, 1, 1): ComplexF64 operands, f64 matrix cores
+@pytest.mark.parametrize("dtype,acc64,mfma", [(0, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (0, 1, 1), (1, 1, 1)])       # (1, 1, 1): ComplexF64 operands with the matrix cores on (D K > 64 or < 4: the vector kernel; asserted below)
 @pytest.mark.parametrize("D,PA,K,PB,same", [(2, 64, 64, 16, 1), (2, 2, 64, 300, 1), (1, 64, 64, 32, 0), (2, 1024, 32, 32, 1), (2, 32, 32, 1000, 1), (2, 1, 32, 1024, 1), (2, 77, 19, 11, 1), (1, 64, 32, 1024, 0), (1, 2048, 32, 32, 0), (1, 2, 32, 700, 1), (1, 70, 17, 9, 0),
                                            (1, 2, 3, 5, 0), (1, 100, 10, 7, 0), (1, 1, 7, 130, 1), (2, 9, 5, 40, 1), (2, 30, 1, 1, 0),
                                            (1, 64, 32, 33, 0), (2, 16, 16, 16, 1), (2, 512, 32, 8, 1), (3, 5, 5, 6, 0)])
@@ -106,6 +125,8 @@ def test_gram(dtype, acc64, mfma, D, PA, K, PB, same):
     KK = D * K
     odt = np.complex128 if (acc64 or dtype == 1) else np.complex64
     out = np.zeros(KK * KK, dtype=odt)
+    if dtype == 1 and mfma == 1:      # mfma_gram_f64in_kernel where 4 <= D K <= 64, else the vector kernel: asserted before the numbers
+        assert c128_routes(D, PA, K, PB, D, K, same)[1] == (GRAM_F64IN if 4 <= KK <= 64 else GRAM_GENERIC)
     rc = lib.tnqs_dbg_gram(dtype, D, PA, K, PB, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p),
                            out.ctypes.data_as(C.c_void_p), acc64, mfma)
     assert rc == 0, lib.tnqs_last_error()
