@@ -290,6 +290,25 @@ int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, cons
  * niter, final_diff may be NULL. */
 int tnqs_inner_bp(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff);
 
+/* ---- amplitudes of bitstrings --------------------------------------------------------------------------------------
+ * log <x|psi> of nstrings bitstrings in ONE call, by belief propagation on the single-layer network A_v = T_v[x_v, ...] (the reference's contract(tn; alg = "bp"),
+ * src/contract.jl:7-9; what certify_sample contracts per sample, src/sampling.jl:258-285).  configs: nstrings x nv int32, string-major, vertex order of tnqs_create,
+ * 0 <= x_v < d_v (the CURRENT site dimension).  The state is taken as it stands on the handle, un-normalised: deferred one-site gates are applied first, pending scale
+ * factors are honoured; the handle's own messages are neither read nor written.  Messages are vectors of length chi(e) in the state's type that live in buffers of the
+ * call and start as ALL ONES (src/TensorNetworks/tensornetwork.jl:62-64) -- not e_0, which is what tnqs_inner_bp's rectangular delta gives a chi = 1 bra: same fixed
+ * points, different numbers after finitely many sweeps on a loopy graph.  Update: m_{u->v}[j] = sum A_u[.., j, ..] prod_{k != v} m_{k->u}[i_k], divided by its element
+ * sum when opts->normalize and that sum is not exactly zero; sweeps are Gauss-Seidel over the sequence of bp_opts exactly as tnqs_inner_bp runs them; message_diff is
+ * averaged over the sequence.  opts == NULL: maxiter 25 (1 on a tree), NO tolerance, default sequence (a NaN tolerance in opts selects 1e-5 / 1e-8).
+ * out_log_re_im[2 n, 2 n + 1] = sum_v log(vertex scalar) - sum_e log(edge scalar) of string n, complex logs in f64 whatever the element type, imaginary part in
+ * (-pi, pi]; the amplitude is its exp.  niter[n], final_diff[n], flags[n] (each may be NULL): with a tolerance string n stops at the first sweep whose average diff is
+ * <= tolerance and its messages are frozen from then on, so all three and the result are what a call with that string alone gives (one read-back of the done flags per
+ * sweep; without a tolerance one read-back per call).  flags bit 0: a vertex or edge scalar of the string is exactly zero, its result is (-inf, 0); bit 1: a scalar is
+ * not finite, its result is (NaN, NaN).  Neither fails the call nor touches the other strings.  nstrings == 0: TNQS_OK, nothing done.
+ * TNQS_ERR_INVALID, before any device work: a null pointer with work to do, a configuration outside 0 .. d_v - 1, a null explicit sequence, nstrings < 0.
+ * TNQS_ERR_UNSUPPORTED: a sharded handle, a vertex of more than 7 neighbours, a bond dimension above 64 (refused up front: the kernels take 1..64 and there is no
+ * scalar form), a site tensor of more than 2^30 d_v elements. */
+int tnqs_amplitudes_bp(tnqs_handle h, int nstrings, const int32_t* configs, const tnqs_bp_opts* opts, double* out_log_re_im, int32_t* niter, double* final_diff, int32_t* flags);
+
 /* ---- multi-GPU sharding (no reference analogue).  A rank owns a vertex subset: it holds only
  *      those site tensors and does all per-vertex work for them; messages are replicated.  The library calls
  *      the host-supplied all-gather at the exchange points (host side: torch.distributed over RCCL). --------- */

@@ -290,6 +290,26 @@ int tnqs_dbg_norm_factor(int nitems, const int* npart, const double* partials, d
 int tnqs_dbg_scale(int dtype, int nitems, const int* len, const void* src, const double* factor, void* dst, int guard);
 /* tnqs_inner_bp with the bound on a batch's chain workspace given explicitly (bytes, >= 1); *nbatches_out (may be NULL): the batches of messages it ran */
 int tnqs_dbg_inner_bp_ws(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, int64_t workspace_bytes, int* nbatches_out);
+/* ---- bitstring amplitudes (csrc/kernels_amp.hip, csrc/engine_amp.cpp; dtype 0 c64, 1 c128), launched as the engine launches them for one chunk of strings ----
+ * amp_leg_gemm_kernel<T>, ONE launch over the groups of nitems jobs.  shape: (d, PA, K, PB, nstr) per job; T: the jobs' site tensors [d][PA][K][PB] one after the other;
+ * x: nstr site values per job (0 .. d - 1), one after the other; M: the strings' message vectors [K][nstr] per job (has_m[i] == 0: the kernel gets a null pointer, all ones).
+ * Per job and value g the strings with x = g form one item (group) whose index list is built as the engine builds it; a value no string takes gives no item.
+ * R_i[(a + PA b') + PA PB p] = sum_k T_i[x_p + d (a + PA (k + K b'))] M_i[k + K p], laid out as guard, job 0 (PA PB nstr numbers), guard, ..., guard: it goes up as the
+ * caller filled it and comes back whole.  K outside 1..64: TNQS_ERR_UNSUPPORTED (there is no scalar form), nothing is written */
+int tnqs_dbg_amp_leg_gemm(int dtype, int nitems, const int* shape, const void* T, const int32_t* x, const void* M, const int* has_m, void* R, int guard);
+/* amp_absorb_kernel<T>, ONE launch over nitems steps.  shape: (PA, K, PB, nstr) per step; in_i [PA][K][PB][nstr], m_i [K][nstr] (a slot for every step; has_m[i] == 0: a null
+ * pointer, all ones); out_i[a + PA (b' + PB p)] = sum_k in_i[a, k, b', p] m_i[k, p], guarded as above.  K outside 1..64: TNQS_ERR_UNSUPPORTED, nothing is written */
+int tnqs_dbg_amp_absorb(int dtype, int nitems, const int* shape, const void* in, const void* m, const int* has_m, void* out, int guard);
+/* amp_finalize_kernel<T>, ONE launch over nitems messages of chi[i] numbers for nstr[i] strings: raw_i, old_msg_i [chi][nstr] (a slot for every item; has_old[i] == 0: a null
+ * pointer, all ones); done (may be NULL): one int per string, the items one after the other.  Per string p: sum_out = the raw element sum (two doubles), new_msg = raw / sum
+ * when normalize[i] != 0 and the sum is not exactly zero, diff_out = message_diff(new, old).  A string whose done flag is set: nothing of it is stored -- diff_out and sum_out
+ * come back as they went up -- and its old message is carried over into new_msg bit for bit.  new_msg guarded as above.  chi outside 1..64: TNQS_ERR_UNSUPPORTED */
+int tnqs_dbg_amp_finalize(int dtype, int nitems, const int* chi, const int* nstr, const void* raw, const void* old_msg, const int* has_old, const int* normalize, const int* done,
+                          void* new_msg, double* diff_out, double* sum_out, int guard);
+/* tnqs_amplitudes_bp with the workspace bound given explicitly (bytes, >= 1): it sizes the batches of jobs AND the chunks of strings; *nbatches_out (may be NULL): the
+ * (batch of messages, chunk of strings) pairs it ran */
+int tnqs_dbg_amplitudes_bp_ws(tnqs_handle h, int nstrings, const int32_t* configs, const tnqs_bp_opts* opts, double* out_log_re_im, int32_t* niter, double* final_diff,
+                              int32_t* flags, int64_t workspace_bytes, int* nbatches_out);
 /* ---- the ComplexF64 kernels of csrc/kernels_f64.hip as the engine launches them: ONE launch over items of different sizes.  The items' arrays are passed one after
  * the other; on the device every sub-array starts at a multiple of 256 bytes; each output with a `guard` is laid out as guard, item 0, guard, ..., guard (elements of
  * its own type), goes up as the caller filled it and comes back whole.  Nothing is refused for its shape: a launch the matrix-core kernel does not take runs on the

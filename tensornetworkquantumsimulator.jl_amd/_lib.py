@@ -95,6 +95,7 @@ _SIGS = {
     "tnqs_rdm_paths": ([H, C.c_int, _I32P, _I32P, _DP], C.c_int),
     "tnqs_bond_spectra": ([H, C.c_int, _I32P, _I32P, _DP], C.c_int),
     "tnqs_inner_bp": ([H, H, C.POINTER(BpOpts), _DP, C.POINTER(C.c_int), _DP], C.c_int),
+    "tnqs_amplitudes_bp": ([H, C.c_int, _I32P, C.POINTER(BpOpts), _DP, _I32P, _DP, _I32P], C.c_int),
     "tnqs_expect_all": ([H, _DP, _DP], C.c_int),
     "tnqs_expect_region": ([H, C.c_int, _I32P, _I32P, _DP, _DP], C.c_int),
     "tnqs_vertex_scalars": ([H, _DP], C.c_int),

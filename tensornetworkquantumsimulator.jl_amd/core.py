@@ -14,6 +14,7 @@ reference repo):
   sample(psi, nsamples; alg = "bp")                                       src/sampling.jl:3-46
   norm_sqr / norm (alg = "bp", "loopcorrections"), loopcorrected_partitionfunction   src/norm_sqr.jl:10-18,62-78, src/MessagePassing/loopcorrection.jl:3-14
   inner / log_inner (alg = "bp")                                          src/inner.jl:65-69, src/Forms/bilinearform.jl:16-25
+  log_amplitudes / amplitudes / log_probabilities (alg = "bp")            src/contract.jl:7-9 on the network certify_sample builds, src/sampling.jl:258-285
   bond_spectra / bond_entropies / renyi_entropy / von_neumann_... / second_renyi_entanglement_entropy   src/entanglement.jl:21-29,73-159 (alg = "bp")
 Every flop runs in libtnqs_hip.so; this file only marshals arguments through the C ABI (include/tnqs.h)."""
 from __future__ import annotations
@@ -1227,6 +1228,90 @@ def log_inner(psi, phi, alg: str = "bp", cache_update_kwargs: Optional[dict] = N
 def inner(psi, phi, alg: str = "bp", cache_update_kwargs: Optional[dict] = None, device: int = 0, info: Optional[dict] = None) -> complex:
     """inner(psi, phi; alg = "bp") = exp(log_inner(...)) = sum psi conj(phi) in the BP approximation (exact on trees); see log_inner for the arguments"""
     return complex(np.exp(log_inner(psi, phi, alg=alg, cache_update_kwargs=cache_update_kwargs, device=device, info=info)))
+
+
+def _configs_of(graph, dims, bitstrings, who: str):
+    """bitstrings -> ((B, nv) int32 array in graph.vertices order, single): a sequence of {vertex: int} dicts (what `sample` returns) or an integer array (B, nv);
+    one dict or one row is a single string.  TnqsArgumentError for a missing vertex, a wrong width, a value that is no integer or lies outside 0 .. d_v - 1"""
+    verts = list(graph.vertices)
+    nv = len(verts)
+    single = isinstance(bitstrings, dict)
+    rows = [bitstrings] if single else bitstrings
+    if single or (isinstance(rows, (list, tuple)) and len(rows) > 0 and all(isinstance(r, dict) for r in rows)):
+        cfg = np.zeros((len(rows), nv), dtype=np.int64)
+        for j, r in enumerate(rows):
+            for i, v in enumerate(verts):
+                if v not in r:
+                    raise L.TnqsArgumentError(f"{who}: bitstring {j} has no value for vertex {v!r}")
+                if int(r[v]) != r[v]:
+                    raise L.TnqsArgumentError(f"{who}: the value of vertex {v!r} in bitstring {j} is not an integer ({r[v]!r})")
+                cfg[j, i] = int(r[v])
+    else:
+        a = np.asarray(rows)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise L.TnqsArgumentError(f"{who}: bitstrings are dicts {{vertex: int}} or an integer array (received dtype {a.dtype})")
+        if a.ndim == 1 and a.size == nv and nv > 0:
+            a, single = a.reshape(1, nv), True
+        if a.ndim == 1 and a.size == 0:
+            a = a.reshape(0, nv)
+        if a.ndim != 2 or a.shape[1] != nv:
+            raise L.TnqsArgumentError(f"{who}: an array of bitstrings has shape (B, number of vertices) = (B, {nv}); received {a.shape}")
+        cfg = a.astype(np.int64)
+    d = np.asarray(dims, dtype=np.int64).reshape(1, nv)
+    bad = np.argwhere((cfg < 0) | (cfg >= d))
+    if len(bad):
+        j, i = (int(t) for t in bad[0])
+        raise L.TnqsArgumentError(f"{who}: the value {int(cfg[j, i])} of vertex {verts[i]!r} in bitstring {j} is outside 0..{int(d[0, i]) - 1}")
+    return np.ascontiguousarray(cfg, dtype=np.int32), single
+
+
+def log_amplitudes(x, bitstrings, alg: str = "bp", cache_update_kwargs: Optional[dict] = None, device: int = 0, info: Optional[dict] = None):
+    """log <x|psi> of a batch of bitstrings in one device call (tnqs_amplitudes_bp): belief propagation on the single-layer network T_v[x_v, ...] -- the reference's
+    contract(tn; alg = "bp") (src/contract.jl:7-9) with vector messages that start as all ones, what certify_sample contracts per sample (src/sampling.jl:258-285); exact
+    on trees.  Returns a complex128 array, one entry per string (imaginary parts in (-pi, pi]; -inf + 0j: the amplitude is exactly 0), or one complex number for a single
+    string.  x: a TensorNetworkState (uploaded to a temporary handle on `device`) or a BeliefPropagationCache, whose network is used as it stands on its handle,
+    un-normalised -- its own messages are neither read nor changed.  bitstrings: a sequence of {vertex: int} dicts, exactly what `sample` returns, or an integer array
+    (B, nv) in graph.vertices order; one dict or one row gives a scalar.  cache_update_kwargs: maxiter, tolerance, edge_sequence (and normalize) as `inner` takes them;
+    omitted: maxiter 25 (1 on a tree), no tolerance, the default sequence.  With a tolerance every string stops on its own, as if it had been the only one.  info
+    (optional dict) receives the arrays niter, diff, converged and flags (bit 0: a vertex or edge scalar exactly zero, bit 1: a scalar not finite, the result then nan)."""
+    if alg != "bp":
+        raise L.TnqsError(f'amplitudes: algorithm choice not supported; supported on the HIP path: "bp" (received {alg!r})')
+    if not isinstance(x, (TensorNetworkState, BeliefPropagationCache)):
+        raise TypeError("amplitudes: expected a TensorNetworkState or a BeliefPropagationCache")
+    g = x.graph
+    cfg, single = _configs_of(g, _site_dims_of(x), bitstrings, "amplitudes")
+    o, keep = _bp_opts(g, {} if cache_update_kwargs is None else cache_update_kwargs)
+    bpc = x if isinstance(x, BeliefPropagationCache) else BeliefPropagationCache(x, device=device)
+    nb = cfg.shape[0]
+    out = np.zeros(2 * max(nb, 1), dtype=np.float64)
+    niter, flags, diff = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.float64)
+    L.check(L.lib.tnqs_amplitudes_bp(bpc._h, nb, cfg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(o), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                     niter.ctypes.data_as(C.POINTER(C.c_int32)), diff.ctypes.data_as(C.POINTER(C.c_double)), flags.ctypes.data_as(C.POINTER(C.c_int32))))
+    if info is not None:
+        info.update(niter=niter[:nb].copy(), diff=diff[:nb].copy(), converged=(diff[:nb] <= o.tolerance) if o.tolerance >= 0 else np.zeros(nb, dtype=bool), flags=flags[:nb].copy())
+    res = out[:2 * nb:2] + 1j * out[1:2 * nb:2]
+    return complex(res[0]) if single else res
+
+
+def amplitudes(x, bitstrings, alg: str = "bp", cache_update_kwargs: Optional[dict] = None, device: int = 0, info: Optional[dict] = None):
+    """<x|psi> = exp(log_amplitudes(...)) in the BP approximation (exact on trees); see log_amplitudes for the arguments"""
+    la = log_amplitudes(x, bitstrings, alg=alg, cache_update_kwargs=cache_update_kwargs, device=device, info=info)
+    return complex(np.exp(la)) if isinstance(la, complex) else np.exp(la)
+
+
+def log_probabilities(bpc, bitstrings, alg: str = "bp", cache_update_kwargs: Optional[dict] = None, device: int = 0, info: Optional[dict] = None):
+    """log p(x) = 2 Re log <x|psi> - log norm_sqr(psi; alg = "bp"): the normalised BP probability of each string, the p that goes with the log q of
+    sample_with_probabilities (p / q re-weighting, src/sampling.jl:258-285).  bpc: an updated BeliefPropagationCache (its messages give the norm) or a TensorNetworkState
+    (a cache is built and updated with its defaults on `device`)."""
+    if alg != "bp":
+        raise L.TnqsError(f'amplitudes: algorithm choice not supported; supported on the HIP path: "bp" (received {alg!r})')
+    if isinstance(bpc, TensorNetworkState):
+        bpc = BeliefPropagationCache(bpc, device=device)
+        bpc = update(bpc, **bpc.default_bp_update_kwargs())
+    la = log_amplitudes(bpc, bitstrings, alg=alg, cache_update_kwargs=cache_update_kwargs, device=device, info=info)
+    with np.errstate(divide="ignore"):
+        ln = float(np.log(complex(norm_sqr(bpc, alg="bp"))).real)
+    return 2 * la.real - ln
 
 
 def site_probabilities(bpc: BeliefPropagationCache, v) -> np.ndarray:

@@ -137,6 +137,9 @@ int tnqs_rdm_paths(tnqs_handle h, int npaths, const int32_t* path_len, const int
 int tnqs_inner_bp(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff) {
     return guard([&] { inner_bp(S(ket), S(bra), opts, out_log_re_im, niter, final_diff); });
 }
+int tnqs_amplitudes_bp(tnqs_handle h, int nstrings, const int32_t* configs, const tnqs_bp_opts* opts, double* out_log_re_im, int32_t* niter, double* final_diff, int32_t* flags) {
+    return guard([&] { amplitudes_bp(S(h), nstrings, configs, opts, out_log_re_im, niter, final_diff, flags); });
+}
 int tnqs_expect_all(tnqs_handle h, const double* ops, double* out) {
     return guard([&] { if (!ops || !out) throw Err(TNQS_ERR_INVALID, "expect_all: null"); expect_all(S(h), ops, out); });
 }

@@ -1,6 +1,6 @@
 // debug_obs.cpp -- kernel-level test entry points (include/tnqs_debug.h) of the observables: loop corrections (kernels_loop.hip), reduced density matrices of bonds and
 // paths (kernels_rdm.hip, engine_rdm.cpp, engine_paths.cpp), bond entanglement spectra (kernels_spectrum.hip, engine_spectra.cpp), overlap of two states
-// (kernels_inner.hip, engine_inner.cpp).
+// (kernels_inner.hip, engine_inner.cpp), bitstring amplitudes (kernels_amp.hip, engine_amp.cpp).
 #include "debug_util.hpp"
 
 using namespace tnqs;
@@ -325,5 +325,121 @@ extern "C" int tnqs_dbg_inner_bp_ws(tnqs_handle ket, tnqs_handle bra, const tnqs
     return guard([&] {
         if (workspace_bytes < 1) throw Err(TNQS_ERR_INVALID, "dbg_inner_bp_ws: the workspace bound must be positive");
         inner_bp(S(ket), S(bra), opts, out_log_re_im, niter, final_diff, (size_t)workspace_bytes, nbatches_out);
+    });
+}
+
+// ---- bitstring amplitudes (kernels_amp.hip), the descriptors filled as engine_amp.cpp run_batch fills them for one chunk of strings ------------------------------------
+// ONE launch_amp_leg_gemm<T> over the groups of nitems jobs (d, PA, K, PB, nstr): per job and site value g < d the strings with x = g are one item, an empty group none
+extern "C" int tnqs_dbg_amp_leg_gemm(int dtype, int nitems, const int* shape, const void* T, const int32_t* x, const void* M, const int* has_m, void* R, int guard_elems) {
+    return guard([&] {
+        if (!is_dtype(dtype) || nitems < 1 || !shape || !T || !x || !M || !has_m || !R || guard_elems < 0) throw Err(TNQS_ERR_INVALID, "dbg_amp_leg_gemm: bad arguments");
+        const size_t esz = esz_of(dtype);
+        Slots sT, sM; Guarded gR((size_t)guard_elems * esz);
+        std::vector<int> idx; std::vector<size_t> xoff(nitems + 1, 0);
+        for (int i = 0; i < nitems; ++i) {
+            const int* q = shape + 5 * i;
+            if (q[0] < 1 || q[1] < 1 || q[3] < 1 || q[4] < 1 || (long long)q[1] * q[3] > (1LL << 30) / q[4]) throw Err(TNQS_ERR_INVALID, "dbg_amp_leg_gemm: bad shape");
+            if (!amp_covers(q[2])) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_amp_leg_gemm: the leg GEMM takes 1 <= K <= 64");
+            xoff[i + 1] = xoff[i] + q[4];
+            for (int p = 0; p < q[4]; ++p) if (x[xoff[i] + p] < 0 || x[xoff[i] + p] >= q[0]) throw Err(TNQS_ERR_INVALID, "dbg_amp_leg_gemm: a site value outside 0 .. d - 1");
+            sT.add((size_t)q[0] * q[1] * q[2] * q[3] * esz); sM.add((size_t)q[2] * q[4] * esz); gR.add((size_t)q[1] * q[3] * q[4] * esz);
+        }
+        need_gpu();
+        alloc_all(sT, sM, gR);
+        put_all(sT, T); put_all(sM, M);
+        idx.resize(xoff[nitems]);
+        DBuf dIdx(sizeof(int) * idx.size());
+        std::vector<AmpGemmItem> gi;
+        for (int i = 0; i < nitems; ++i) {
+            const int* q = shape + 5 * i; const int32_t* xi = x + xoff[i];
+            std::vector<int> off(q[0] + 1, 0);
+            for (int p = 0; p < q[4]; ++p) ++off[xi[p] + 1];
+            for (int g = 0; g < q[0]; ++g) off[g + 1] += off[g];
+            std::vector<int> at(off.begin(), off.end() - 1);
+            for (int p = 0; p < q[4]; ++p) idx[xoff[i] + at[xi[p]]++] = p;
+            for (int g = 0; g < q[0]; ++g) {
+                AmpGemmItem it{};
+                it.d = q[0]; it.PA = q[1]; it.K = q[2]; it.PB = q[3]; it.ncols = off[g + 1] - off[g];
+                if (!it.ncols) continue;
+                it.T = sT.at(i) + (size_t)g * esz; it.M = has_m[i] ? sM.at(i) : nullptr; it.idx = (const int*)dIdx.p + xoff[i] + off[g]; it.R = gR.at(i);
+                gi.push_back(it);
+            }
+        }
+        const int tiles = plan_amp_gemm(gi.data(), (int)gi.size());
+        up_ints(dIdx, idx.data(), idx.size());
+        up_all(sT, sM); gR.up(R); DevItems<AmpGemmItem> dG(gi);
+        by_dtype(dtype, [&](auto t) { launch_amp_leg_gemm<decltype(t)>(nullptr, dG.get(), (int)gi.size(), tiles); });
+        HIPCHK(hipDeviceSynchronize());
+        gR.down(R, "R");
+    });
+}
+// ONE launch_amp_absorb<T> over nitems steps (PA, K, PB, nstr): in_i [PA][K][PB][nstr], m_i [K][nstr] (has_m[i] == 0: a null pointer, all ones), out_i [PA][PB][nstr]
+extern "C" int tnqs_dbg_amp_absorb(int dtype, int nitems, const int* shape, const void* in, const void* m, const int* has_m, void* out, int guard_elems) {
+    return guard([&] {
+        if (!is_dtype(dtype) || nitems < 1 || !shape || !in || !m || !has_m || !out || guard_elems < 0) throw Err(TNQS_ERR_INVALID, "dbg_amp_absorb: bad arguments");
+        const size_t esz = esz_of(dtype);
+        Slots sI, sM; Guarded gO((size_t)guard_elems * esz);
+        for (int i = 0; i < nitems; ++i) {
+            const int* q = shape + 4 * i;
+            if (q[0] < 1 || q[2] < 1 || q[3] < 1 || (long long)q[0] * q[2] > (1LL << 30) / q[3]) throw Err(TNQS_ERR_INVALID, "dbg_amp_absorb: bad shape");
+            if (!amp_covers(q[1])) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_amp_absorb: bond dimensions 1 <= K <= 64");
+            sI.add((size_t)q[0] * q[1] * q[2] * q[3] * esz); sM.add((size_t)q[1] * q[3] * esz); gO.add((size_t)q[0] * q[2] * q[3] * esz);
+        }
+        need_gpu();
+        alloc_all(sI, sM, gO);
+        put_all(sI, in); put_all(sM, m);
+        std::vector<AmpAbsorbItem> ai(nitems);
+        for (int i = 0; i < nitems; ++i) {
+            const int* q = shape + 4 * i;
+            ai[i] = AmpAbsorbItem{}; ai[i].in = sI.at(i); ai[i].m = has_m[i] ? sM.at(i) : nullptr; ai[i].out = gO.at(i); ai[i].PA = q[0]; ai[i].K = q[1]; ai[i].PB = q[2]; ai[i].nstr = q[3];
+        }
+        const int wgs = plan_amp_absorb(ai.data(), nitems);
+        up_all(sI, sM); gO.up(out); DevItems<AmpAbsorbItem> dA(ai);
+        by_dtype(dtype, [&](auto t) { launch_amp_absorb<decltype(t)>(nullptr, dA.get(), nitems, wgs); });
+        HIPCHK(hipDeviceSynchronize());
+        gO.down(out, "out");
+    });
+}
+// ONE launch_amp_finalize<T> over nitems messages of chi[i] x nstr[i]; done: one int per string, the items one after the other (null: no flags)
+extern "C" int tnqs_dbg_amp_finalize(int dtype, int nitems, const int* chi, const int* nstr, const void* raw, const void* old_msg, const int* has_old, const int* normalize,
+                                     const int* done, void* new_msg, double* diff, double* sum, int guard_elems) {
+    return guard([&] {
+        if (!is_dtype(dtype) || nitems < 1 || !chi || !nstr || !raw || !old_msg || !has_old || !normalize || !new_msg || !diff || !sum || guard_elems < 0)
+            throw Err(TNQS_ERR_INVALID, "dbg_amp_finalize: bad arguments");
+        const size_t esz = esz_of(dtype);
+        Slots sR, sOld; Guarded gN((size_t)guard_elems * esz);
+        std::vector<size_t> soff(nitems + 1, 0);
+        for (int i = 0; i < nitems; ++i) {
+            if (nstr[i] < 1) throw Err(TNQS_ERR_INVALID, "dbg_amp_finalize: nstr >= 1");
+            if (!amp_covers(chi[i])) throw Err(TNQS_ERR_UNSUPPORTED, "dbg_amp_finalize: bond dimensions 1 <= chi <= 64");
+            const size_t mb = (size_t)chi[i] * nstr[i] * esz;
+            sR.add(mb); sOld.add(mb); gN.add(mb); soff[i + 1] = soff[i] + nstr[i];
+        }
+        need_gpu();
+        alloc_all(sR, sOld, gN);
+        put_all(sR, raw); put_all(sOld, old_msg);
+        const size_t ns = soff[nitems];
+        DBuf dD(sizeof(double) * ns), dS(sizeof(double) * 2 * ns), dDone(sizeof(int) * ns);
+        dD.up(diff, sizeof(double) * ns); dS.up(sum, sizeof(double) * 2 * ns); if (done) up_ints(dDone, done, ns);
+        std::vector<AmpFinalItem> fi(nitems);
+        for (int i = 0; i < nitems; ++i) {
+            AmpFinalItem& it = fi[i]; it = AmpFinalItem{};
+            it.raw = sR.at(i); it.old_msg = has_old[i] ? sOld.at(i) : nullptr; it.new_msg = gN.at(i); it.done = done ? (const int*)dDone.p + soff[i] : nullptr;
+            it.diff_out = (double*)dD.p + soff[i]; it.sum_out = (double*)dS.p + 2 * soff[i]; it.chi = chi[i]; it.nstr = nstr[i]; it.normalize = normalize[i];
+        }
+        const int wgs = plan_amp_finalize(fi.data(), nitems);
+        up_all(sR, sOld); gN.up(new_msg); DevItems<AmpFinalItem> dF(fi);
+        by_dtype(dtype, [&](auto t) { launch_amp_finalize<decltype(t)>(nullptr, dF.get(), nitems, wgs); });
+        HIPCHK(hipDeviceSynchronize());
+        gN.down(new_msg, "new_msg");
+        dD.down(diff, sizeof(double) * ns); dS.down(sum, sizeof(double) * 2 * ns);
+    });
+}
+// tnqs_amplitudes_bp with the workspace bound given explicitly: it sizes the batches of jobs and the chunks of strings
+extern "C" int tnqs_dbg_amplitudes_bp_ws(tnqs_handle h, int nstrings, const int32_t* configs, const tnqs_bp_opts* opts, double* out_log_re_im, int32_t* niter, double* final_diff,
+                                         int32_t* flags, int64_t workspace_bytes, int* nbatches_out) {
+    return guard([&] {
+        if (workspace_bytes < 1) throw Err(TNQS_ERR_INVALID, "dbg_amplitudes_bp_ws: the workspace bound must be positive");
+        amplitudes_bp(S(h), nstrings, configs, opts, out_log_re_im, niter, final_diff, flags, (size_t)workspace_bytes, nbatches_out);
     });
 }

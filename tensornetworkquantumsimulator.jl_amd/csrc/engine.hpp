@@ -238,6 +238,10 @@ void rdm_paths(State* s, int npaths, const int32_t* path_len, const int32_t* pat
 // up to 64); out_log_re_im = log z with the imaginary part in (-pi, pi] ((-inf, 0) when a scalar is exactly zero); opts == null: maxiter 25 (1 on a tree), no tolerance,
 // default sequence; workspace_bytes: bound on the chain temporaries of a batch of messages (0: min(2 GiB, a quarter of the free device memory)); nbatches (may be null)
 void inner_bp(State* ket, State* bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff, size_t workspace_bytes = 0, int* nbatches = nullptr);
+// engine_amp.cpp: log <x|psi> of nstrings bitstrings (configs: nstrings x nv, string-major) by BP on the single-layer network T_v[x_v, ...] with vector messages that
+// start as all ones; out_log_re_im: 2 nstrings doubles; niter, final_diff, flags (may be null): per string; workspace_bytes / nbatches as inner_bp's
+void amplitudes_bp(State* s, int nstrings, const int32_t* configs, const tnqs_bp_opts* opts, double* out_log_re_im, int32_t* niter, double* final_diff, int32_t* flags,
+                   size_t workspace_bytes = 0, int* nbatches = nullptr);
 // engine_spectra.cpp: entanglement spectra of bonds (entanglement.jl:73-86): request i = (u, v) receives chi doubles, descending, summing to 1, unfiltered (null lists:
 // every edge as (src, dst)); workspace: 64 chi^2 bytes per request, all requests of a call at once
 void bond_spectra(State* s, int n_edges, const int32_t* eu, const int32_t* ev, double* out_spectra);

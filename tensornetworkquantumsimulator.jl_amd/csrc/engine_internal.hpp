@@ -14,6 +14,7 @@
 //   engine_rdm.cpp    two-site reduced density matrices of bonds (batched chains + Grams, one contraction kernel)
 //   engine_paths.cpp  two-site reduced density matrices of the ends of paths (environments, transfer matrices, the sweep along the path)
 //   engine_inner.cpp  overlap of two states: BP on the bilinear form (rectangular messages, mode products that change a leg's dimension, form scalars)
+//   engine_amp.cpp    amplitudes of a batch of bitstrings: BP on the single-layer network T_v[x_v] (vector messages per string, groups of strings per site value)
 //   engine_spectra.cpp  entanglement spectra of bonds from the two messages (batched eigen problems, one read-back)
 //   sharding.cpp      exchange step (RCCL or host callback)
 //   api.cpp           the extern "C" boundary of include/tnqs.h (api_guard.hpp: the exception guard every entry point runs in)
@@ -29,6 +30,7 @@
 //   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, antiprojector, trace
 //   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs), environment through a transfer matrix (path RDMs)
 //   kernels_inner.hip  overlap of two states: rectangular two-operand Gram (f32 / f64 matrix cores), bilinear message epilogue, form scalars
+//   kernels_amp.hip    bitstring amplitudes: strided-slice GEMM over groups of strings (f32 / f64 matrix cores), per-string vector absorption, epilogue, scalars
 //   kernels_spectrum.hip  bond entanglement spectra: W = D V^dagger m1^T V D from a message's eigen factorisation, signed sorted spectrum
 #pragma once
 #include "engine.hpp"

@@ -392,6 +392,31 @@ template <class T> void launch_inner_finalize(hipStream_t s, const InnerFinalIte
 // rawsum when that pointer is set, normalize != 0 and the number is not exactly zero (m = raw / sum(raw): the product is then sum_ab raw[a, b] mr[a, b]), else 1
 struct InnerScalarItem { const void* m; const void* mr; int rows, cols; const double* rawsum; int normalize; const double* scale_a; const double* scale_b; double* out; };
 template <class T> void launch_inner_scalar(hipStream_t s, const InnerScalarItem* d_items, int nitems);
+// ---- bitstring amplitudes (kernels_amp.hip; engine_amp.cpp): BP on the single-layer network A_v = T_v[x_v, ...] for a batch of strings, vector messages [chi][string] -------
+// first absorption of a message over the strings of one GROUP (the strings whose site value selects the slice T points at): for column n of the group, p = idx[n] the
+// string's position in the chunk, R[(a + PA b') + PA PB p] = sum_k T[d (a + PA (k + K b'))] M[k + K p] (M null: all ones).  1 <= K <= 64; a workgroup owns 64 rows x 64 columns
+struct AmpGemmItem { const void* T; const void* M; const int* idx; void* R; int d, PA, K, PB, ncols; int tile_begin, ntr, ntc; };
+inline bool amp_covers(int K) { return K >= 1 && K <= 64; }
+int plan_amp_gemm(AmpGemmItem* it, int n);      // sets ntr, ntc, tile_begin; returns the launch's workgroups
+template <class T> void launch_amp_leg_gemm(hipStream_t s, const AmpGemmItem* d_items, int nitems, int total_tiles);
+// a further leg, every string with its own vector: out[a + PA (b' + PB p)] = sum_k in[a + PA (k + K (b' + PB p))] m[k + K p] (m null: all ones), k ascending, p < nstr
+struct AmpAbsorbItem { const void* in; const void* m; void* out; int PA, K, PB, nstr; int wg_begin; };
+int plan_amp_absorb(AmpAbsorbItem* it, int n);
+template <class T> void launch_amp_absorb(hipStream_t s, const AmpAbsorbItem* d_items, int nitems, int total_wgs);
+// epilogue of a message for the nstr strings of a chunk (one wave per string, chi <= 64): raw[k + chi p] -> sum_out[2 p], [2 p + 1] = the raw element sum (f64);
+// new_msg[k + chi p] = raw / sum when normalize != 0 and the sum is not exactly zero; diff_out[p] = message_diff against old_msg (null: all ones).  A string whose done flag
+// is set gets nothing stored: its old message is carried over bit for bit where new_msg is another buffer.  old_msg, new_msg, done, diff_out, sum_out start at the chunk
+struct AmpFinalItem { const void* raw; const void* old_msg; void* new_msg; const int* done; double* diff_out; double* sum_out; int chi, nstr, normalize; int wg_begin; };
+int plan_amp_finalize(AmpFinalItem* it, int n);
+template <class T> void launch_amp_finalize(hipStream_t s, const AmpFinalItem* d_items, int nitems, int total_wgs);
+// end of a sweep, per string that is not done: avg = sum_t diffs[t nstrings + n] / nseq (t ascending), niter[n] = iter, fdiff[n] = avg, done[n] = (tol >= 0 && avg <= tol)
+void launch_amp_sweep_end(hipStream_t s, const double* diffs, int nseq, int nstrings, int iter, double tol, int* done, int* niter, double* fdiff);
+// the scalars of one string n in f64 (one wave per string): item i < nv a vertex, the rest edges.  value = sum_k m[k + chi n] mr[k + chi n] (null: ones), times the complex
+// number at rawsum + 2 n when rawsum is set, normalize != 0 and the number is not zero, times *scale; site set: the entry site[cfg[n ld + vertex]] of a vertex without
+// neighbours instead of the sum.  out[2 n] = sum of the vertices' complex logs minus the edges', imaginary part in (-pi, pi]; flags[n] bit 0: a scalar exactly zero
+// (out = -inf, 0), bit 1: a scalar not finite (out = NaN, NaN)
+struct AmpScalarItem { const void* m; const void* mr; const double* rawsum; const double* scale; const void* site; int chi, normalize, vertex; };
+template <class T> void launch_amp_scalar(hipStream_t s, const AmpScalarItem* d_items, int nv, int ne, const int* cfg, int ld, int nstrings, double* out, int* flags);
 // one-site gates on d = 2, ComplexF32: streaming 2x2 apply, norm partials [item][nbx]
 void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int nbx, double* d_norm_partials);
 
