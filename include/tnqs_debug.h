@@ -69,6 +69,29 @@ int tnqs_dbg_pair16(int d, int nitems, const int* z, const int* chi, const int* 
  * conj(Y_i[.. d' on lx ..]); both[i] == 0: the single-message form (My = NULL, no partial_x; out_x[i] untouched) */
 int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const int* both, const void* X, const void* Y, const void* M,
                            void* out_y, void* out_x, int spw);
+/* ---- the chi = 32 plane kernels as the engine launches them (engine_bp.cpp launch_products / launch_plane_grams, engine_batch.cpp run_chains): ONE launch over nitems
+ * items of different geometry, planned by the engine's plan_* function and launched by its launch_* function.  ComplexF32 only.  Item i is a site tensor
+ * [d][chi_0]..[chi_{z[i]-1}] (chi: the items' dimensions one after the other) with the plane (lx[i], ly[i]) of two 32-dimensional legs; the items' arrays are passed one
+ * after the other and every sub-array starts at a multiple of 256 bytes on the device.  M: (Mx, My) per item, 2 x 1024 complex64, M[i + 32 j].  spw <= 0: the plan
+ * function's own rule, else that many slices per workgroup (any positive value up to 65536).  A shape pair_geometry does not cover -- a plane leg that is not
+ * 32-dimensional, lx == ly, a lower plane leg above 8 elements without a companion leg, a site that needs a fourth slice counter -- is refused with
+ * TNQS_ERR_UNSUPPORTED and nothing is written.  Optional outputs (each may be NULL): *route_out = TNQS_DBG_ROUTE_X3 or TNQS_DBG_ROUTE_F32 (TNQS_NO_BF16X3=1), *spw_out =
+ * the slices per workgroup the plan chose, wg_begin_out[i] / nwg_out[i] = item i's first workgroup and its workgroups (= its partials per message), *total_wgs_out.
+ * in == NULL (pair32) / X == NULL (pair_gram32): HOST ONLY, these outputs alone are filled and no device is touched (tests/test_plane32_ref_cpu.py).
+ * tnqs_dbg_pair32: plan_pair + launch_mfma_pair (x3_pair_kernel / mfma_pair_kernel): out_i = in_i x_lx Mx_i x_ly My_i.  out holds `guard` elements, item 0, `guard`
+ * elements, item 1, ..., `guard` elements; it goes up as the caller filled it and comes back whole */
+int tnqs_dbg_pair32(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const void* in, const void* M, void* out, int spw, int guard,
+                    int* route_out, int* spw_out, int* wg_begin_out, int* nwg_out, int* total_wgs_out);
+/* one pair-Gram launch of one form (the engine launches doubles and singles separately), then launch_reduce<float, float> over every item's nwg[i] partials per message.
+ * form 0, both messages: plan_pair_gram2 + launch_mfma_pair_gram2 (x3_pair_gram2_kernel<false> / mfma_pair_gram2_kernel); out_y[i] (1024 complex64, b + 32 b') =
+ * sum (X_i x_lx Mx)[.. b on ly ..] conj(Y_i[.. b' on ly ..]), out_x[i] = sum (X_i x_ly My)[.. d on lx ..] conj(Y_i[.. d' on lx ..]).
+ * form 1, one message, on the route launch_plane_grams takes: plan_x3_pair_gram1 + launch_x3_pair_gram1 (x3_pair_gram2_kernel<true>, My = partial_x = null), under
+ * TNQS_NO_BF16X3=1 plan_pair_gram + launch_mfma_pair_gram (mfma_pair_gram_kernel); Mx alone is read, out_y alone is written, out_x (may be NULL) is not touched.
+ * The partial arrays live in one device buffer laid out as guard band, item 0's partials, guard band, ..., guard band, filled with 0xff bytes (an f32 NaN) before the
+ * launch: a partial nobody wrote makes the item's sum NaN, a touched band is an error return.  out_y / out_x: guard, item 0 (1024 complex64), guard, ..., guard, up as
+ * filled and back whole */
+int tnqs_dbg_pair_gram32(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, int form, const void* X, const void* Y, const void* M,
+                         void* out_y, void* out_x, int spw, int guard, int* route_out, int* spw_out, int* wg_begin_out, int* nwg_out, int* total_wgs_out);
 /* the tall route of the ComplexF32 theta SVD (Cholesky-QR preprocessing, Jacobi on R, A J, polishing sweeps where the pivot collapsed) on nitems matrices
  * A_i (m[i] x n[i], 2 <= n <= 128, n <= m <= 512): A_i <- U Sigma (columns); chol_fail[i]: a Cholesky pivot was refused; polished[i]: the polishing sweeps
  * ran on the item; sweeps[i]: sweeps of the Jacobi on R (each output array may be NULL).  (m > 256 is where svd_batch sends a ComplexF32 theta of more than 256 rows whose

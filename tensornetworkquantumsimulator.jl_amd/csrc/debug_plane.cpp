@@ -307,3 +307,107 @@ extern "C" int tnqs_dbg_pair_gram2x16(int d, int nitems, const int* z, const int
         if (out_x) for (int i = 0; i < nitems; ++i) if (both[i]) HIPCHK(hipMemcpy((char*)out_x + (size_t)i * 256 * 8, (char*)dO.p + ((size_t)nitems + i) * 256 * 8, 256 * 8, hipMemcpyDeviceToHost));
     });
 }
+
+namespace {
+// chi = 32 planes: item i is a site tensor [d][chi_0]..[chi_{z[i]-1}] (chi: the items' dimensions one after the other) with the plane (lx[i], ly[i]); n[i] = its elements
+void pair32_geoms(const char* who, int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, int spw, int guard_elems, std::vector<PairGeom>& g,
+                  std::vector<size_t>& n) {
+    if (nitems < 1 || !z || !chi || !lx || !ly || d < 1 || guard_elems < 0 || spw > (1 << 16)) throw Err(TNQS_ERR_INVALID, std::string(who) + ": bad arguments");
+    g.resize(nitems); n.resize(nitems);
+    int c = 0;
+    for (int i = 0; i < nitems; ++i) {
+        if (z[i] < 2 || z[i] > 8) throw Err(TNQS_ERR_INVALID, std::string(who) + ": 2 <= z <= 8");
+        n[i] = d;
+        for (int k = 0; k < z[i]; ++k) { if (chi[c + k] < 1 || chi[c + k] > 1024) throw Err(TNQS_ERR_INVALID, std::string(who) + ": 1 <= chi <= 1024"); n[i] *= chi[c + k]; }
+        if (!pair_geometry(d, z[i], chi + c, lx[i], ly[i], g[i]) || (size_t)g[i].n0 * g[i].n1 * g[i].n2 * 16 * 1024 != n[i])
+            throw Err(TNQS_ERR_UNSUPPORTED, std::string(who) + ": shape not covered by the chi = 32 plane kernels");
+        c += z[i];
+    }
+}
+// what a plan_* function decided, for the caller: the launch's spw, every item's first workgroup and workgroups, the total
+template <class Item> void plan_report(const std::vector<Item>& items, int Item::*begin, int total, int* spw_out, int* wg_begin_out, int* nwg_out, int* total_wgs_out) {
+    const int n = (int)items.size();
+    if (spw_out) *spw_out = items[0].spw;
+    for (int i = 0; i < n; ++i) {
+        if (wg_begin_out) wg_begin_out[i] = items[i].*begin;
+        if (nwg_out) nwg_out[i] = (i + 1 < n ? items[i + 1].*begin : total) - items[i].*begin;
+    }
+    if (total_wgs_out) *total_wgs_out = total;
+}
+}  // namespace
+// ONE launch_mfma_pair over nitems items planned by plan_pair (x3_pair_kernel, mfma_pair_kernel under TNQS_NO_BF16X3=1): out_i = in_i x_lx Mx_i x_ly My_i
+extern "C" int tnqs_dbg_pair32(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, const void* in, const void* M, void* out, int spw, int guard_elems,
+                               int* route, int* spw_out, int* wg_begin_out, int* nwg_out, int* total_wgs_out) {
+    return guard([&] {
+        std::vector<PairGeom> g; std::vector<size_t> n;
+        pair32_geoms("dbg_pair32", d, nitems, z, chi, lx, ly, spw, guard_elems, g, n);
+        if (in && (!M || !out)) throw Err(TNQS_ERR_INVALID, "dbg_pair32: bad arguments");
+        std::vector<PairItem> items(nitems);
+        for (int i = 0; i < nitems; ++i) { items[i] = PairItem{}; items[i].g = g[i]; }
+        const int wgs = plan_pair(items.data(), nitems, spw);
+        plan_report(items, &PairItem::slice_begin, wgs, spw_out, wg_begin_out, nwg_out, total_wgs_out);
+        if (route) *route = mfma_use_x3() ? TNQS_DBG_ROUTE_X3 : TNQS_DBG_ROUTE_F32;
+        if (!in) return;
+        need_gpu();
+        Slots sIn, sM; Guarded gO((size_t)guard_elems * 8);
+        for (int i = 0; i < nitems; ++i) { sIn.add(n[i] * 8); sM.add(2 * 1024 * 8); gO.add(n[i] * 8); }
+        alloc_all(sIn, sM, gO); put_all(sIn, in); put_all(sM, M);
+        for (int i = 0; i < nitems; ++i) { PairItem& it = items[i]; it.in = sIn.at(i); it.out = gO.at(i); it.Mx = sM.at(i); it.My = sM.at(i) + 1024 * 8; }
+        DevItems<PairItem> dI(items);
+        up_all(sIn, sM); gO.up(out);
+        launch_mfma_pair(nullptr, dI.get(), nitems, wgs);
+        HIPCHK(hipDeviceSynchronize());
+        gO.down(out, "out");
+    });
+}
+// ONE pair-Gram launch of one form over nitems items, then launch_reduce over every item's partials.  form 0: both messages (plan_pair_gram2, launch_mfma_pair_gram2);
+// form 1: one message, on the route launch_plane_grams takes (plan_x3_pair_gram1 / launch_x3_pair_gram1, under TNQS_NO_BF16X3=1 plan_pair_gram / launch_mfma_pair_gram)
+extern "C" int tnqs_dbg_pair_gram32(int d, int nitems, const int* z, const int* chi, const int* lx, const int* ly, int form, const void* X, const void* Y, const void* M,
+                                    void* out_y, void* out_x, int spw, int guard_elems, int* route, int* spw_out, int* wg_begin_out, int* nwg_out, int* total_wgs_out) {
+    return guard([&] {
+        std::vector<PairGeom> g; std::vector<size_t> n;
+        pair32_geoms("dbg_pair_gram32", d, nitems, z, chi, lx, ly, spw, guard_elems, g, n);
+        if ((form != 0 && form != 1) || (X && (!Y || !M || !out_y || (form == 0 && !out_x)))) throw Err(TNQS_ERR_INVALID, "dbg_pair_gram32: bad arguments");
+        const bool x3 = mfma_use_x3(), f32_single = form == 1 && !x3;
+        std::vector<PairGram2Item> two(nitems); std::vector<PairGramItem> one(f32_single ? nitems : 0);      // one: the items of mfma_pair_gram_kernel
+        std::vector<int> nwg(nitems); int wgs = 0;
+        for (int i = 0; i < nitems; ++i) { two[i] = PairGram2Item{}; two[i].g = g[i]; if (f32_single) { one[i] = PairGramItem{}; one[i].g = g[i]; } }
+        if (form == 0) wgs = plan_pair_gram2(two.data(), nitems, nwg.data(), spw);
+        else if (x3) wgs = plan_x3_pair_gram1(two.data(), nitems, nwg.data(), spw);
+        else wgs = plan_pair_gram(one.data(), nitems, nwg.data(), spw);
+        if (f32_single) plan_report(one, &PairGramItem::wg_begin, wgs, spw_out, wg_begin_out, nwg_out, total_wgs_out);
+        else plan_report(two, &PairGram2Item::wg_begin, wgs, spw_out, wg_begin_out, nwg_out, total_wgs_out);
+        if (route) *route = x3 ? TNQS_DBG_ROUTE_X3 : TNQS_DBG_ROUTE_F32;
+        if (!X) return;
+        need_gpu();
+        const size_t band = 256, pb = 1024 * 8;        // guard band behind every partial array (and in front of the first), 0xff like the partials themselves
+        const int nmsg = form == 0 ? 2 : 1;
+        Slots sX, sY, sM, sP(band); Guarded gOy((size_t)guard_elems * 8), gOx((size_t)guard_elems * 8);
+        for (int i = 0; i < nitems; ++i) {
+            sX.add(n[i] * 8); sY.add(n[i] * 8); sM.add(2 * pb); gOy.add(pb); gOx.add(pb);
+            for (int m = 0; m < nmsg; ++m) sP.add((size_t)nwg[i] * pb);
+        }
+        alloc_all(sX, sY, sM, sP, gOy); put_all(sX, X); put_all(sY, Y); put_all(sM, M);
+        if (form == 0) gOx.alloc();
+        std::vector<ReduceItem> ri;
+        for (int i = 0; i < nitems; ++i) {
+            void* py = sP.at((size_t)nmsg * i); void* px = form == 0 ? sP.at((size_t)nmsg * i + 1) : nullptr;
+            if (f32_single) { PairGramItem& it = one[i]; it.X = sX.at(i); it.Y = sY.at(i); it.M = sM.at(i); it.partial = py; }
+            else { PairGram2Item& it = two[i]; it.X = sX.at(i); it.Y = sY.at(i); it.Mx = sM.at(i); it.My = form == 0 ? sM.at(i) + pb : nullptr; it.partial_y = py; it.partial_x = px; }
+            ri.push_back(ReduceItem{py, gOy.at(i), 1024, nwg[i], 0, (int)ri.size() * 1024});
+            if (form == 0) ri.push_back(ReduceItem{px, gOx.at(i), 1024, nwg[i], 0, (int)ri.size() * 1024});
+        }
+        DevItems<PairGram2Item> dTwo(two); DevItems<PairGramItem> dOne(one); DevItems<ReduceItem> dR(ri);
+        up_all(sX, sY, sM, sP); gOy.up(out_y); if (form == 0) gOx.up(out_x);
+        if (form == 0) launch_mfma_pair_gram2(nullptr, dTwo.get(), nitems, wgs);
+        else if (x3) launch_x3_pair_gram1(nullptr, dTwo.get(), nitems, wgs);
+        else launch_mfma_pair_gram(nullptr, dOne.get(), nitems, wgs);
+        launch_reduce<float, float>(nullptr, dR.get(), (int)ri.size(), (int)ri.size() * 1024);
+        HIPCHK(hipDeviceSynchronize());
+        sP.down("the pair-Gram partials");
+        auto untouched = [&](size_t b0, size_t b1) { for (size_t b = b0; b < b1; ++b) if (sP.host[b] != (char)0xff) throw Err(TNQS_ERR_INVALID, "dbg: a kernel wrote outside an item of the pair-Gram partials"); };
+        untouched(0, band);
+        for (size_t k = 0; k < sP.off.size(); ++k) untouched(sP.off[k] + sP.len[k], sP.off[k] + sP.len[k] + band);
+        gOy.down(out_y, "out_y"); if (form == 0) gOx.down(out_x, "out_x");
+    });
+}
