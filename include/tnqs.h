@@ -271,6 +271,18 @@ int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uin
  * still run on its own (its allocation may then fail with TNQS_ERR_HIP).
  * TNQS_ERR_INVALID: a list that is not a cycle of the graph; TNQS_ERR_UNSUPPORTED: sharded handles, vertex degree > 7. */
 int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im);
+/* The same quantity for connected leafless configurations given as EDGE lists, with at most two independent loops (|E| - |V| <= 1): simple cycles, thetas (two
+ * vertices of internal degree 3 joined by three chains), dumbbells (two such vertices, each carrying a closed chain, joined by a bridge) and figure-eights (one vertex
+ * of internal degree 4 carrying two closed chains).  Configuration c has config_nedges[c] edges (edge_u[i], edge_v[i]), the lists one after the other;
+ * out_re_im[2c, 2c+1] = W(c): the double-layer tensors of its vertices, the cache's messages on every leg that leaves it, the antiprojector on every edge of it.
+ * Order and orientation of the edges do not matter: the list is put into a canonical form first.  A simple cycle is handed to the code of tnqs_loop_weights as the
+ * ring that starts at its lowest vertex and goes on to the lower of that vertex's two ring neighbours (bit-identical to that call).
+ * Precondition, pending gates and scales, unset messages and batching as for tnqs_loop_weights; the workspace of every configuration is computed before anything is
+ * allocated.  nconfigs = 0 is allowed.
+ * TNQS_ERR_INVALID: an edge that is not in the graph, a repeated edge, a disconnected set, a vertex of internal degree 1, null pointers with nconfigs > 0;
+ * TNQS_ERR_UNSUPPORTED: more than two independent loops, sharded handles, vertex degree > 7, a configuration whose workspace exceeds the free device memory, the bytes the
+ * handle's own pool holds from earlier calls counted as free (the message names the bytes). */
+int tnqs_config_weights(tnqs_handle h, int nconfigs, const int32_t* config_nedges, const int32_t* edge_u, const int32_t* edge_v, double* out_re_im);
 
 /* ---- overlap of two states ---------------------------------------------------------------------------------------
  * inner(psi, phi; alg = "bp") (src/inner.jl:65-69): BP on BilinearForm(ket, bra).  out_log_re_im = the reference's freenergy
@@ -349,7 +361,7 @@ enum { TNQS_PROF_BP_MODEPROD = 0, TNQS_PROF_BP_GRAM = 1, TNQS_PROF_GATE_MODEPROD
        /* whole phases, first to last kernel on the handle's stream (side streams join it before a phase ends): the CRITICAL-PATH time of the BP updates (launches =
         * sweeps) and of the batches of two-site gates (launches = batches) -- the kernel classes above overlap each other where a phase runs on two streams */
        TNQS_PROF_PHASE_BP_UPDATE = 10, TNQS_PROF_PHASE_GATE_BATCH = 11,
-       /* every launch of tnqs_loop_weights; flops: 8 m n k per complex product of the batched GEMM */
+       /* every launch of tnqs_loop_weights and tnqs_config_weights; flops: 8 m n k per complex product of the batched GEMM */
        TNQS_PROF_LOOP = 12,
        /* the bond-contraction kernel of tnqs_rdm_edges (its chains and Grams are booked under TNQS_PROF_SMALL, as the one-site probe's); bytes: Gram partials read + matrices
         * written, flops: 8 chi^2 (d_u d_v)^2 per bond */

@@ -144,6 +144,11 @@ int tnqs_dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m, const int*
 int tnqs_dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* T_inout, const void* f, const void* b);
 /* loop_trace_kernel<T> + its tail: out[i] (complex128) = sum_ab X_i[a,b] Y_i[b,a], X_i p[i] x q[i], Y_i q[i] x p[i] */
 int tnqs_dbg_loop_trace(int dtype, int nitems, const int* p, const int* q, const void* X, const void* Y, double* out_re_im);
+/* loop_branch_gram_kernel<T>, ONE launch: item i has three legs of dimensions dims[3 i .. 3 i + 2] = (x_0, x_1, x_2) and a contraction length k[i];
+ * A_i, B_i are (x_0 x_1 x_2) x k[i], rows i_0 + x_0 (i_1 + x_0 x_1 ... ) i.e. leg 0 fastest.  C_i[(l_p0, l_p0'), (l_p1, l_p1'), (l_p2, l_p2')] = sum_kk A_i[l, kk] conj(B_i[l', kk]),
+ * every pair (ket, bra) interleaved with the ket index faster, the pairs in the order p = order[3 i .. 3 i + 2] (a permutation of 0, 1, 2; order = NULL: 0, 1, 2).
+ * C holds guard bands as for tnqs_dbg_loop_cgemm. */
+int tnqs_dbg_loop_branch_gram(int dtype, int nitems, const int* dims, const int* order, const int* k, const void* A, const void* B, void* C, int guard);
 /* ---- the kernels that post-process a BP cache and prepare a gate's environments (dtype 0 c64 = T float, 1 c128 = T double; column-major n x n matrices).  ONE launch
  * over nitems items of different n, descriptors filled as the engine fills them; on the device every array of every item starts at a multiple of 256 bytes.  Input
  * arrays hold the items' matrices one after the other (a slot for every item, read only where its `present` flag is not 0 -- 0 hands the kernel a null pointer, i.e.

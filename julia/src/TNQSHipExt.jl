@@ -483,6 +483,19 @@ function Adapt.adapt_structure(::Type{Array}, c::HipBeliefPropagationCache)     
     return b
 end
 
+# ---- loop corrections: weight(bpc, eg) (src/MessagePassing/loopcorrection.jl:79-89) of connected leafless configurations with at most two independent loops --
+# simple cycles, thetas, dumbbells, figure-eights -- in one call (tnqs_config_weights).  `configs`: vectors of edges; the cache must be rescaled (rescale!)
+# for these to be the weights of loopcorrected_partitionfunction.  Three or more independent loops: an error (TNQS_ERR_UNSUPPORTED)
+function configuration_weights(c::HipBeliefPropagationCache, configs::Vector{<:Vector{<:NamedGraphs.AbstractEdge}})
+    n = Int32[length(cfg) for cfg in configs]
+    eu = Int32[c.vid[src(e)] for cfg in configs for e in cfg]
+    ev = Int32[c.vid[dst(e)] for cfg in configs for e in cfg]
+    out = zeros(ComplexF64, length(configs))
+    GC.@preserve n eu ev out check(ccall((:tnqs_config_weights, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                                         c.handle, length(configs), n, eu, ev, out))
+    return out
+end
+
 # ---- multi-GPU: one Julia process per GPU, RCCL inside the library (tnqs_set_sharding_rccl, include/tnqs.h:188-202) -------------------
 # `bcast128` must hand rank 0's 128-byte id to every rank (with MPI.jl: id -> MPI.Bcast!(id, 0, comm)); `allmin` must return the minimum of
 # an Int over the ranks (MPI.Allreduce(x, MPI.MIN, comm)).  Every rank runs the local preflight first and the ranks agree on it, so that no

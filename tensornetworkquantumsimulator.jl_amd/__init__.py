@@ -9,7 +9,7 @@ from .core import (TensorNetworkState, tensornetworkstate, random_tensornetworks
                    scalartype, maxvirtualdim, default_bp_update_kwargs, default_tolerance, update, apply_gates,
                    apply_circuit, truncate, expect, expect_all, expect_edges, rdm, rdm_edges, rdm_paths, rdm_pairs, expect_pairs, correlation_function, vertex_scalars, edge_scalars, freenergy, partitionfunction,
                    rescale, rescale_messages, rescale_vertices, normalize, symmetric_gauge, symmetrize_and_normalize, sample, sample_with_probabilities, site_probabilities,
-                   loopcorrected_partitionfunction, loop_weights, norm_sqr, norm, inner, log_inner, log_amplitudes, amplitudes, log_probabilities,
+                   loopcorrected_partitionfunction, loop_weights, configuration_weights, norm_sqr, norm, inner, log_inner, log_amplitudes, amplitudes, log_probabilities,
                    bond_spectra, bond_entropies, renyi_entropy, von_neumann_entanglement_entropy, second_renyi_entanglement_entropy,
                    profile_enable, profile_get, profile_reset,
                    PROF_CLASSES)

@@ -109,6 +109,7 @@ _SIGS = {
     "tnqs_site_probabilities": ([H, C.c_int, _DP], C.c_int),
     "tnqs_sample_bp": ([H, C.c_int, C.POINTER(BpOpts), C.c_uint64, _DP, _I32P, _DP, C.POINTER(ApplyStats)], C.c_int),
     "tnqs_loop_weights": ([H, C.c_int, _I32P, _I32P, _DP], C.c_int),
+    "tnqs_config_weights": ([H, C.c_int, _I32P, _I32P, _I32P, _DP], C.c_int),
     "tnqs_set_sharding": ([H, C.c_int, C.c_int, _I32P, ALLGATHER_FN, C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
     "tnqs_rccl_unique_id": ([C.c_void_p], C.c_int),
     "tnqs_set_sharding_rccl": ([H, C.c_int, C.c_int, _I32P, C.c_void_p, C.c_int64], C.c_int),

@@ -1045,6 +1045,34 @@ def loop_weights(bpc: BeliefPropagationCache, cycles) -> np.ndarray:
     return out
 
 
+def configuration_weights(bpc: BeliefPropagationCache, configurations) -> np.ndarray:
+    """W(c) of connected leafless configurations (lists of edges) with at most two independent loops -- simple cycles, thetas, dumbbells, figure-eights -- on the
+    device, in one call (tnqs_config_weights); `bpc` must be rescaled for these to be the weights of the loop series.  Order and orientation of a
+    configuration's edges do not matter.  Three or more independent loops: TnqsError (unsupported)."""
+    g = bpc.graph
+    configurations = [list(c) for c in configurations]
+    out = np.zeros(len(configurations), dtype=np.complex128)
+    try:
+        eu = [g.index[a] for c in configurations for (a, b) in c]
+        ev = [g.index[b] for c in configurations for (a, b) in c]
+    except KeyError as e:
+        raise L.TnqsArgumentError(f"configuration_weights: {e.args[0]!r} is not a vertex of the graph") from None
+    ln, lnp = L.i32([len(c) for c in configurations] or [0])
+    us, usp = L.i32(eu or [0])
+    vs, vsp = L.i32(ev or [0])
+    L.check(L.lib.tnqs_config_weights(bpc._h, len(configurations), lnp, usp, vsp, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def _independent_loops(edges) -> int:
+    return len(edges) - len({v for e in edges for v in e}) + 1
+
+
+def _check_branched(branched, who: str):
+    if branched not in ("host", "device"):
+        raise L.TnqsArgumentError(f'{who}: branched must be "host" or "device" (received {branched!r})')
+
+
 def _cycle_order(edges):
     """the vertices of a simple cycle, given as its edge set, in ring order (None: some vertex has another degree than 2)"""
     nb: Dict = {}
@@ -1138,11 +1166,14 @@ def _host_weight(bpc: BeliefPropagationCache, edges) -> complex:
     return complex(np.einsum(*real, [], optimize=["einsum_path"] + list(path)))
 
 
-def loopcorrected_partitionfunction(bpc: BeliefPropagationCache, max_configuration_size: int, connected_only: bool = False) -> complex:
+def loopcorrected_partitionfunction(bpc: BeliefPropagationCache, max_configuration_size: int, connected_only: bool = False, branched: str = "host") -> complex:
     """loopcorrected_partitionfunction (loopcorrection.jl:3-14): Z_bp (1 + sum_c W(c)) over the leafless edge-induced subgraphs c of at most
     `max_configuration_size` edges, on a rescaled copy of the cache.  A disconnected configuration weighs the product of its components' weights
     (`connected_only` leaves those out: DESIGN.md section 5 on what the reference's enumeration is not pinned to).  Simple cycles are weighed on the
-    device in one call; a connected configuration with a vertex of internal degree >= 3 is contracted on the host (_host_weight)."""
+    device in one call; a connected configuration with a vertex of internal degree >= 3 is contracted on the host (_host_weight) -- or, with
+    branched = "device", on the device together with the cycles (configuration_weights) when it has two independent loops; components with three or more
+    independent loops stay on the host path with its limit."""
+    _check_branched(branched, "loopcorrected_partitionfunction")
     zbp = partitionfunction(bpc)
     configs = leafless_edge_induced_subgraphs(bpc.graph, max_configuration_size, connected_only=connected_only)
     if not configs:
@@ -1151,7 +1182,13 @@ def loopcorrected_partitionfunction(bpc: BeliefPropagationCache, max_configurati
     parts = [connected_edge_components(c) for c in configs]
     weight: Dict = {}
     cycles, keys = [], []
-    for comp in dict.fromkeys(c for p in parts for c in p):
+    comps = list(dict.fromkeys(c for p in parts for c in p))
+    if branched == "device":
+        on_device = [c for c in comps if _independent_loops(c) <= 2]
+        for k, w in zip(on_device, configuration_weights(r, on_device) if on_device else []):
+            weight[k] = complex(w)
+        comps = [c for c in comps if c not in weight]
+    for comp in comps:
         ring = _cycle_order(comp)
         if ring is None:
             weight[comp] = _host_weight(r, comp)
@@ -1164,9 +1201,12 @@ def loopcorrected_partitionfunction(bpc: BeliefPropagationCache, max_configurati
     return zbp * (1 + total)
 
 
-def norm_sqr(x, alg: str, max_configuration_size: Optional[int] = None, cache_update_kwargs: Optional[dict] = None, device: int = 0) -> complex:
+def norm_sqr(x, alg: str, max_configuration_size: Optional[int] = None, cache_update_kwargs: Optional[dict] = None, device: int = 0,
+             branched: str = "host") -> complex:
     """norm_sqr(psi; alg) (src/norm_sqr.jl:10-18,62-78) for alg = "bp" and "loopcorrections".  x: a TensorNetworkState (a cache is built and
-    updated with cache_update_kwargs, default default_bp_update_kwargs, on `device`) or an updated BeliefPropagationCache (which stays on its own device: `device` is not used)."""
+    updated with cache_update_kwargs, default default_bp_update_kwargs, on `device`) or an updated BeliefPropagationCache (which stays on its own device: `device` is not used).
+    branched ("host" / "device"): where loopcorrected_partitionfunction weighs configurations with two independent loops."""
+    _check_branched(branched, "norm_sqr")
     if alg not in ("bp", "loopcorrections"):
         raise L.TnqsError(f'norm_sqr: algorithm choice not supported; supported on the HIP path: "bp" and "loopcorrections" (received {alg!r})')
     if alg == "loopcorrections" and max_configuration_size is None:
@@ -1180,11 +1220,11 @@ def norm_sqr(x, alg: str, max_configuration_size: Optional[int] = None, cache_up
         raise TypeError("norm_sqr: expected a TensorNetworkState or a BeliefPropagationCache")
     if alg == "bp":
         return partitionfunction(bpc)
-    return loopcorrected_partitionfunction(bpc, int(max_configuration_size))
+    return loopcorrected_partitionfunction(bpc, int(max_configuration_size), branched=branched)
 
 
 def norm(x, alg: str, **kwargs) -> complex:
-    """norm = sqrt(norm_sqr) (src/norm_sqr.jl:80-81)"""
+    """norm = sqrt(norm_sqr) (src/norm_sqr.jl:80-81); every keyword of norm_sqr, `branched` included"""
     return complex(np.sqrt(complex(norm_sqr(x, alg, **kwargs))))
 
 
@@ -1385,7 +1425,7 @@ def profile_enable(bpc: BeliefPropagationCache, on: bool = True):
 PROF_CLASSES = ("bp_modeprod", "bp_gram", "gate_modeprod", "gate_gram", "gate_apply", "jacobi", "small", "bp_fused", "bp_pair", "bp_pairgram",
                 # whole phases on the handle's stream (critical path; the kernel classes above overlap where a phase uses two streams): launches = sweeps / batches
                 "phase_bp_update", "phase_gate_batch",
-                # every launch of tnqs_loop_weights (loopcorrected_partitionfunction); flops = 8 m n k per complex product of the batched GEMM
+                # every launch of tnqs_loop_weights and tnqs_config_weights (loopcorrected_partitionfunction); flops = 8 m n k per complex product of the batched GEMM
                 "loop",
                 # the bond-contraction kernel of tnqs_rdm_edges (rdm_edges / expect_edges); its chains and Grams are booked under "small"
                 "edge_rdm",

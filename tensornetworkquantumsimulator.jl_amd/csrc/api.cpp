@@ -125,6 +125,9 @@ int tnqs_sample_bp(tnqs_handle h, int nsamples, const tnqs_bp_opts* bp_opts, uin
 int tnqs_loop_weights(tnqs_handle h, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im) {
     return guard([&] { loop_weights(S(h), ncycles, cycle_len, cycle_verts, out_re_im); });
 }
+int tnqs_config_weights(tnqs_handle h, int nconfigs, const int32_t* config_nedges, const int32_t* edge_u, const int32_t* edge_v, double* out_re_im) {
+    return guard([&] { config_weights(S(h), nconfigs, config_nedges, edge_u, edge_v, out_re_im); });
+}
 int tnqs_rdm_edges(tnqs_handle h, int n_edges, const int32_t* edge_u, const int32_t* edge_v, double* out_rho) {
     return guard([&] { rdm_edges(S(h), n_edges, edge_u, edge_v, out_rho); });
 }

@@ -31,6 +31,32 @@ extern "C" int tnqs_dbg_loop_cgemm(int dtype, int opB, int nitems, const int* m,
         dC.down(C, nc * esz);
     });
 }
+// C_i[(l_p0, l_p0'), (l_p1, l_p1'), (l_p2, l_p2')] = sum_kk A_i[l, kk] conj(B_i[l', kk]); the item is the one the engine builds (branch_gram_item)
+extern "C" int tnqs_dbg_loop_branch_gram(int dtype, int nitems, const int* dims, const int* order, const int* k, const void* A, const void* B, void* C, int guard_elems) {
+    return guard([&] {
+        need_gpu();
+        if (!is_dtype(dtype) || nitems < 1 || !dims || !k || !A || !B || !C || guard_elems < 0) throw Err(TNQS_ERR_INVALID, "dbg_loop_branch_gram: bad arguments");
+        const size_t esz = esz_of(dtype);
+        size_t na = 0, nc = (size_t)guard_elems;
+        std::vector<BranchGramItem> items(nitems);
+        for (int i = 0; i < nitems; ++i) {
+            const int* x = dims + 3 * i; int ord[3] = {0, 1, 2};
+            if (order) { for (int p = 0; p < 3; ++p) ord[p] = order[3 * i + p]; }
+            if (x[0] < 1 || x[1] < 1 || x[2] < 1 || k[i] < 1 || (size_t)x[0] * x[1] * x[2] > 4096) throw Err(TNQS_ERR_INVALID, "dbg_loop_branch_gram: dims, k >= 1, at most 4096 rows");
+            if ((1 << ord[0] | 1 << ord[1] | 1 << ord[2]) != 7 || ord[0] < 0 || ord[1] < 0 || ord[2] < 0) throw Err(TNQS_ERR_INVALID, "dbg_loop_branch_gram: order is no permutation of 0, 1, 2");
+            BranchGramItem& it = items[i]; it = branch_gram_item(x, ord, k[i]);
+            it.A = (const void*)(na * esz); it.B = (const void*)(na * esz); it.C = (void*)(nc * esz);      // offsets for now
+            na += (size_t)it.m * k[i]; nc += (size_t)it.m * it.n + guard_elems;
+        }
+        DBuf dA(na * esz), dB(na * esz), dC(nc * esz); DevItems<BranchGramItem> dI(nitems);
+        for (auto& it : items) { it.A = (char*)dA.p + (size_t)it.A; it.B = (char*)dB.p + (size_t)it.B; it.C = (char*)dC.p + (size_t)it.C; }
+        const int tiles = plan_loop_branch_gram(items.data(), nitems);
+        dA.up(A, na * esz); dB.up(B, na * esz); dC.up(C, nc * esz); dI.up(items);
+        by_dtype(dtype, [&](auto t) { launch_loop_branch_gram<decltype(t)>(nullptr, dI.get(), nitems, tiles); });
+        HIPCHK(hipDeviceSynchronize());
+        dC.down(C, nc * esz);
+    });
+}
 // T_i (nr[i] x nc[i], in place) <- T_i - f_i (b_i^T T_i); f, b: nr[i] elements per item
 extern "C" int tnqs_dbg_loop_antiproject(int dtype, int nitems, const int* nr, const int* nc, void* Tm, const void* f, const void* b) {
     return guard([&] {

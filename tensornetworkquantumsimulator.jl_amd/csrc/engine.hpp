@@ -228,6 +228,9 @@ void site_probabilities(State* s, int v, double* out_p);
 void sample_bp(State* s, int nsamples, const tnqs_bp_opts* bp, uint64_t seed, const double* uniforms, int32_t* out_config, double* out_prob, tnqs_apply_stats* stats);
 // engine_loops.cpp: W(cycle) = Tr prod_k (A_k T_k) for simple cycles of a rescaled cache (loopcorrection.jl:79-89); out: one complex128 per cycle
 void loop_weights(State* s, int ncycles, const int32_t* cycle_len, const int32_t* cycle_verts, double* out_re_im);
+// engine_configs.cpp: the weight of connected leafless configurations (edge lists) with at most two independent loops -- simple cycles (through loop_weights), thetas,
+// dumbbells and figure-eights -- of a rescaled cache; out: one complex128 per configuration
+void config_weights(State* s, int nconfigs, const int32_t* config_nedges, const int32_t* edge_u, const int32_t* edge_v, double* out_re_im);
 // engine_rdm.cpp: un-normalised two-site reduced density matrices of bonds, (d_u d_v)^2 complex128 each, one after the other (null lists: every edge as (src, dst));
 // workspace_bytes: bound on the chain temporaries of a batch of ends (0: min(2 GiB, a quarter of the free device memory)); nbatches (may be null): batches run
 void rdm_edges(State* s, int n_edges, const int32_t* eu, const int32_t* ev, double* out_rho, size_t workspace_bytes = 0, int* nbatches = nullptr);

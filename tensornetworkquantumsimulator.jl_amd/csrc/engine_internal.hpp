@@ -11,6 +11,7 @@
 //   engine_obs.cpp    observables, BP scalars / rescale, symmetric gauge
 //   engine_sample.cpp site probabilities, projection, the sample(alg = "bp") loop
 //   engine_loops.cpp  loop corrections: transfer matrices of simple cycles, ring products, traces (batched)
+//   engine_configs.cpp  loop corrections: configurations with two independent loops (theta, dumbbell, figure-eight): decomposition, branch Grams, chain products
 //   engine_rdm.cpp    two-site reduced density matrices of bonds (batched chains + Grams, one contraction kernel)
 //   engine_paths.cpp  two-site reduced density matrices of the ends of paths (environments, transfer matrices, the sweep along the path)
 //   engine_inner.cpp  overlap of two states: BP on the bilinear form (rectangular messages, mode products that change a leg's dimension, form scalars)
@@ -27,7 +28,7 @@
 //                      V recovery, small-SVD prepare / finish            kernels_gate.hip   fused gauge + f64 Gram of the gate path
 //   kernels_chol.hip   Cholesky (square / packed), env prepare / finish  kernels_f64.hip    ComplexF64 on the f64 matrix cores
 //   kernels_theta.hip  per-gate small algebra: gate_eigs .. gate_finish  kernels_sample.hip sampling
-//   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, antiprojector, trace
+//   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, branch Gram, antiprojector, trace, dot
 //   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs), environment through a transfer matrix (path RDMs)
 //   kernels_inner.hip  overlap of two states: rectangular two-operand Gram (f32 / f64 matrix cores), bilinear message epilogue, form scalars
 //   kernels_amp.hip    bitstring amplitudes: strided-slice GEMM over groups of strings (f32 / f64 matrix cores), per-string vector absorption, epilogue, scalars
@@ -365,6 +366,14 @@ template <class T> void run_env_ends(State* s, std::vector<EnvEnd>& ends, size_t
 // build_transfer_matrices; shared by loop_weights and rdm_paths); phi / psi: the permuted operands of the GEMM that wrote T
 struct TransferVertex { int v, ja, jb, ca, cb; SD sd; Buf phi, psi, T; };
 template <class T> void build_transfer_matrices(State* s, const std::vector<TransferVertex*>& lvs, const char* who);
+// the three-leg Gram of a branch vertex (engine_configs.cpp, tnqs_dbg_loop_branch_gram): legs of dimensions x[0 .. 2] (the row index of both operands, leg 0 fastest),
+// contraction length k; the output holds the pairs (ket, bra) of the legs ord[0], ord[1], ord[2] in this order, ket faster.  Pointers are left to the caller
+inline BranchGramItem branch_gram_item(const int x[3], const int ord[3], int k) {
+    BranchGramItem it{}; it.m = it.n = x[0] * x[1] * x[2]; it.k = k; it.R0 = it.C0 = x[0]; it.R1 = it.C1 = x[1];
+    long long base = 1;
+    for (int p = 0; p < 3; ++p) { const int l = ord[p]; it.sr[l] = base; it.sc[l] = base * x[l]; base *= (long long)x[l] * x[l]; }
+    return it;
+}
 template <class T> void svd_batch(State* s, const std::vector<JacobiItem>& all, bool with_v);
 void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail = nullptr, int* d_polish_sweeps = nullptr);     // svd_batch's Cholesky-QR route (ComplexF32, no V)
 // the launch of svd_batch an item is put into, decided from the sizes the host knows (upper bounds where JacobiItem::dyn is set); none: an empty matrix

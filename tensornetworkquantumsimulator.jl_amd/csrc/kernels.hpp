@@ -341,6 +341,17 @@ struct LoopGemmItem { const void* A; const void* B; void* C; int m, n, k, opB; i
                       int tile_begin, ntm, ntn; };      // set by plan_loop_cgemm: first workgroup, 64 x 64 tiles along m / n
 int plan_loop_cgemm(LoopGemmItem* it, int n);           // returns the launch's workgroups
 template <class T> void launch_loop_cgemm(hipStream_t s, const LoopGemmItem* d_items, int nitems, int total_tiles);
+// C = A B^H (A m x k, B n x k) through a six-index output map: row i = i0 + R0 (i1 + R1 i2) at i0 sr[0] + i1 sr[1] + i2 sr[2], column j = j0 + C0 (j1 + C1 j2)
+// at j0 sc[0] + j1 sc[1] + j2 sc[2] (elements).  The three-leg Gram of a branch vertex (engine_configs.cpp)
+struct BranchGramItem { const void* A; const void* B; void* C; int m, n, k; int R0, R1, C0, C1; long long sr[3], sc[3];
+                        int tile_begin, ntm, ntn; };    // set by plan_loop_branch_gram, as for LoopGemmItem
+int plan_loop_branch_gram(BranchGramItem* it, int n);
+template <class T> void launch_loop_branch_gram(hipStream_t s, const BranchGramItem* d_items, int nitems, int total_tiles);
+// out (one complex128) = sum_i X[i] Y[i], i < n (64-bit), accumulated in f64; partial: 2 nwg doubles of scratch (nwg <= kLoopDotMaxWgs, set by the plan)
+constexpr int kLoopDotMaxWgs = 1024;
+struct LoopDotItem { const void* X; const void* Y; long long n; double* partial; double* out; int wg_begin, nwg; };
+int plan_loop_dot(LoopDotItem* it, int n);
+template <class T> void launch_loop_dot(hipStream_t s, const LoopDotItem* d_items, int nitems, int total_wgs);
 // T (nr x nc) <- T - f (b^T T): f, b vectors of nr elements, bilinear pairing (no conjugate)
 struct LoopProjItem { void* T; const void* f; const void* b; int nr, nc; int wg_begin; };
 int plan_loop_antiproject(LoopProjItem* it, int n);
