@@ -321,6 +321,39 @@ int tnqs_inner_bp(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, do
  * scalar form), a site tensor of more than 2^30 d_v elements. */
 int tnqs_amplitudes_bp(tnqs_handle h, int nstrings, const int32_t* configs, const tnqs_bp_opts* opts, double* out_log_re_im, int32_t* niter, double* final_diff, int32_t* flags);
 
+/* ---- boundary MPS ---------------------------------------------------------------------------------------------------
+ * expect(psi, obs; alg = "boundarymps") and norm_sqr(psi; alg = "boundarymps") (src/expect.jl:84-156, src/norm_sqr.jl:86-91, src/MessagePassing/boundarympscache.jl)
+ * in ONE call, for a state on an open rectangular grid.  vertex_row / vertex_col: the two coordinates of every vertex, in the vertex order of tnqs_create.
+ * partition_by 0 ("row") groups the vertices by vertex_row and orders a group by vertex_col, 1 ("col") the other way round (BoundaryMPSCache, :145-175).  Between
+ * neighbouring partitions there is one MPS per direction with one tensor M[l, a, a', r] per cross edge (a / a' = the ket / bra leg of the edge) and link dimensions
+ * min(x1^2, x2^2, mps_bond_dimension) (virtual_index_dimension, :119-143); it starts as delta(a, a') times all-ones links and is fitted ONCE (the quotient graph is a
+ * line) by the "fitting" update (:330-369): QR gauge walk, one-site sweeps there and back, at most niters sweeps (<= 0: 50), stopping when |cf - previous cf| <
+ * tolerance (tolerance < 0: never, NaN: 1e-5 for ComplexF32 / 1e-8 for ComplexF64; one read-back per sweep with a tolerance, none without); normalize != 0 divides
+ * every fitted tensor by its norm.  Only the messages the request needs are fitted.  Observable i has obs_nverts[i] support vertices (listed one after the other in
+ * obs_verts, all in ONE partition) and one d x d complex128 column-major matrix op[s' + d s] per support vertex in obs_ops, as tnqs_expect_region takes them;
+ * out_numer_denom[4 i ..] = {Re, Im numerator, Re, Im denominator} (path_contract, :616-667; the environments of a partition are built once and shared by its
+ * observables).  out_log_norm_sqr (may be NULL; with nobs = 0 this is the norm): {Re, Im} of log Z = sum_partitions log(vertex scalar) - sum_quotient edges
+ * log(edge scalar) (:504-519), f64 complex logs, imaginary part in (-pi, pi], (-inf, 0) when a scalar is exactly zero.  out_fit_sweeps / out_fit_eps (may be NULL):
+ * 2 (P - 1) entries for P partitions, entry p for the message p -> p + 1, entry P - 1 + p for p + 1 -> p: sweeps run and the last |cf - previous cf| (0 sweeps and NaN
+ * for a message the request did not need).  The handle's site tensors and BP messages are not changed (deferred one-site gates and pending scale factors are applied
+ * first, as tnqs_rdm_1site does); messages and environments live in buffers of the call.
+ * LIMITS (TNQS_ERR_UNSUPPORTED before any device work, tnqs_last_error names the limit): bond dimension chi <= 8 with every link <= 64, or chi <= 16 with every link
+ * <= 16, a link being min(x1^2, x2^2, mps_bond_dimension) (so chi <= 8 with mps_bond_dimension <= 64 and chi <= 16 with mps_bond_dimension <= 16 are always taken, and a
+ * larger mps_bond_dimension is taken where no link of the network reaches it); site dimension <= 16; sharded handles are refused.
+ * TNQS_ERR_INVALID (before any device work): a graph that is not an open rectangular grid under the partitioning -- it would need pseudo-edges, its partitions form
+ * a ring, a partition is not a path --, fewer than two partitions or two vertices per partition, a support outside one partition, a repeated or bad vertex, null pointers,
+ * mps_bond_dimension < 1. */
+typedef struct {
+    int partition_by;         /* 0: "row", 1: "col" */
+    int mps_bond_dimension;   /* R >= 1 */
+    int niters;               /* <= 0: 50 */
+    double tolerance;         /* < 0: none, NaN: default_tolerance of the element type */
+    int normalize;
+} tnqs_bmps_opts;
+int tnqs_expect_bmps(tnqs_handle h, const tnqs_bmps_opts* opts, const int32_t* vertex_row, const int32_t* vertex_col,
+                     int nobs, const int32_t* obs_nverts, const int32_t* obs_verts, const double* obs_ops,
+                     double* out_numer_denom, double* out_log_norm_sqr, int32_t* out_fit_sweeps, double* out_fit_eps);
+
 /* ---- multi-GPU sharding (no reference analogue).  A rank owns a vertex subset: it holds only
  *      those site tensors and does all per-vertex work for them; messages are replicated.  The library calls
  *      the host-supplied all-gather at the exchange points (host side: torch.distributed over RCCL). --------- */

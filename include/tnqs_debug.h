@@ -290,6 +290,20 @@ int tnqs_dbg_inner_finalize(int dtype, int nitems, const int* rows, const int* c
  * (guard counts complex128).  rows or cols outside 1..64: TNQS_ERR_UNSUPPORTED, nothing is written */
 int tnqs_dbg_inner_scalar(int dtype, int nitems, const int* rows, const int* cols, const void* m, const void* mr, const int* present, const double* rawsum, const int* has_rawsum,
                           const int* normalize, const double* scale_a, const double* scale_b, const int* has_scale, double* out_re_im, int guard);
+/* ---- boundary MPS (csrc/kernels_bmps.hip), launched as csrc/engine_bmps.cpp launches them (dtype 0 c64, 1 c128) ----
+ * bmps_contract_kernel<T> and, where an item is chunked, bmps_reduce_kernel<T>: ONE launch each over nitems items of different shape.  Item i: C[m, n] = sum_k A[m, k] B[k, n]
+ * (B conjugated where conjB[i] != 0); m, n, k are groups of ngroup[3 i], [3 i + 1], [3 i + 2] legs (0 .. 4 each) with dimensions dims[12 i + 0 .. 3] (M legs), [+ 4 .. 7] (N
+ * legs), [+ 8 .. 11] (K legs) and element strides strides[24 i + ..]: + 0 .. 3 the M legs in A, + 4 .. 7 the M legs in C, + 8 .. 11 the N legs in B, + 12 .. 15 the N legs in C,
+ * + 16 .. 19 the K legs in A, + 20 .. 23 the K legs in B.  sizes[3 i ..]: the elements of item i's A, B and C arrays; A, B: the items' arrays one after the other; C: guard, item
+ * 0, guard, item 1, ..., guard (guard elements each), up as the caller filled it and back whole -- elements of C that no (m, n) addresses keep what they held.  An index
+ * that would fall outside its array is TNQS_ERR_INVALID before anything runs.  force_chunks <= 0: the engine's chunking, else that many chunks per item where the
+ * contracted range has as many blocks (32 indices for c64, 16 for c128); nchunks_out[i] (may be NULL): the chunks of item i */
+int tnqs_dbg_bmps_contract(int dtype, int nitems, const int32_t* ngroup, const int32_t* dims, const int64_t* strides, const int32_t* conjB, const int64_t* sizes,
+                           const void* A, const void* B, void* C, int guard, int force_chunks, int32_t* nchunks_out);
+/* bmps_qr_kernel<T>, ONE launch over nitems matrices: A_i = Q_i Y_i, m[i] x n[i], m >= n, 1 <= n <= 64 (else TNQS_ERR_UNSUPPORTED, nothing written).  row_major[i] == 0: A_i and
+ * Q_i are column-major (the gauge step towards higher positions), != 0: element (r, c) at r n + c (the step towards lower positions).  A: the items one after the other; Q (m n
+ * numbers per item) and Y (n n, column-major, upper triangular): guard, item 0, guard, ..., guard */
+int tnqs_dbg_bmps_qr(int dtype, int nitems, const int32_t* m, const int32_t* n, const int32_t* row_major, const void* A, void* Q, void* Y, int guard);
 /* ---- sampling (csrc/kernels_sample.hip), launched as csrc/engine_sample.cpp launches them ----
  * site_prob_partial_kernel<T> on one site tensor of n = d k elements (site index fastest) and T = the tensor with its messages absorbed: partial holds `guard` doubles, the raw
  * nblocks x 16 array (partial[16 b + s] = workgroup b's share of diag[s] = Re sum_l T[s, l] conj(psi[s, l]); slots s >= d are not written), `guard` doubles; it goes up as the

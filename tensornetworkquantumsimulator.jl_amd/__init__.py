@@ -7,7 +7,7 @@ from .graphs import (NamedGraph, named_grid, named_hexagonal_lattice_graph, heav
 from .gates import (GATES, ALIASES, BUILTIN_GATES, gate_matrix, register_gate, register_alias, unregister_gate, levenshtein)
 from .core import (TensorNetworkState, tensornetworkstate, random_tensornetworkstate, BeliefPropagationCache, network,
                    scalartype, maxvirtualdim, default_bp_update_kwargs, default_tolerance, update, apply_gates,
-                   apply_circuit, truncate, expect, expect_all, expect_edges, rdm, rdm_edges, rdm_paths, rdm_pairs, expect_pairs, correlation_function, vertex_scalars, edge_scalars, freenergy, partitionfunction,
+                   apply_circuit, truncate, expect, boundarymps_partitioning, expect_all, expect_edges, rdm, rdm_edges, rdm_paths, rdm_pairs, expect_pairs, correlation_function, vertex_scalars, edge_scalars, freenergy, partitionfunction,
                    rescale, rescale_messages, rescale_vertices, normalize, symmetric_gauge, symmetrize_and_normalize, sample, sample_with_probabilities, site_probabilities,
                    loopcorrected_partitionfunction, loop_weights, configuration_weights, norm_sqr, norm, inner, log_inner, log_amplitudes, amplitudes, log_probabilities,
                    bond_spectra, bond_entropies, renyi_entropy, von_neumann_entanglement_entropy, second_renyi_entanglement_entropy,

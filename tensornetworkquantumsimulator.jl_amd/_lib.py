@@ -60,6 +60,10 @@ class ApplyStats(C.Structure):
                 ("n_chol_fallbacks", C.c_int), ("n_qr2_sites", C.c_int), ("n_lowrank_svd", C.c_int), ("n_tall_svd", C.c_int), ("n_svd_sweeps", C.c_int), ("n_svd_sweeps_max", C.c_int), ("n_deferred_1site", C.c_int), ("n_bp_products_reused", C.c_int), ("n_bp_products_evicted", C.c_int), ("n_lowrank_fallbacks", C.c_int), ("n_spec_batches", C.c_int), ("n_spec_redone", C.c_int)]
 
 
+class BmpsOpts(C.Structure):
+    _fields_ = [("partition_by", C.c_int), ("mps_bond_dimension", C.c_int), ("niters", C.c_int), ("tolerance", C.c_double), ("normalize", C.c_int)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
 H = C.c_void_p
@@ -96,6 +100,7 @@ _SIGS = {
     "tnqs_bond_spectra": ([H, C.c_int, _I32P, _I32P, _DP], C.c_int),
     "tnqs_inner_bp": ([H, H, C.POINTER(BpOpts), _DP, C.POINTER(C.c_int), _DP], C.c_int),
     "tnqs_amplitudes_bp": ([H, C.c_int, _I32P, C.POINTER(BpOpts), _DP, _I32P, _DP, _I32P], C.c_int),
+    "tnqs_expect_bmps": ([H, C.POINTER(BmpsOpts), _I32P, _I32P, C.c_int, _I32P, _I32P, _DP, _DP, _DP, _I32P, _DP], C.c_int),
     "tnqs_expect_all": ([H, _DP, _DP], C.c_int),
     "tnqs_expect_region": ([H, C.c_int, _I32P, _I32P, _DP, _DP], C.c_int),
     "tnqs_vertex_scalars": ([H, _DP], C.c_int),

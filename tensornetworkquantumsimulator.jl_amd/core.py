@@ -884,9 +884,145 @@ def _collect_observable(obs, g):
     return op, verts, coeff
 
 
-def expect(bpc: BeliefPropagationCache, observable):
+def _observable_ops(op, verts) -> list:
+    ops = [c for c in op] if isinstance(op, str) else list(op)      # one Pauli character per vertex (collectobservable, expect.jl:159-175)
+    if len(ops) != len(verts):
+        raise L.TnqsError("Invalid observable: need as many operators as vertices passed.")
+    return ops
+
+
+def boundarymps_partitioning(observable, g) -> str:
+    """boundarymps_partitioning (src/expect.jl:186-200): "row" when every observable's support shares its first coordinate, else "col" when it shares the last"""
+    partitioning = None
+    for o in (observable if isinstance(observable, list) else [observable]):
+        vs = _collect_observable(o, g)[1]
+        if len({v[0] for v in vs}) == 1 and partitioning in ("row", None):
+            partitioning = "row"
+        elif len({v[-1] for v in vs}) == 1 and partitioning in ("col", None):
+            partitioning = "col"
+        else:
+            raise L.TnqsArgumentError("Observables must all be aligned in either the same column or the same row to do BoundaryMPS measurements.")
+    return "row" if partitioning is None else partitioning
+
+
+def _bmps_check_format(g, partition_by: str):
+    """what BoundaryMPSCache(...) would need of the graph (src/MessagePassing/boundarympscache.jl:145-175, is_correct_format, :69-81), checked before any device work"""
+    if partition_by not in ("row", "col"):
+        raise L.TnqsArgumentError(f'boundarymps: partition_by must be "row" or "col" (received {partition_by!r})')
+    if not all(isinstance(v, tuple) and len(v) == 2 for v in g.vertices):
+        raise L.TnqsArgumentError("boundarymps: vertices must be 2-tuples (row, column)")
+    key = (lambda v: v[0]) if partition_by == "row" else (lambda v: v[1])
+    order = (lambda v: v[1]) if partition_by == "row" else (lambda v: v[0])
+    keys = sorted({key(v) for v in g.vertices})
+    part = {v: keys.index(key(v)) for v in g.vertices}
+    groups = [sorted([v for v in g.vertices if part[v] == p], key=order) for p in range(len(keys))]
+    for gr in groups:
+        for a, b in zip(gr, gr[1:]):
+            if b not in g.neighbors(a):
+                raise L.TnqsArgumentError("boundarymps: consecutive vertices of a partition are not neighbours: the graph would need pseudo-edges, which are not supported")
+    for (a, b) in g.edges:                            # the quotient graph first, then the partitions, as is_correct_format does
+        dp = abs(part[a] - part[b])
+        if dp > 1:
+            if dp == len(keys) - 1:
+                raise L.TnqsArgumentError("boundarymps: upon partitioning the graph forms a ring (periodic boundaries), which is not supported")
+            raise L.TnqsArgumentError("Upon partitioning, graph does not form a line or ring: can't run boundary MPS")
+    for (a, b) in g.edges:
+        if part[a] == part[b] and abs(groups[part[a]].index(a) - groups[part[a]].index(b)) != 1:
+            raise L.TnqsArgumentError("There's a partition that does not form a line: can't run boundary MPS")
+    return part
+
+
+def _bmps_handle(x, gauge_state: bool, device: int, who: str) -> BeliefPropagationCache:
+    if isinstance(x, BeliefPropagationCache):
+        return x                                      # the network as it stands; its messages are neither read nor changed
+    if not isinstance(x, TensorNetworkState):
+        raise TypeError(f"{who}: expected a TensorNetworkState or a BeliefPropagationCache")
+    bpc = BeliefPropagationCache(x, device=device)
+    if gauge_state:                                   # gauge_and_scale (src/symmetric_gauge.jl:76-83): BP with maxiter = 40, rescale, symmetric gauge
+        bpc = symmetrize_and_normalize(update(bpc, maxiter=40))
+    return bpc
+
+
+def _bmps_call(bpc: BeliefPropagationCache, partition_by: str, mps_bond_dimension: int, message_update_kwargs, obs, want_norm: bool, info):
+    """one tnqs_expect_bmps call; obs: [(verts, matrices)]; returns (numer / denom pairs as an (n, 2) complex array, log norm^2 or None)"""
+    g = bpc.graph
+    kw = dict(message_update_kwargs or {})
+    unknown = set(kw) - {"niters", "tolerance", "normalize"}
+    if unknown:
+        raise L.TnqsArgumentError(f"boundarymps: unknown message_update_kwargs {sorted(unknown)}")
+    tol = kw.get("tolerance", float("nan"))           # absent: default_tolerance of the element type; None: no tolerance
+    o = L.BmpsOpts(0 if partition_by == "row" else 1, int(mps_bond_dimension), int(kw.get("niters", 50)), -1.0 if tol is None else float(tol), 1 if kw.get("normalize", True) else 0)
+    _, rp = L.i32([v[0] for v in g.vertices]); _, cp = L.i32([v[1] for v in g.vertices])
+    nv_, nvp = L.i32([len(vs) for vs, _ in obs] or [0]); ov, ovp = L.i32([g.index[v] for vs, _ in obs for v in vs] or [0])
+    mats = [np.asarray(m, dtype=np.complex128).ravel(order="F") for _, ms in obs for m in ms]
+    flat = np.ascontiguousarray(np.concatenate(mats)) if mats else np.zeros(1, dtype=np.complex128)
+    out = np.zeros((max(len(obs), 1), 2), dtype=np.complex128)
+    lg = np.zeros(2, dtype=np.float64)
+    nq = 2 * (len({(v[0] if partition_by == "row" else v[1]) for v in g.vertices}) - 1)
+    sweeps = np.zeros(max(nq, 1), dtype=np.int32); eps = np.zeros(max(nq, 1), dtype=np.float64)
+    DP = C.POINTER(C.c_double)
+    L.check(L.lib.tnqs_expect_bmps(bpc._h, C.byref(o), rp, cp, len(obs), nvp, ovp, flat.ctypes.data_as(DP), out.ctypes.data_as(DP),
+                                   lg.ctypes.data_as(DP) if want_norm else None, sweeps.ctypes.data_as(C.POINTER(C.c_int32)), eps.ctypes.data_as(DP)))
+    if info is not None:
+        info.update(partition_by=partition_by, fit_sweeps=sweeps[:nq].copy(), fit_eps=eps[:nq].copy())
+        if want_norm:
+            info.update(log_norm_sqr=complex(lg[0], lg[1]))
+    return out[:len(obs)], (complex(lg[0], lg[1]) if want_norm else None)
+
+
+def _expect_bmps(x, observable, mps_bond_dimension, partition_by, gauge_state, message_update_kwargs, device, info):
+    """expect(alg"boundarymps", psi, obs; mps_bond_dimension, partition_by, gauge_state) (src/expect.jl:84-156): every observable of the call in one device call"""
+    if not isinstance(x, (TensorNetworkState, BeliefPropagationCache)):
+        raise TypeError("expect: expected a TensorNetworkState or a BeliefPropagationCache")
+    if mps_bond_dimension is None:
+        raise L.TnqsArgumentError('expect: alg = "boundarymps" needs mps_bond_dimension')
+    g = x.graph
+    many = isinstance(observable, list)
+    collected = [_collect_observable(o, g) for o in (observable if many else [observable])]
+    by = boundarymps_partitioning(observable, g) if partition_by is None else partition_by
+    part = _bmps_check_format(g, by)
+    dims = dict(zip(g.vertices, _site_dims_of(x)))
+    obs, slot = [], []
+    for op, verts, coeff in collected:
+        for v in verts:
+            if v not in g.index:
+                raise L.TnqsArgumentError(f"expect: {v!r} is not a vertex of the graph")
+        ops = _observable_ops(op, verts)
+        if len({part[v] for v in verts}) != 1:
+            raise L.TnqsArgumentError("Observable support must be within a single partition (row/ column) of the graph for now.")
+        if len(set(verts)) != len(verts):
+            raise L.TnqsArgumentError("expect: a vertex appears twice in an observable")
+        if coeff == 0:
+            slot.append(None)                          # iszero(coeff) && return zero(coeff) (expect.jl:91)
+            continue
+        mats = []
+        for v, o_ in zip(verts, ops):
+            m = np.asarray(gate_matrix(o_) if isinstance(o_, str) else o_, dtype=np.complex128)
+            if m.shape != (dims[v], dims[v]):
+                raise L.TnqsArgumentError(f"expect: the operator on {v!r} is not a {dims[v]} x {dims[v]} matrix")
+            mats.append(m)
+        slot.append(len(obs)); obs.append((verts, mats))
+    bpc = _bmps_handle(x, gauge_state, device, "expect")
+    nd = _bmps_call(bpc, by, mps_bond_dimension, message_update_kwargs, obs, False, info)[0] if obs else None
+    res = [0.0 * c if k is None else c * nd[k, 0] / nd[k, 1] for (_, _, c), k in zip(collected, slot)]
+    return res if many else res[0]
+
+
+def expect(x, observable, alg: str = "bp", mps_bond_dimension: Optional[int] = None, partition_by: Optional[str] = None, gauge_state: bool = True,
+           message_update_kwargs: Optional[dict] = None, device: int = 0, info: Optional[dict] = None):
     """expect(alg"bp", cache, obs) for single-site observables (src/expect.jl:59-82); a list of observables returns
-    a list (:114-121)."""
+    a list (:114-121).
+    alg = "boundarymps" (src/expect.jl:84-156): x is a TensorNetworkState on an open rectangular grid (vertices (row, column)), uploaded to a temporary handle on `device`
+    and, with gauge_state, first taken through gauge_and_scale (BP with maxiter = 40, rescale, symmetric gauge); or a BeliefPropagationCache, whose network is used as it
+    stands (its messages are neither read nor changed, gauge_state does not apply).  mps_bond_dimension is required; partition_by ("row" / "col") is inferred from the
+    observables when omitted (row preferred); message_update_kwargs: niters (50), tolerance (default_tolerance of the element type; None: none), normalize (True).  All
+    observables of the call are measured in ONE device call; info (optional dict) receives partition_by, fit_sweeps and fit_eps (one entry per directed pair of
+    neighbouring partitions: p -> p + 1 first, then p + 1 -> p)."""
+    if alg == "boundarymps":
+        return _expect_bmps(x, observable, mps_bond_dimension, partition_by, gauge_state, message_update_kwargs, device, info)
+    if alg != "bp":
+        raise L.TnqsError(f'expect: algorithm choice not supported; supported on the HIP path: "bp" and "boundarymps" (received {alg!r})')
+    bpc = x
     if isinstance(observable, list):
         return [expect(bpc, o) for o in observable]
     op, verts, coeff = _collect_observable(observable, bpc.graph)
@@ -1202,13 +1338,24 @@ def loopcorrected_partitionfunction(bpc: BeliefPropagationCache, max_configurati
 
 
 def norm_sqr(x, alg: str, max_configuration_size: Optional[int] = None, cache_update_kwargs: Optional[dict] = None, device: int = 0,
-             branched: str = "host") -> complex:
-    """norm_sqr(psi; alg) (src/norm_sqr.jl:10-18,62-78) for alg = "bp" and "loopcorrections".  x: a TensorNetworkState (a cache is built and
+             branched: str = "host", mps_bond_dimension: Optional[int] = None, partition_by: str = "row", message_update_kwargs: Optional[dict] = None,
+             info: Optional[dict] = None) -> complex:
+    """norm_sqr(psi; alg) (src/norm_sqr.jl:10-18,62-91) for alg = "bp", "loopcorrections" and "boundarymps".  x: a TensorNetworkState (a cache is built and
     updated with cache_update_kwargs, default default_bp_update_kwargs, on `device`) or an updated BeliefPropagationCache (which stays on its own device: `device` is not used).
-    branched ("host" / "device"): where loopcorrected_partitionfunction weighs configurations with two independent loops."""
+    branched ("host" / "device"): where loopcorrected_partitionfunction weighs configurations with two independent loops.
+    alg = "boundarymps" (:86-91): mps_bond_dimension is required, partition_by defaults to "row", message_update_kwargs as `expect` takes them; the state is not gauged and a
+    cache's messages are neither read nor changed; one device call; info (optional dict) receives log_norm_sqr (the complex logarithm the result is the exp of), fit_sweeps, fit_eps."""
     _check_branched(branched, "norm_sqr")
+    if alg == "boundarymps":
+        if not isinstance(x, (TensorNetworkState, BeliefPropagationCache)):
+            raise TypeError("norm_sqr: expected a TensorNetworkState or a BeliefPropagationCache")
+        if mps_bond_dimension is None:
+            raise L.TnqsArgumentError('norm_sqr: alg = "boundarymps" needs mps_bond_dimension')
+        _bmps_check_format(x.graph, partition_by)
+        bpc = _bmps_handle(x, False, device, "norm_sqr")
+        return complex(np.exp(_bmps_call(bpc, partition_by, mps_bond_dimension, message_update_kwargs, [], True, info)[1]))
     if alg not in ("bp", "loopcorrections"):
-        raise L.TnqsError(f'norm_sqr: algorithm choice not supported; supported on the HIP path: "bp" and "loopcorrections" (received {alg!r})')
+        raise L.TnqsError(f'norm_sqr: algorithm choice not supported; supported on the HIP path: "bp" and "loopcorrections", and "boundarymps" on open rectangular grids (received {alg!r})')
     if alg == "loopcorrections" and max_configuration_size is None:
         raise L.TnqsArgumentError('norm_sqr: alg = "loopcorrections" needs max_configuration_size')
     if isinstance(x, TensorNetworkState):

@@ -140,6 +140,10 @@ int tnqs_rdm_paths(tnqs_handle h, int npaths, const int32_t* path_len, const int
 int tnqs_inner_bp(tnqs_handle ket, tnqs_handle bra, const tnqs_bp_opts* opts, double* out_log_re_im, int* niter, double* final_diff) {
     return guard([&] { inner_bp(S(ket), S(bra), opts, out_log_re_im, niter, final_diff); });
 }
+int tnqs_expect_bmps(tnqs_handle h, const tnqs_bmps_opts* opts, const int32_t* vertex_row, const int32_t* vertex_col, int nobs, const int32_t* obs_nverts,
+                     const int32_t* obs_verts, const double* obs_ops, double* out_numer_denom, double* out_log_norm_sqr, int32_t* out_fit_sweeps, double* out_fit_eps) {
+    return guard([&] { expect_bmps(S(h), opts, vertex_row, vertex_col, nobs, obs_nverts, obs_verts, obs_ops, out_numer_denom, out_log_norm_sqr, out_fit_sweeps, out_fit_eps); });
+}
 int tnqs_amplitudes_bp(tnqs_handle h, int nstrings, const int32_t* configs, const tnqs_bp_opts* opts, double* out_log_re_im, int32_t* niter, double* final_diff, int32_t* flags) {
     return guard([&] { amplitudes_bp(S(h), nstrings, configs, opts, out_log_re_im, niter, final_diff, flags); });
 }

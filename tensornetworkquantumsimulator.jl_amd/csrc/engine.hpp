@@ -248,6 +248,9 @@ void amplitudes_bp(State* s, int nstrings, const int32_t* configs, const tnqs_bp
 // engine_spectra.cpp: entanglement spectra of bonds (entanglement.jl:73-86): request i = (u, v) receives chi doubles, descending, summing to 1, unfiltered (null lists:
 // every edge as (src, dst)); workspace: 64 chi^2 bytes per request, all requests of a call at once
 void bond_spectra(State* s, int n_edges, const int32_t* eu, const int32_t* ev, double* out_spectra);
+// engine_bmps.cpp: expect / norm_sqr with alg = "boundarymps" on an open rectangular grid (include/tnqs.h tnqs_expect_bmps: arguments, outputs and limits)
+void expect_bmps(State* s, const tnqs_bmps_opts* opts, const int32_t* vertex_row, const int32_t* vertex_col, int nobs, const int32_t* obs_nverts, const int32_t* obs_verts,
+                 const double* obs_ops, double* out_numer_denom, double* out_log_norm_sqr, int32_t* out_fit_sweeps, double* out_fit_eps);
 void prof_collect(State* s);
 void materialize_pending_all(State* s);      // apply every deferred one-site gate (State::pend1)
 // sharding.cpp

@@ -17,9 +17,10 @@
 //   engine_inner.cpp  overlap of two states: BP on the bilinear form (rectangular messages, mode products that change a leg's dimension, form scalars)
 //   engine_amp.cpp    amplitudes of a batch of bitstrings: BP on the single-layer network T_v[x_v] (vector messages per string, groups of strings per site value)
 //   engine_spectra.cpp  entanglement spectra of bonds from the two messages (batched eigen problems, one read-back)
+//   engine_bmps.cpp   boundary MPS on open rectangular grids: partition plan, the fitting update of the interpartition messages, measurement and norm
 //   sharding.cpp      exchange step (RCCL or host callback)
 //   api.cpp           the extern "C" boundary of include/tnqs.h (api_guard.hpp: the exception guard every entry point runs in)
-//   debug_*.cpp       the kernel-level test entry points of include/tnqs_debug.h, one file per kernel family: svd, fiber, plane, bp, gate, obs, sample (debug_util.hpp)
+//   debug_*.cpp       the kernel-level test entry points of include/tnqs_debug.h, one file per kernel family: svd, fiber, plane, bp, gate, obs, sample, bmps (debug_util.hpp)
 // and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
 //   kernels_bp.hip     message epilogue, small-site message, rescale,    kernels_x3.hip     the same on the bf16 matrix cores (three-way split)
@@ -33,6 +34,7 @@
 //   kernels_inner.hip  overlap of two states: rectangular two-operand Gram (f32 / f64 matrix cores), bilinear message epilogue, form scalars
 //   kernels_amp.hip    bitstring amplitudes: strided-slice GEMM over groups of strings (f32 / f64 matrix cores), per-string vector absorption, epilogue, scalars
 //   kernels_spectrum.hip  bond entanglement spectra: W = D V^dagger m1^T V D from a message's eigen factorisation, signed sorted spectrum
+//   kernels_bmps.hip   boundary MPS: batched complex contraction over strided leg groups (f32 / f64 matrix cores), chunk reduction, thin Householder QR, norm / scale / conjugate
 #pragma once
 #include "engine.hpp"
 #include "kernels.hpp"

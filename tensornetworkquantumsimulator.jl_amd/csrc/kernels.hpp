@@ -428,6 +428,37 @@ void launch_amp_sweep_end(hipStream_t s, const double* diffs, int nseq, int nstr
 // (out = -inf, 0), bit 1: a scalar not finite (out = NaN, NaN)
 struct AmpScalarItem { const void* m; const void* mr; const double* rawsum; const double* scale; const void* site; int chi, normalize, vertex; };
 template <class T> void launch_amp_scalar(hipStream_t s, const AmpScalarItem* d_items, int nv, int ne, const int* cfg, int ld, int nstrings, double* out, int* flags);
+// ---- boundary MPS (kernels_bmps.hip; engine_bmps.cpp) ----------------------------------------------------------------------------------------------------------------
+// batched complex tensor contraction on the matrix cores: C[m, n] = sum_k A[m, k] B[k, n] (B conjugated when conjB), where m, n and k are each a GROUP of up to four
+// legs (first leg fastest in the group's own counting) with their own element strides: md / ma / mc = dimension of an M leg, its stride in A, its stride in C; nd / nb /
+// nc the same for the N legs in B and C; kd / ka / kb for the contracted legs in A and B.  No operand is ever copied into a permuted layout; a leg of dimension 1 is an
+// ordinary leg.  A workgroup owns a 64 x 64 tile of (m, n) and one CHUNK of consecutive blocks of the contracted range (32 indices per block for ComplexF32, 16 for
+// ComplexF64).  One chunk and out_f64 == 0: the tile is stored into C.  Otherwise every chunk leaves a dense partial [M][N] in the element type and launch_bmps_reduce sums
+// them in f64 and stores C (complex128 when out_f64, whatever the element type: the scalars of a call)
+struct BmpsContractItem {
+    const void* A; const void* B; void* C; void* partial;
+    int nm, nn, nk; int md[4], nd[4], kd[4];
+    long long ma[4], mc[4], nb[4], nc[4], ka[4], kb[4];
+    long long M, N, K;
+    int conjB, out_f64;
+    int ntm, ntn, nchunks, blocks_per_chunk;      // set by plan_bmps_contract
+    int wg_begin, red_begin;
+};
+constexpr int kBmpsMaxLegs = 4;
+// force_chunks > 0: that many chunks per item where the contracted range has as many blocks (debug entry point); otherwise items with fewer than 128 tiles are cut so that
+// the launch has about 256 workgroups, a chunk no shorter than 4 blocks.  npartial[i]: elements of item i's partial buffer (0: it stores C itself); wgs[0]: workgroups of
+// the contraction, wgs[1]: of the reduction
+void plan_bmps_contract(BmpsContractItem* it, int n, size_t esz, int force_chunks, size_t* npartial, int wgs[2]);
+template <class T> void launch_bmps_contract(hipStream_t s, const BmpsContractItem* d_items, int nitems, int wgs);
+template <class T> void launch_bmps_reduce(hipStream_t s, const BmpsContractItem* d_items, int nitems, int wgs);
+// thin Householder QR A = Q Y of an m x n matrix, m >= n, 1 <= n <= 64: A(r, c) at A[r ars + c acs], Q(r, c) at Q[r qrs + c qcs] (Q^dagger Q = I to rounding whatever
+// the rank of A), Y n x n column-major upper triangular; W, W2: m n elements of scratch each.  One workgroup per item
+struct BmpsQrItem { const void* A; long long ars, acs; void* Q; long long qrs, qcs; void* Y; void* W; void* W2; int m, n; };
+constexpr int kBmpsQrMaxCols = 64;
+template <class T> void launch_bmps_qr(hipStream_t s, const BmpsQrItem* d_items, int nitems);
+// *norm_out = ||src||_2 (f64); dst[i] = f src[i], conjugated when conj, f = 1 / norm when normalize != 0 and the norm is not zero, else 1.  One workgroup per item
+struct BmpsNormItem { const void* src; void* dst; long long n; double* norm_out; int normalize, conj; };
+template <class T> void launch_bmps_norm(hipStream_t s, const BmpsNormItem* d_items, int nitems);
 // one-site gates on d = 2, ComplexF32: streaming 2x2 apply, norm partials [item][nbx]
 void launch_site1_c64(hipStream_t s, const Site1Item* d_items, int nitems, int nbx, double* d_norm_partials);
 
