@@ -381,6 +381,47 @@ int tnqs_dbg_gram_c128(int use_mfma, int nitems, const int* shape, const int* sa
  * accumulation in double; has_m: the jobs carry a matrix to absorb; all_same: X == Y on every job; all_f64in: every job has 4 <= D K <= 64 and carries no matrix; the two
  * switches.  *route_out: 0 generic, 1 Mfma32, 2 Mfma64, 3 Fused32, 4 F64x64, 5 F64x128, 6 F64In, 7 Gauge64, 8 Gauge32 (the order of GramRoute).  HOST ONLY */
 int tnqs_dbg_gram_route(int dtype, int acc64, int has_m, int all_same, int all_f64in, int kkmax, int use_mfma, int use_chi64, int* route_out);
+/* ---- the small kernels that otherwise run inside larger calls only (csrc/debug_misc.cpp): each entry point calls the engine's own launch_* / plan_* function.  dtype 0 c64,
+ * 1 c128; on the device every sub-array starts at a multiple of 256 bytes; an output with a guard is laid out as guard, item 0, guard, ..., guard, goes up as the caller
+ * filled it and comes back whole ----
+ * permute_kernel<T> (launch_permute): out[e] = in[sum_k idx_k stride_in[k]] with e = idx_0 + dims_out[0] (idx_1 + ...), 1 <= ndim <= 8.  A source index outside
+ * 0 .. in_elems - 1 is TNQS_ERR_INVALID before anything runs.  guard in elements */
+int tnqs_dbg_permute(int dtype, int ndim, const int32_t* dims_out, const int64_t* stride_in, int64_t in_elems, const void* in, void* out, int guard);
+/* random_fill_kernel<T> (launch_random_fill): n iid normal entries of standard deviation `scale` per part from `seed`; real_only: imaginary parts 0.  guard in elements */
+int tnqs_dbg_random_fill(int dtype, int64_t n, uint64_t seed, double scale, int real_only, void* out, int guard);
+/* identity_kernel<T> (launch_identity): the n x n identity.  guard in elements */
+int tnqs_dbg_identity(int dtype, int n, void* out, int guard);
+/* sum_doubles_kernel (launch_sum_doubles): *out = sum of in[0 .. n - 1], n >= 0 */
+int tnqs_dbg_sum_doubles(int n, const double* in, double* out);
+/* record_pack_kernel, ONE launch over nitems records, then header_gather_kernel over pointers to those records.  info: 4 ints per item; terr: one double per item; S: nS[i]
+ * doubles per item, X2: x2_words[i] 8-byte words per item, both one item after the other (x2_words[i] == 0: the kernel gets a null pointer).  Record i (dst_bytes[i] bytes)
+ * = (info[2], info[3], terr, 0) as doubles | S | ... | X2 at byte x2_off[i]; what lies between and behind the parts is not written.  dst: guard, record 0, guard, ...,
+ * guard, the guard in BYTES.  headers_out: 4 doubles per item.  A record that does not hold its parts is TNQS_ERR_INVALID */
+int tnqs_dbg_record_pack(int nitems, const int32_t* info, const double* terr, const double* S, const int32_t* nS, const void* X2, const int64_t* x2_words, const int64_t* x2_off,
+                         const int64_t* dst_bytes, void* dst, double* headers_out, int guard);
+/* copy_items_kernel (launch_copy_items), ONE launch: item i is n16[i] 16-byte words followed by tail8[i] (0 or 1; tail8 == NULL: none) 8-byte words.  guard in BYTES */
+int tnqs_dbg_copy_items(int nitems, const int64_t* n16, const int32_t* tail8, const void* src, void* dst, int guard);
+/* plan_loop_dot + launch_loop_dot<T> (loop_dot_kernel<T> and its tail), ONE launch: out_i = sum_e X_i[e] Y_i[e] (bilinear, no conjugate) as two doubles, n[i] >= 0 elements.
+ * The partials live in a guarded device buffer prefilled with NaN bytes.  nwg_out[i] (may be NULL): the workgroups the plan gives item i.  X == NULL: only nwg_out is
+ * filled (HOST ONLY, no device is touched) */
+int tnqs_dbg_loop_dot(int dtype, int nitems, const int64_t* n, const void* X, const void* Y, double* out_re_im, int32_t* nwg_out);
+/* bmps_norm_kernel<T> (launch_bmps_norm), ONE launch over nitems vectors of n[i] elements: norm_out[i] = ||src_i||_2 (has_norm[i] == 0: a null pointer, norm_out[i] comes
+ * back as it went up); dst_i = src_i (conjugated when conj[i]) times 1 / norm when normalize[i] and the norm is not 0 (has_dst[i] == 0: a null pointer; the item keeps
+ * its place in dst).  guard in elements */
+int tnqs_dbg_bmps_norm(int dtype, int nitems, const int64_t* n, const void* src, const int32_t* normalize, const int32_t* conj, const int32_t* has_dst, const int32_t* has_norm,
+                       void* dst, double* norm_out, int guard);
+/* amp_sweep_end_kernel (launch_amp_sweep_end): diffs[t nstrings + n]; per string n that is not done: fdiff = (sum_t diffs[t]) / nseq, niter = iter,
+ * done = 1 when tol >= 0 and fdiff <= tol.  The three arrays go up as filled and come back */
+int tnqs_dbg_amp_sweep_end(int nseq, int nstrings, int iter, double tol, const double* diffs, int32_t* done_inout, int32_t* niter_inout, double* fdiff_inout);
+/* amp_scalar_kernel<T> (launch_amp_scalar) over nv + ne items in the engine's order (vertices, then edges): per string the sum over vertex items minus the sum over edge
+ * items of log(sum_j m[j] mr[j]), as (log|.|, phase in (-pi, pi]); flags 1 an exactly zero item, 2 a non-finite one.  Every array holds a part for every item, one item
+ * after the other: m, mr [chi[i]][nstrings] (present[2 i], present[2 i + 1] == 0: a null pointer, all ones); rawsum 2 nstrings doubles (has_rawsum[i] == 0: null; with
+ * normalize[i] the item is multiplied by its string's rawsum unless that is exactly zero); scale one double (has_scale[i] == 0: null); site site_d[i] numbers (may be 0).
+ * is_site[i] (vertex items only) makes item i an isolated vertex: its value is site_i[cfg[n ld + i]].  out_re_im (2 nstrings doubles) and flags_out are guarded, the
+ * guard in their own elements.  chi outside 1..64: TNQS_ERR_UNSUPPORTED */
+int tnqs_dbg_amp_scalar(int dtype, int nv, int ne, const int32_t* chi, const void* m, const void* mr, const int32_t* present, const double* rawsum, const int32_t* has_rawsum,
+                        const int32_t* normalize, const double* scale, const int32_t* has_scale, const void* site, const int32_t* site_d, const int32_t* is_site,
+                        const int32_t* cfg, int ld, int nstrings, double* out_re_im, int32_t* flags_out, int guard);
 #ifdef __cplusplus
 }
 #endif

@@ -133,14 +133,18 @@ extern "C" int tnqs_dbg_svd_tall(int nitems, const int* m, const int* n, void* A
         int dev = 0; HIPCHK(hipGetDevice(&dev));
         std::unique_ptr<State> s(state_create(1, 0, nullptr, nullptr, nullptr, TNQS_C64, dev));
         {
-            DBuf dA(off[nitems] * 8), dF(sizeof(int) * nitems), dS(sizeof(int) * nitems), dW(sizeof(int) * nitems);
-            dA.up(A, off[nitems] * 8);
+            // every matrix starts at a multiple of 256 bytes, as the engine's theta slots do (an odd m n would leave the next one at 8 bytes only); the gaps keep
+            // their 0xff filling, checked below
+            Slots sA; for (int i = 0; i < nitems; ++i) sA.add((size_t)m[i] * n[i] * 8);
+            sA.alloc(); put_all(sA, A); sA.up();
+            DBuf dF(sizeof(int) * nitems), dS(sizeof(int) * nitems), dW(sizeof(int) * nitems);
             HIPCHK(hipMemset(dS.p, 0, sizeof(int) * nitems)); HIPCHK(hipMemset(dW.p, 0xff, sizeof(int) * nitems));      // polish sweeps: -1 = not run
             std::vector<JacobiItem> tall(nitems);
-            for (int i = 0; i < nitems; ++i) { JacobiItem j{}; j.A = (char*)dA.p + off[i] * 8; j.m = m[i]; j.n = n[i]; j.sweeps_out = (int*)dS.p + i; tall[i] = j; }
+            for (int i = 0; i < nitems; ++i) { JacobiItem j{}; j.A = sA.at(i); j.m = m[i]; j.n = n[i]; j.sweeps_out = (int*)dS.p + i; tall[i] = j; }
             svd_tall(s.get(), tall, (int*)dF.p, (int*)dW.p);
             HIPCHK(hipStreamSynchronize(s->stream));
-            dA.down(A, off[nitems] * 8);
+            sA.down("the matrices");
+            for (int i = 0; i < nitems; ++i) sA.get(i, (char*)A + off[i] * 8);
             std::vector<int> f(nitems), w(nitems);
             dF.down(f.data(), sizeof(int) * nitems); dW.down(w.data(), sizeof(int) * nitems);
             if (sweeps) dS.down(sweeps, sizeof(int) * nitems);

@@ -170,7 +170,7 @@ void svd_tall(State* s, const std::vector<JacobiItem>& tall, int* d_fail_out, in
         rj.push_back(JacobiItem{ap + oRr[i], nullptr, n, n, tall[i].sweeps_out});
         wi.push_back(TallSvdItem{nullptr, d_fail + i, ap + oW[i], ap + oJ[i], ap + oRr[i], n, n});   // J = R^-1 (R J), f64; G slot: the item's Cholesky failure flag (J := I then)
         gi.push_back(SmallGemmItem{tall[i].A, ap + oJ[i], ap + oT[i], m, n, n});
-        cp.push_back(CopyItem{ap + oT[i], tall[i].A, (size_t)m * n * 8 / 16});
+        cp.push_back(CopyItem{ap + oT[i], tall[i].A, (size_t)m * n / 2, (m * n) & 1});      // ComplexF32 elements in pairs; an odd count leaves one
     }
     const TallSvdItem* dt = upload(s, ti); const CholItem* dc = upload(s, ci); const JacobiItem* dj = upload(s, rj);
     const TallSvdItem* dw = upload(s, wi); const SmallGemmItem* dg = upload(s, gi); const CopyItem* dcp = upload(s, cp);

@@ -295,7 +295,7 @@ struct CholItem { const void* G; void* L; void* Winv; int n; int* fail; double t
 // Cholesky-QR preprocessing of a tall theta for the LDS-resident Jacobi (kernels_chi64.hip): A m x n (ComplexF32, ld = m)
 struct TallSvdItem { const void* A; void* G; const void* L; void* R0; void* Rrot; int m, n; };
 struct SmallGemmItem { const void* A; const void* B; void* C; int m, n, k; };           // C (m x n) = A (m x k) B (k x n), ComplexF32
-struct CopyItem { const void* src; void* dst; size_t n16; };                             // n16 16-byte words
+struct CopyItem { const void* src; void* dst; size_t n16; int tail8; };                  // n16 16-byte words, then tail8 (0 or 1) 8-byte words
 // register-direct MFMA fiber GEMM for chi = 64 sites (kernels_chi64.hip): rowgemm_tiles() sets the tile grid of an item, plan_rowgemm() the layout
 // of a batch (tpw rule capped at `cap`)
 bool rowgemm_covers(const FiberItem& it);

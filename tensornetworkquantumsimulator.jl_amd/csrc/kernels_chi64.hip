@@ -345,6 +345,9 @@ __global__ __launch_bounds__(256) void copy_items_kernel(const CopyItem* __restr
     const CopyItem it = items[blockIdx.x];
     const v4f* __restrict__ src = reinterpret_cast<const v4f*>(it.src); v4f* __restrict__ dst = reinterpret_cast<v4f*>(it.dst);
     for (size_t e = blockIdx.y * 256 + threadIdx.x; e < it.n16; e += (size_t)gridDim.y * 256) dst[e] = src[e];
+    // an odd number of 8-byte elements: the last one is moved on its own, so nothing behind the item is touched
+    if (it.tail8 && blockIdx.y == 0 && threadIdx.x == 0)
+        reinterpret_cast<unsigned long long*>(it.dst)[2 * it.n16] = reinterpret_cast<const unsigned long long*>(it.src)[2 * it.n16];
 }
 void launch_tall_gram(hipStream_t s, const TallSvdItem* d_items, int nitems, int nmax) {
     if (nitems <= 0) return;

@@ -30,7 +30,8 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_library_exports_every_declared_debug_symbol():
-    """the kernel-level entry points of include/tnqs_debug.h (tests/test_gpu_kernels.py reaches every kernel through them): each declaration has its export"""
+    """the kernel-level entry points of include/tnqs_debug.h (the GPU tests reach the kernels through them; tests/kernel_coverage.py says which test reaches which
+    kernel, and tests/test_kernel_coverage_cpu.py keeps that table complete): each declaration has its export"""
     import ctypes
     import tnqs_amd as tn
     lib = ctypes.CDLL(tn.LIB_PATH)
@@ -41,7 +42,9 @@ def test_library_exports_every_declared_debug_symbol():
             "tnqs_dbg_symg_build", "tnqs_dbg_symg_finish", "tnqs_dbg_diag", "tnqs_dbg_cscale", "tnqs_dbg_fiber_plan",
             "tnqs_dbg_operator_sum", "tnqs_dbg_gate_theta", "tnqs_dbg_gate_finish", "tnqs_dbg_qr2", "tnqs_dbg_small_svd",
             "tnqs_dbg_site_prob", "tnqs_dbg_site_draw", "tnqs_dbg_site_project", "tnqs_dbg_site1", "tnqs_dbg_norm_factor", "tnqs_dbg_scale",
-            "tnqs_dbg_inner_scalar", "tnqs_dbg_theta_svd_stage", "tnqs_dbg_fiber_pass_c128", "tnqs_dbg_gram_c128", "tnqs_dbg_gram_route"} <= decl
+            "tnqs_dbg_inner_scalar", "tnqs_dbg_theta_svd_stage", "tnqs_dbg_fiber_pass_c128", "tnqs_dbg_gram_c128", "tnqs_dbg_gram_route",
+            "tnqs_dbg_permute", "tnqs_dbg_random_fill", "tnqs_dbg_identity", "tnqs_dbg_sum_doubles", "tnqs_dbg_record_pack", "tnqs_dbg_copy_items",
+            "tnqs_dbg_loop_dot", "tnqs_dbg_bmps_norm", "tnqs_dbg_amp_sweep_end", "tnqs_dbg_amp_scalar"} <= decl
     for name in sorted(decl):
         assert hasattr(lib, name), f"{name} declared in include/tnqs_debug.h but not exported"
 

@@ -848,6 +848,24 @@ def test_svd_tall_route(scale):
         check_tall(a, A)
 
 
+def test_svd_tall_route_odd_sizes():
+    """the tall route where m n is odd (d = 3 sites with unequal odd ranks give such thetas, 165 x 123 for one): A J comes back through copy_items, which moves 16-byte
+    words, i.e. PAIRS of ComplexF32 elements -- the last element of an odd count has to be moved on its own.  One launch with an even control.  The inputs are dense
+    and generic (no column of A is a singular direction), so the last element of U Sigma = A J mixes a whole row of A: it is the input's last element only if it was
+    left behind.  A left-behind element also breaks the bounds of check_tall by three orders of magnitude (one entry of relative size 1 / sqrt(m n) against 4.5e-6)"""
+    rng = np.random.default_rng(77)
+    mats = []
+    for (m, n) in [(261, 13), (165, 123), (257, 3), (511, 127), (260, 12)]:
+        q1, _ = np.linalg.qr(rnd(rng, (m, n), np.complex128)); q2, _ = np.linalg.qr(rnd(rng, (n, n), np.complex128))
+        mats.append(((q1 * np.exp(-np.arange(n) * (4.0 / n))) @ q2.conj().T).astype(np.complex64).astype(np.complex128))
+    outs, fail, pol, sw = tall_svd(mats)
+    assert not fail.any() and not pol.any() and np.all(sw >= 0) and np.all(sw < 60)
+    for a, A in zip(mats, outs):
+        assert np.linalg.matrix_rank(a) == a.shape[1]
+        assert A[-1, -1] != a[-1, -1], a.shape          # the last element was written
+        check_tall(a, A)
+
+
 def test_f32_matrix_core_leg():
     """the f32 matrix-instruction variants that only run under TNQS_NO_BF16X3=1 (mfma_rowgemm_kernel<2,2,1>, <2,2,2>, mfma_gram64_kernel): the library reads
     the switch once per process, so the rowgemm and Gram tests above run again in a child process with the switch set, asserting that route"""
