@@ -1,5 +1,6 @@
 // device_common.hpp -- the device-side vocabulary shared by every kernel translation unit: the launch check, vector types, complex numbers,
-// wave / workgroup sums, the item lookup of batched launches and the f64 matrix-core tile products.  (mfma_common.hpp adds the MFMA tile machinery on top of it.)
+// wave / workgroup sums, the item lookup of batched launches, the complex 16x16x4 matrix-core product (CMfma16, cmac16), its split-plane multiply phase (cplane_mm16)
+// and the f64 tile products built on it.  (mfma_common.hpp adds the MFMA tile machinery on top of it.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -54,15 +55,53 @@ template <class Item> __device__ __forceinline__ int find_item(const Item* __res
     return lo;
 }
 
-// one 16 x 16 complex f64 tile product on v_mfma_f64_16x16x4_f64: lane (l15, kq) supplies A[row i][k0 + kq] = fa(i, k) and B[k0 + kq][column j] = fb(k, j)
+// the two 16x16x4 matrix instructions (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64): lane (c = lane & 15, g = lane >> 4) supplies A[row c][k = g] and B[k = g][column c]
+// and holds C / D[row(g, r)][column c] in register r.  TN, LD: the block of contracted indices and the LDS pitch of the split-plane kernels (cplane_mm16)
+template <class T> struct CMfma16;
+template <> struct CMfma16<float> {
+    using Acc = v4f; static constexpr int TN = 32, LD = 36;      // LD: 16 rows x 4 contraction indices of an operand read fall into 64 distinct banks
+    static __device__ __forceinline__ Acc mma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int g, int r) { return 4 * g + r; }
+};
+template <> struct CMfma16<double> {
+    using Acc = v4d; static constexpr int TN = 16, LD = 18;
+    static __device__ __forceinline__ Acc mma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int g, int r) { return g + 4 * r; }      // the f64 instruction's own C / D map
+};
+// one complex rank-4 update as four real ones, c += a b (CONJ: c += a conj(b)).  The instruction order is part of the contract (results are kept bit for bit):
+//   plain       ar br, -ai bi -> re;  ar bi,  ai br -> im
+//   conjugated  ar br,  ai bi -> re;  ai br, -ar bi -> im
+template <bool CONJ, class T> __device__ __forceinline__ void cmac16(T ar, T ai, T br, T bi, typename CMfma16<T>::Acc& cr, typename CMfma16<T>::Acc& ci) {
+    using M = CMfma16<T>;
+    if constexpr (CONJ) { cr = M::mma(ar, br, cr); cr = M::mma(ai, bi, cr); ci = M::mma(ai, br, ci); ci = M::mma(-ar, bi, ci); }
+    else { cr = M::mma(ar, br, cr); cr = M::mma(-ai, bi, cr); ci = M::mma(ar, bi, ci); ci = M::mma(ai, br, ci); }
+}
+
+// the multiply phase of the split-plane kernels (4 waves): one block of TN contracted indices, operands in LDS as (re, im) planes [row][k] of pitch LD.  The live
+// 16 x 16 tiles of the nta x (ntiles / nta) grid are dealt round robin to the waves: tile t = w + 4 u = (ta = t % nta rows of x, tb = t / nta rows of y) goes into
+// cr[u], ci[u] as x y (CONJ: x conj(y)); A[i = row of x][k], B[k][j = row of y]
+template <bool CONJ, class T> __device__ __forceinline__ void cplane_mm16(const T* xr, const T* xi, const T* yr, const T* yi, int nta, int ntiles,
+                                                                          typename CMfma16<T>::Acc (&cr)[4], typename CMfma16<T>::Acc (&ci)[4]) {
+    constexpr int TN = CMfma16<T>::TN, LD = CMfma16<T>::LD;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int t = w + 4 * u;
+        if (t < ntiles) {                                  // (uniform in the wave)
+            const int ta = t % nta, tb = t / nta;
+            const int xo = (16 * ta + c) * LD + g, yo = (16 * tb + c) * LD + g;
+#pragma unroll
+            for (int ks = 0; ks < TN / 4; ++ks) cmac16<CONJ>(xr[xo + 4 * ks], xi[xo + 4 * ks], yr[yo + 4 * ks], yi[yo + 4 * ks], cr[u], ci[u]);
+        }
+    }
+}
+
+// one 16 x 16 complex f64 tile product: lane (l15, kq) supplies A[row i][k0 + kq] = fa(i, k) and B[k0 + kq][column j] = fb(k, j)
 template <class FA, class FB> __device__ __forceinline__ void ztile_mm(int K, int i, int j, FA fa, FB fb, v4d& cr, v4d& ci) {
     const int kq = (threadIdx.x & 63) >> 4;
     for (int k0 = 0; k0 < K; k0 += 4) {
         const cx<double> a = fa(i, k0 + kq), b = fb(k0 + kq, j);
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(a.re, b.re, cr, 0, 0, 0);
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.im, b.im, cr, 0, 0, 0);
-        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(a.re, b.im, ci, 0, 0, 0);
-        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(a.im, b.re, ci, 0, 0, 0);
+        cmac16<false>(a.re, a.im, b.re, b.im, cr, ci);
     }
 }
 
@@ -75,10 +114,7 @@ template <bool CA> __device__ __forceinline__ void tile_mm_f32(const cx<float>* 
     for (int k0 = 0; k0 < K; k0 += 4) {
         const cx<float> a = ap[k0 * as], b = bp[k0 * bs];
         const double ar = a.re, ai = CA ? -(double)a.im : (double)a.im, br = b.re, bi = b.im;
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, cr, 0, 0, 0);
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(-ai, bi, cr, 0, 0, 0);
-        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi, ci, 0, 0, 0);
-        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, ci, 0, 0, 0);
+        cmac16<false>(ar, ai, br, bi, cr, ci);
     }
 }
 

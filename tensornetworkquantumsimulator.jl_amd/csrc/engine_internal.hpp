@@ -21,7 +21,8 @@
 //   sharding.cpp      exchange step (RCCL or host callback)
 //   api.cpp           the extern "C" boundary of include/tnqs.h (api_guard.hpp: the exception guard every entry point runs in)
 //   debug_*.cpp       the kernel-level test entry points of include/tnqs_debug.h, one file per kernel family: svd, fiber, plane, bp, gate, obs, sample, bmps (debug_util.hpp)
-// and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
+// and the kernel translation units behind kernels.hpp (device vocabulary: device_common.hpp, with the complex 16x16x4 matrix-core product CMfma16 / cmac16 and the
+// split-plane multiply phase cplane_mm16 that kernels_inner.hip and kernels_bmps.hip share; MFMA tile machinery: mfma_common.hpp, x3_common.hpp):
 //   kernels.hip        generic fiber GEMM, Gram, Gram route, reduce      kernels_mfma.hip   chi = 32 matrix-core mode products / Grams
 //   kernels_bp.hip     message epilogue, small-site message, rescale,    kernels_x3.hip     the same on the bf16 matrix cores (three-way split)
 //                      edge scalars, symmetric gauge                     kernels_plane.hip  16-dimensional planes (chi = 16)
@@ -29,7 +30,7 @@
 //                      V recovery, small-SVD prepare / finish            kernels_gate.hip   fused gauge + f64 Gram of the gate path
 //   kernels_chol.hip   Cholesky (square / packed), env prepare / finish  kernels_f64.hip    ComplexF64 on the f64 matrix cores
 //   kernels_theta.hip  per-gate small algebra: gate_eigs .. gate_finish  kernels_sample.hip sampling
-//   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM, branch Gram, antiprojector, trace, dot
+//   kernels_util.hip   diag, norm factor, scale, pack, permute, fills       kernels_loop.hip   loop corrections: batched complex GEMM and branch Gram (one tile body), antiprojector, trace, dot
 //   kernels_rdm.hip    bond contraction of two Gram partials (edge RDMs), environment through a transfer matrix (path RDMs)
 //   kernels_inner.hip  overlap of two states: rectangular two-operand Gram (f32 / f64 matrix cores), bilinear message epilogue, form scalars
 //   kernels_amp.hip    bitstring amplitudes: strided-slice GEMM over groups of strings (f32 / f64 matrix cores), per-string vector absorption, epilogue, scalars

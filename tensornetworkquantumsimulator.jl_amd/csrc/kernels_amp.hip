@@ -6,7 +6,7 @@
 //                                R[a, b', p] = sum_k T_u[g + d (a + PA (k + K b'))] M[k, p],   p = idx[n] the position of the group's n-th string in the chunk.
 //                            The slice is read IN PLACE with stride d, the contracted leg anywhere among the bond legs (PA = 1: first, PB = 1: last); 1 <= K <= 64.
 //                            Matrix cores: v_mfma_f32_16x16x4_f32 (ComplexF32, f32 accumulation) / v_mfma_f64_16x16x4_f64 (ComplexF64), four real products per complex
-//                            one.  A workgroup (4 waves) owns 64 rows (a, b') x 64 columns; a wave loads its 16 rows x K of the slice ONCE into registers (lane (c, q):
+//                            one (CMfma16, cmac16 of device_common.hpp).  A workgroup (4 waves) owns 64 rows (a, b') x 64 columns; a wave loads its 16 rows x K of the slice ONCE into registers (lane (c, q):
 //                            row c, k = 4 ks + q) and walks the four 16-column tiles with them.  Rows, columns and k beyond the edge are zero operands (masked loads,
 //                            nothing padded in memory) and are not stored.
 //                            OUTPUT LAYOUT [row a + PA b'][string p]: string p's intermediate is the contiguous tensor of the site's remaining legs, so the next
@@ -25,23 +25,9 @@
 
 namespace tnqs {
 
-namespace {
-template <class T> struct AmpMfma;
-template <> struct AmpMfma<float> {
-    using Acc = v4f;
-    static __device__ __forceinline__ Acc mma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int q, int r) { return 4 * q + r; }
-};
-template <> struct AmpMfma<double> {
-    using Acc = v4d;
-    static __device__ __forceinline__ Acc mma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int q, int r) { return q + 4 * r; }      // the f64 instruction's own C / D map
-};
-}  // namespace
-
 template <class T>
 __global__ __launch_bounds__(256) void amp_leg_gemm_kernel(const AmpGemmItem* __restrict__ items, int nitems) {
-    using M = AmpMfma<T>;
+    using M = CMfma16<T>;
     const AmpGemmItem it = items[find_item(items, nitems, &AmpGemmItem::tile_begin, (int)blockIdx.x)];
     const int t = (int)blockIdx.x - it.tile_begin, tr = t % it.ntr, tc = t / it.ntr;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, q = lane >> 4;
@@ -78,9 +64,7 @@ __global__ __launch_bounds__(256) void amp_leg_gemm_kernel(const AmpGemmItem* __
                 const int k = 4 * ks + q;
                 T br = 0, bi = 0;
                 if (clive && k < K) { if (Mm) { const cx<T> v = Mm[(size_t)K * p + k]; br = v.re; bi = v.im; } else br = 1; }
-                // A[i = row][k] B[k][j = column]: re = ar br - ai bi, im = ar bi + ai br
-                cr = M::mma(ar[ks], br, cr); cr = M::mma(-ai[ks], bi, cr);
-                ci = M::mma(ar[ks], bi, ci); ci = M::mma(ai[ks], br, ci);
+                cmac16<false>(ar[ks], ai[ks], br, bi, cr, ci);      // A[i = row][k] B[k][j = column]
             }
         }
         if (clive) {

@@ -5,8 +5,9 @@
 //                             Matrix cores: v_mfma_f32_16x16x4_f32 (ComplexF32, f32 accumulation) / v_mfma_f64_16x16x4_f64 (ComplexF64), four real products per complex
 //                             rank-4 update.  A workgroup (4 waves) owns a 64 x 64 tile of (m, n) and one chunk of consecutive blocks of TN = 32 (f32) / 16 (f64)
 //                             contracted indices; per block the operands go through LDS as split (re, im) planes [row][k], rows padded with zeros to the 16 x 16 tile
-//                             grid of the tile's live part and the tail of the range zero-filled (the arrangement of inner_gram_kernel, kernels_inner.hip): loads are
-//                             masked, and only entries m < M, n < N of the item's own output are stored.  Items of different shape share a launch (find_item).
+//                             grid of the tile's live part and the tail of the range zero-filled: loads are masked, and only entries m < M, n < N of the item's own
+//                             output are stored.  The instruction trait and the multiply phase of a block are CMfma16 and cplane_mm16<false> of device_common.hpp
+//                             (B is conjugated while it is staged), which inner_gram_kernel (kernels_inner.hip) shares.  Items of different shape share a launch (find_item).
 //   bmps_reduce_kernel<T>     the chunks of an item summed in f64 and stored through the output strides -- as complex128 for the scalars of a call.
 //   bmps_qr_kernel<T>         thin Householder QR A = Q Y, m >= n, n <= 64 (gauge_step!, boundarympscache.jl:270-285: factorize(...; ortho = "left")), one workgroup per
 //                             matrix.  Householder because the initial guess of a message (:180-202) is a product state: its matricisations have rank 1, and Q^dagger Q = I
@@ -22,17 +23,6 @@
 namespace tnqs {
 
 namespace {
-template <class T> struct BmpsMfma;
-template <> struct BmpsMfma<float> {
-    using Acc = v4f; static constexpr int TN = 32, LD = 36;
-    static __device__ __forceinline__ Acc mma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int g, int r) { return 4 * g + r; }
-};
-template <> struct BmpsMfma<double> {
-    using Acc = v4d; static constexpr int TN = 16, LD = 18;
-    static __device__ __forceinline__ Acc mma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int g, int r) { return g + 4 * r; }
-};
 // offsets of the combined index idx of a leg group in two tensors / in one
 __device__ __forceinline__ void bmps_split2(long long idx, int n, const int* dim, const long long* s1, const long long* s2, long long& o1, long long& o2) {
     o1 = 0; o2 = 0;
@@ -47,7 +37,7 @@ __device__ __forceinline__ long long bmps_split1(long long idx, int n, const int
 
 template <class T>
 __global__ __launch_bounds__(256) void bmps_contract_kernel(const BmpsContractItem* __restrict__ items, int nitems) {
-    using Mf = BmpsMfma<T>;
+    using Mf = CMfma16<T>;
     constexpr int TN = Mf::TN, LD = Mf::LD, RS = 256 / TN, NR = 64 / RS;
     __shared__ T xr[64 * LD], xi[64 * LD], yr[64 * LD], yi[64 * LD];
     __shared__ BmpsContractItem it;
@@ -101,20 +91,7 @@ __global__ __launch_bounds__(256) void bmps_contract_kernel(const BmpsContractIt
             }
         }
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = w + 4 * u;
-            if (t < ntiles) {                              // (uniform in the wave)
-                const int ta = t % nta, tb = t / nta;
-                const int xo = (16 * ta + c) * LD + g, yo = (16 * tb + c) * LD + g;
-#pragma unroll
-                for (int ks = 0; ks < TN / 4; ++ks) {
-                    const T ar = xr[xo + 4 * ks], ai = xi[xo + 4 * ks], br = yr[yo + 4 * ks], bi = yi[yo + 4 * ks];
-                    cr[u] = Mf::mma(ar, br, cr[u]); cr[u] = Mf::mma(-ai, bi, cr[u]);
-                    ci[u] = Mf::mma(ar, bi, ci[u]); ci[u] = Mf::mma(ai, br, ci[u]);
-                }
-            }
-        }
+        cplane_mm16<false>(xr, xi, yr, yi, nta, ntiles, cr, ci);      // (B was conjugated on the way in)
     }
     const bool direct = it.partial == nullptr;
     cx<T>* out = direct ? reinterpret_cast<cx<T>*>(it.C) : reinterpret_cast<cx<T>*>(it.partial) + (size_t)chunk * it.M * it.N;

@@ -89,10 +89,7 @@ __global__ __launch_bounds__(256) void mfma_fiber_gemm_f64_kernel(const FiberIte
                 if (4 * ks >= KK) break;                         // (uniform)
                 const zc a = xr[4 * ks];
                 const zc b = cur[ks];
-                cr = __builtin_amdgcn_mfma_f64_16x16x4f64(a.re, b.re, cr, 0, 0, 0);
-                cr = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.im, b.im, cr, 0, 0, 0);
-                ci = __builtin_amdgcn_mfma_f64_16x16x4f64(a.re, b.im, ci, 0, 0, 0);
-                ci = __builtin_amdgcn_mfma_f64_16x16x4f64(a.im, b.re, ci, 0, 0, 0);
+                cmac16<false>(a.re, a.im, b.re, b.im, cr, ci);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -238,10 +235,7 @@ __global__ __launch_bounds__(256) void mfma_gram_f64in_kernel(const GramItem* __
 #pragma unroll
             for (int ks = 0; ks < TF / 4; ++ks) {
                 const zc a = pa[4 * ks], b = pb[4 * ks];
-                cr[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.re, b.re, cr[q], 0, 0, 0);       // a conj(b)
-                cr[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.im, b.im, cr[q], 0, 0, 0);
-                ci[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.im, b.re, ci[q], 0, 0, 0);
-                ci[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.re, b.im, ci[q], 0, 0, 0);
+                cmac16<true>(a.re, a.im, b.re, b.im, cr[q], ci[q]);      // a conj(b)
             }
         }
         lds_barrier();                                           // tile t consumed, tile t + 1 committed

@@ -7,6 +7,8 @@
 //                             CHUNK of consecutive blocks of one item and writes one [Ka Kb] partial.  Per block the operands go through LDS as split (re, im) planes
 //                             [row][n], rows padded with zeros to the 16 x 16 tile grid (ceil(Ka / 16) x ceil(Kb / 16) tiles, dealt round robin to the waves) and the
 //                             tail of the range zero-filled: loads are masked, and only entries a < Ka, b < Kb of the item's own partials are stored.
+//                             The instruction trait and the multiply phase of a block are CMfma16 and cplane_mm16<true> of device_common.hpp, which
+//                             bmps_contract_kernel (kernels_bmps.hip) shares.
 //                             A dimension beyond 64 is NOT taken (inner_gram_covers): the engine and the debug entry point answer TNQS_ERR_UNSUPPORTED, there is no
 //                             scalar form.
 //   inner_finalize_kernel<T>  the epilogue of a bilinear message (the contract of msg_finalize_kernel with rows x cols in place of chi^2): chunks summed in f64,
@@ -21,17 +23,6 @@
 namespace tnqs {
 
 namespace {
-template <class T> struct InnerMfma;
-template <> struct InnerMfma<float> {
-    using Acc = v4f; static constexpr int TN = 32, LD = 36;      // LD: 16 rows x 4 contraction indices of an operand read fall into 64 distinct banks
-    static __device__ __forceinline__ Acc mma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int g, int r) { return 4 * g + r; }
-};
-template <> struct InnerMfma<double> {
-    using Acc = v4d; static constexpr int TN = 16, LD = 18;
-    static __device__ __forceinline__ Acc mma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int g, int r) { return g + 4 * r; }      // the f64 instruction's own C / D map
-};
 // several block-wide sums with one pair of barriers per call (blockDim.x <= 1024); results valid in every thread
 template <int N> __device__ __forceinline__ void inner_block_sums(double (&v)[N], double* sh /* 17 N doubles */) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
@@ -52,7 +43,7 @@ template <int N> __device__ __forceinline__ void inner_block_sums(double (&v)[N]
 
 template <class T>
 __global__ __launch_bounds__(256) void inner_gram_kernel(const InnerGramItem* __restrict__ items, int nitems) {
-    using M = InnerMfma<T>;
+    using M = CMfma16<T>;
     constexpr int TN = M::TN, LD = M::LD;
     __shared__ T xr[64 * LD], xi[64 * LD], yr[64 * LD], yi[64 * LD];
     const InnerGramItem it = items[find_item(items, nitems, &InnerGramItem::chunk_begin, (int)blockIdx.x)];
@@ -91,21 +82,7 @@ __global__ __launch_bounds__(256) void inner_gram_kernel(const InnerGramItem* __
             yr[b * LD + nl] = v.re; yi[b * LD + nl] = v.im;
         }
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = w + 4 * u;
-            if (t < ntiles) {                              // (uniform in the wave)
-                const int ta = t % nta, tb = t / nta;
-                const int xo = (16 * ta + c) * LD + g, yo = (16 * tb + c) * LD + g;
-#pragma unroll
-                for (int ks = 0; ks < TN / 4; ++ks) {
-                    const T ar = xr[xo + 4 * ks], ai = xi[xo + 4 * ks], br = yr[yo + 4 * ks], bi = yi[yo + 4 * ks];
-                    // x conj(y): re = xr yr + xi yi, im = xi yr - xr yi; A[i = row a][k], B[k][j = row b]
-                    cr[u] = M::mma(ar, br, cr[u]); cr[u] = M::mma(ai, bi, cr[u]);
-                    ci[u] = M::mma(ai, br, ci[u]); ci[u] = M::mma(-ar, bi, ci[u]);
-                }
-            }
-        }
+        cplane_mm16<true>(xr, xi, yr, yi, nta, ntiles, cr, ci);      // x conj(y)
     }
     cx<T>* out = reinterpret_cast<cx<T>*>(it.partial) + (size_t)chunk * Ka * Kb;
 #pragma unroll

@@ -2,8 +2,10 @@
 //   loop_cgemm_kernel<T>        batched complex C = A op(B) on the matrix cores, arbitrary m, n, k per item, four-index output map
 //   loop_antiproject_kernel<T>  T <- T - f (b^T T): the antiprojector of one bond applied to the rows of a transfer matrix
 //   loop_trace_kernel<T>        sum_ij X[i,j] Y[j,i] in f64 (partials per workgroup) + loop_trace_tail_kernel (one complex128 per item)
-//   loop_branch_gram_kernel<T>  batched complex C = A B^H like loop_cgemm_kernel, rows and columns each split into three sub-indices with 64-bit strides:
+//   loop_branch_gram_kernel<T>  batched complex C = A B^H, rows and columns each split into three sub-indices with 64-bit strides:
 //                               the three-leg double-layer tensor of a branch vertex, interleaved [(a,a'),(b,b'),(c,c')], without a permuted copy
+//   loop_tile_body              the ONE tile code of these two kernels (staging, predication, multiply loops, store walk); a kernel is its item lookup and its
+//                               output index map, passed as two lambdas
 //   loop_dot_kernel<T>          sum_i X[i] Y[i] in f64 over a 64-bit length (the full contraction of two tensors of one layout) + its tail kernel
 // Matrices are column-major with no padding between columns.
 #include "kernels.hpp"
@@ -18,7 +20,7 @@ namespace tnqs {
 // ZERO in LDS (the global loads are predicated), and the store is predicated: nothing is read or written past the end of a matrix.
 // The matrix instruction gets op(B) as its first operand and A as its second, so a lane holds one ROW i of C and its registers run over
 // columns: the lanes of a store instruction write consecutive elements of the contiguous output axis.
-// ComplexF32: v_mfma_f32_32x32x2_f32, four real products per complex one (CAcc32<false>); ComplexF64: v_mfma_f64_16x16x4_f64, 2 x 2 blocks per wave.
+// ComplexF32: v_mfma_f32_32x32x2_f32, four real products per complex one (CAcc32<false>); ComplexF64: v_mfma_f64_16x16x4_f64 (cmac16), 2 x 2 blocks per wave.
 constexpr int kLoopTile = 64, kLoopPitch = 66;
 template <class T> struct LoopKT { static constexpr int v = sizeof(T) == 4 ? 16 : 8; };
 
@@ -32,23 +34,21 @@ template <class T> __device__ __forceinline__ void loop_load2(const cx<T>* p, bo
     if (ok1) v1 = p[1];
 }
 
-// TWIN: loop_branch_gram_kernel below repeats this kernel's staging, multiply loop and predication for op(B) = B^H with another store; a change to the tile
-// code here belongs there too (they are two kernels so that this one's code object stays what its callers were tested with).
-template <class T> __global__ __launch_bounds__(256) void loop_cgemm_kernel(const LoopGemmItem* __restrict__ items, int nitems) {
+// The tile code of loop_cgemm_kernel and loop_branch_gram_kernel: the tile lt of item `it` (m, n, k, A, B, C, ntm, ntn; opB unless ALWAYS_H), staged, multiplied and
+// stored at C[row_off(i) + col_off(j)].  ALWAYS_H: op(B) = B^H whatever the item says (it need not say), the other staging is not compiled.
+template <class T, bool ALWAYS_H, class Item, class RowOff, class ColOff>
+__device__ __forceinline__ void loop_tile_body(const Item& it, int lt, RowOff row_off, ColOff col_off) {
     constexpr int KT = LoopKT<T>::v, P = kLoopPitch;
     __shared__ __attribute__((aligned(16))) cx<T> As[KT * P];
     __shared__ __attribute__((aligned(16))) cx<T> Bs[KT * P];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, wr = w & 1, wc = w >> 1;
-    const int gt = blockIdx.x;
-    const int lo = find_item(items, nitems, &LoopGemmItem::tile_begin, gt);
-    const LoopGemmItem it = items[lo];
-    const int lt = gt - it.tile_begin;
     if (lt >= it.ntm * it.ntn) return;
     const int i0 = (lt % it.ntm) * kLoopTile, j0 = (lt / it.ntm) * kLoopTile;
     const int m = it.m, n = it.n, k = it.k;
     const cx<T>* __restrict__ A = reinterpret_cast<const cx<T>*>(it.A);
     const cx<T>* __restrict__ B = reinterpret_cast<const cx<T>*>(it.B);
-    const bool conjB = it.opB != 0;
+    bool conjB = true;
+    if constexpr (!ALWAYS_H) conjB = it.opB != 0;
     const bool avec = sizeof(T) == 4 && (m & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
     const bool bvec = sizeof(T) == 4 && (((conjB ? n : k) & 1) == 0) && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
 
@@ -86,7 +86,7 @@ template <class T> __global__ __launch_bounds__(256) void loop_cgemm_kernel(cons
                 v0.im = -v0.im; v1.im = -v1.im;
                 Bs[kk * P + 2 * rp] = v0; Bs[kk * P + 2 * rp + 1] = v1;
             }
-        } else {                                 // B is k x n: element (kk, j) at kk + k j -- k-slices (2 kp, + 1) are memory-adjacent
+        } else if constexpr (!ALWAYS_H) {        // B is k x n: element (kk, j) at kk + k j -- k-slices (2 kp, + 1) are memory-adjacent
             constexpr int KH = KT / 2, JP = 256 / KH;
             const int kp = tid % KH;
 #pragma unroll
@@ -116,136 +116,13 @@ template <class T> __global__ __launch_bounds__(256) void loop_cgemm_kernel(cons
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[b].re, av[a].re, cr[a][b], 0, 0, 0);
-                        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(-bv[b].im, av[a].im, cr[a][b], 0, 0, 0);
-                        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[b].re, av[a].im, ci[a][b], 0, 0, 0);
-                        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[b].im, av[a].re, ci[a][b], 0, 0, 0);
-                    }
-            }
-        }
-        __syncthreads();
-    }
-
-    // store through the output map: row i = i0 + I0 i1 at i0 si0 + i1 si1, column j = j0 + J0 j1 at j0 sj0 + j1 sj1
-    cx<T>* __restrict__ C = reinterpret_cast<cx<T>*>(it.C);
-    if constexpr (sizeof(T) == 4) {
-        const int ln = lane & 31, h = lane >> 5;
-        const int i = i0 + 32 * wr + ln;
-        if (i < m) {
-            const long long ro = (long long)(i % it.I0) * it.si0 + (long long)(i / it.I0) * it.si1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int j = j0 + 32 * wc + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (j < n) C[ro + (long long)(j % it.J0) * it.sj0 + (long long)(j / it.J0) * it.sj1] = cmake<T>(acc.a[r], acc.b[r]);
-            }
-        }
-    } else {
-        const int l15 = lane & 15, kq = lane >> 4;
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int i = i0 + 32 * wr + 16 * a + l15;
-            if (i >= m) continue;
-            const long long ro = (long long)(i % it.I0) * it.si0 + (long long)(i / it.I0) * it.si1;
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = j0 + 32 * wc + 16 * b + kq + 4 * r;
-                    if (j < n) C[ro + (long long)(j % it.J0) * it.sj0 + (long long)(j / it.J0) * it.sj1] = cmake<T>(cr[a][b][r], ci[a][b][r]);
-                }
-        }
-    }
-}
-
-int plan_loop_cgemm(LoopGemmItem* it, int n) {
-    return lay_out(it, n, &LoopGemmItem::tile_begin, nullptr, [](LoopGemmItem& g) {
-        g.ntm = (g.m + kLoopTile - 1) / kLoopTile; g.ntn = (g.n + kLoopTile - 1) / kLoopTile; return g.ntm * g.ntn; });
-}
-template <class T> void launch_loop_cgemm(hipStream_t s, const LoopGemmItem* d_items, int nitems, int total_tiles) {
-    if (nitems <= 0 || total_tiles <= 0) return;
-    hipLaunchKernelGGL((loop_cgemm_kernel<T>), dim3(total_tiles), dim3(256), 0, s, d_items, nitems); TNQS_CHECK_LAUNCH();
-}
-template void launch_loop_cgemm<float>(hipStream_t, const LoopGemmItem*, int, int);
-template void launch_loop_cgemm<double>(hipStream_t, const LoopGemmItem*, int, int);
-
-// ---- three-leg Gram of a branch vertex: C = A B^H, A m x k, B n x k, written through a SIX-index output map -----------------------------------
-// Row i = i0 + R0 (i1 + R1 i2) goes to i0 sr[0] + i1 sr[1] + i2 sr[2], column j = j0 + C0 (j1 + C1 j2) to j0 sc[0] + j1 sc[1] + j2 sc[2]: with A = phi and
-// B = psi of a vertex as [(a, b, c), rest] this writes B[(a,a'),(b,b'),(c,c')] (or any order of the three double legs) without a permuted copy of it.
-// Tile ownership, staging, predication and matrix instructions are those of loop_cgemm_kernel with op(B) = B^H; only the store differs.
-// TWIN of loop_cgemm_kernel: keep the two tile codes in step.
-template <class T> __global__ __launch_bounds__(256) void loop_branch_gram_kernel(const BranchGramItem* __restrict__ items, int nitems) {
-    constexpr int KT = LoopKT<T>::v, P = kLoopPitch;
-    __shared__ __attribute__((aligned(16))) cx<T> As[KT * P];
-    __shared__ __attribute__((aligned(16))) cx<T> Bs[KT * P];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, wr = w & 1, wc = w >> 1;
-    const int gt = blockIdx.x;
-    const int lo = find_item(items, nitems, &BranchGramItem::tile_begin, gt);
-    const BranchGramItem it = items[lo];
-    const int lt = gt - it.tile_begin;
-    if (lt >= it.ntm * it.ntn) return;
-    const int i0 = (lt % it.ntm) * kLoopTile, j0 = (lt / it.ntm) * kLoopTile;
-    const int m = it.m, n = it.n, k = it.k;
-    const cx<T>* __restrict__ A = reinterpret_cast<const cx<T>*>(it.A);
-    const cx<T>* __restrict__ B = reinterpret_cast<const cx<T>*>(it.B);
-    const bool avec = sizeof(T) == 4 && (m & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
-    const bool bvec = sizeof(T) == 4 && (n & 1) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
-
-    CAcc32<false> acc;                           // ComplexF32
-    v4d cr[2][2], ci[2][2];                      // ComplexF64: [row block][column block]
-    if constexpr (sizeof(T) == 4) acc.zero();
-    else {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) { cr[a][b] = (v4d)(0.0); ci[a][b] = (v4d)(0.0); }
-    }
-
-    for (int k0 = 0; k0 < k; k0 += KT) {
-        const int rp = tid & 31;
-#pragma unroll
-        for (int q = 0; q < KT / 8; ++q) {
-            const int kk = (tid >> 5) + 8 * q, gk = k0 + kk, row = i0 + 2 * rp, col = j0 + 2 * rp;
-            const bool kin = gk < k;
-            cx<T> v0, v1;
-            loop_load2<T>(A + (size_t)row + (size_t)m * (kin ? gk : 0), avec, kin && row < m, kin && row + 1 < m, v0, v1);
-            As[kk * P + 2 * rp] = v0; As[kk * P + 2 * rp + 1] = v1;
-            loop_load2<T>(B + (size_t)col + (size_t)n * (kin ? gk : 0), bvec, kin && col < n, kin && col + 1 < n, v0, v1);
-            v0.im = -v0.im; v1.im = -v1.im;
-            Bs[kk * P + 2 * rp] = v0; Bs[kk * P + 2 * rp + 1] = v1;
-        }
-        __syncthreads();
-        if constexpr (sizeof(T) == 4) {
-            const int ln = lane & 31, h = lane >> 5;
-#pragma unroll
-            for (int kk = 0; kk < KT; kk += 2) {
-                const cx<T> a = As[(kk + h) * P + 32 * wr + ln], b = Bs[(kk + h) * P + 32 * wc + ln];
-                acc.mac(b.re, b.im, a.re, a.im);          // D[column = register][row = lane]
-            }
-        } else {
-            const int l15 = lane & 15, kq = lane >> 4;
-#pragma unroll
-            for (int k4 = 0; k4 < KT; k4 += 4) {
-                cx<T> av[2], bv[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) { av[q] = As[(k4 + kq) * P + 32 * wr + 16 * q + l15]; bv[q] = Bs[(k4 + kq) * P + 32 * wc + 16 * q + l15]; }
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[b].re, av[a].re, cr[a][b], 0, 0, 0);
-                        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(-bv[b].im, av[a].im, cr[a][b], 0, 0, 0);
-                        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[b].re, av[a].im, ci[a][b], 0, 0, 0);
-                        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[b].im, av[a].re, ci[a][b], 0, 0, 0);
-                    }
+                    for (int b = 0; b < 2; ++b) cmac16<false>(bv[b].re, bv[b].im, av[a].re, av[a].im, cr[a][b], ci[a][b]);      // (operands swapped, as above)
             }
         }
         __syncthreads();
     }
 
     cx<T>* __restrict__ C = reinterpret_cast<cx<T>*>(it.C);
-    auto row_off = [&](int i) { return (long long)(i % it.R0) * it.sr[0] + (long long)((i / it.R0) % it.R1) * it.sr[1] + (long long)(i / it.R0 / it.R1) * it.sr[2]; };
-    auto col_off = [&](int j) { return (long long)(j % it.C0) * it.sc[0] + (long long)((j / it.C0) % it.C1) * it.sc[1] + (long long)(j / it.C0 / it.C1) * it.sc[2]; };
     if constexpr (sizeof(T) == 4) {
         const int ln = lane & 31, h = lane >> 5;
         const int i = i0 + 32 * wr + ln;
@@ -274,13 +151,42 @@ template <class T> __global__ __launch_bounds__(256) void loop_branch_gram_kerne
         }
     }
 }
-int plan_loop_branch_gram(BranchGramItem* it, int n) {
-    return lay_out(it, n, &BranchGramItem::tile_begin, nullptr, [](BranchGramItem& g) {
+template <class Item> int plan_loop_tiles(Item* it, int n) {
+    return lay_out(it, n, &Item::tile_begin, nullptr, [](Item& g) {
         g.ntm = (g.m + kLoopTile - 1) / kLoopTile; g.ntn = (g.n + kLoopTile - 1) / kLoopTile; return g.ntm * g.ntn; });
 }
-template <class T> void launch_loop_branch_gram(hipStream_t s, const BranchGramItem* d_items, int nitems, int total_tiles) {
+template <class Item> void launch_loop_tiles(void (*kernel)(const Item*, int), hipStream_t s, const Item* d_items, int nitems, int total_tiles) {
     if (nitems <= 0 || total_tiles <= 0) return;
-    hipLaunchKernelGGL((loop_branch_gram_kernel<T>), dim3(total_tiles), dim3(256), 0, s, d_items, nitems); TNQS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kernel, dim3(total_tiles), dim3(256), 0, s, d_items, nitems); TNQS_CHECK_LAUNCH();
+}
+
+// the output map: row i = i0 + I0 i1 at i0 si0 + i1 si1, column j = j0 + J0 j1 at j0 sj0 + j1 sj1
+template <class T> __global__ __launch_bounds__(256) void loop_cgemm_kernel(const LoopGemmItem* __restrict__ items, int nitems) {
+    const LoopGemmItem it = items[find_item(items, nitems, &LoopGemmItem::tile_begin, (int)blockIdx.x)];
+    loop_tile_body<T, false>(it, (int)blockIdx.x - it.tile_begin,
+                             [&](int i) { return (long long)(i % it.I0) * it.si0 + (long long)(i / it.I0) * it.si1; },
+                             [&](int j) { return (long long)(j % it.J0) * it.sj0 + (long long)(j / it.J0) * it.sj1; });
+}
+int plan_loop_cgemm(LoopGemmItem* it, int n) { return plan_loop_tiles(it, n); }
+template <class T> void launch_loop_cgemm(hipStream_t s, const LoopGemmItem* d_items, int nitems, int total_tiles) {
+    launch_loop_tiles(loop_cgemm_kernel<T>, s, d_items, nitems, total_tiles);
+}
+template void launch_loop_cgemm<float>(hipStream_t, const LoopGemmItem*, int, int);
+template void launch_loop_cgemm<double>(hipStream_t, const LoopGemmItem*, int, int);
+
+// ---- three-leg Gram of a branch vertex: C = A B^H, A m x k, B n x k, written through a SIX-index output map -----------------------------------
+// Row i = i0 + R0 (i1 + R1 i2) goes to i0 sr[0] + i1 sr[1] + i2 sr[2], column j = j0 + C0 (j1 + C1 j2) to j0 sc[0] + j1 sc[1] + j2 sc[2]: with A = phi and
+// B = psi of a vertex as [(a, b, c), rest] this writes B[(a,a'),(b,b'),(c,c')] (or any order of the three double legs) without a permuted copy of it.
+// The tile code is loop_tile_body with op(B) = B^H; a kernel of its own, so that the integer divides of this map stay out of loop_cgemm_kernel's store.
+template <class T> __global__ __launch_bounds__(256) void loop_branch_gram_kernel(const BranchGramItem* __restrict__ items, int nitems) {
+    const BranchGramItem it = items[find_item(items, nitems, &BranchGramItem::tile_begin, (int)blockIdx.x)];
+    loop_tile_body<T, true>(it, (int)blockIdx.x - it.tile_begin,
+                            [&](int i) { return (long long)(i % it.R0) * it.sr[0] + (long long)((i / it.R0) % it.R1) * it.sr[1] + (long long)(i / it.R0 / it.R1) * it.sr[2]; },
+                            [&](int j) { return (long long)(j % it.C0) * it.sc[0] + (long long)((j / it.C0) % it.C1) * it.sc[1] + (long long)(j / it.C0 / it.C1) * it.sc[2]; });
+}
+int plan_loop_branch_gram(BranchGramItem* it, int n) { return plan_loop_tiles(it, n); }
+template <class T> void launch_loop_branch_gram(hipStream_t s, const BranchGramItem* d_items, int nitems, int total_tiles) {
+    launch_loop_tiles(loop_branch_gram_kernel<T>, s, d_items, nitems, total_tiles);
 }
 template void launch_loop_branch_gram<float>(hipStream_t, const BranchGramItem*, int, int);
 template void launch_loop_branch_gram<double>(hipStream_t, const BranchGramItem*, int, int);

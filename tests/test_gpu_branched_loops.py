@@ -1,5 +1,5 @@
 """GPU tests of the loop corrections' two-loop configurations on the device (tnqs_config_weights, configuration_weights, branched = "device"):
-loop_branch_gram_kernel through its debug entry point against numpy complex128, the configuration weights against tests/branched_loop_ref.py (and the general
+loop_branch_gram_kernel through its debug entry point against numpy complex128 and against loop_cgemm_kernel to the bit, the configuration weights against tests/branched_loop_ref.py (and the general
 contraction tests/loop_ref.py) on IDENTICAL inputs -- tensors and messages read back from the handle --, and norm_sqr end to end against exact contraction.
 
 Bounds (derived, none measured on the kernels; u = 2^-24 for complex64, 2^-53 for complex128):
@@ -29,7 +29,7 @@ L = tn.core.L
 ERR_INVALID, ERR_UNSUPPORTED = -1, -2                    # include/tnqs.h
 U = {np.complex64: 2.0 ** -24, np.complex128: 2.0 ** -53}
 DT = {np.complex64: 0, np.complex128: 1}
-KCHUNK = {np.complex64: 16, np.complex128: 8}            # LoopKT of csrc/kernels_loop.hip
+KCHUNK = {np.complex64: 16, np.complex128: 8}            # LoopKT of csrc/kernels_loop.hip: the k-chunk of loop_tile_body
 BP_KW = dict(maxiter=300, tolerance=None)
 GUARD = 96
 DTS = [np.complex64, np.complex128]
@@ -85,6 +85,40 @@ def test_loop_branch_gram_against_float64(dt):
         off += n + GUARD
     assert np.all(np.isnan(Cbuf[off - GUARD:].real)) and off == tot
     print(f"MEASURED loop_branch_gram {dt.__name__}: largest error / bound {worst:.3e}")
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_loop_cgemm_and_loop_branch_gram_agree_to_the_bit(dt):
+    """the two kernels share one tile code (loop_tile_body) and differ in the output map only: the same A, B through tnqs_dbg_loop_cgemm (opB = 1, m = n = x0 x1 x2)
+    and through tnqs_dbg_loop_branch_gram give the same BYTES once the GEMM's output is permuted as the Gram's map stores it.  Rows below a tile (6) and one past a
+    tile edge (80), k = 1, chunk + 1, 2 chunk + 3, the identity order and a cyclic one, one launch of each kernel"""
+    kc = KCHUNK[dt]
+    items = [(x, k, od) for x in [(2, 3, 1), (4, 4, 5)] for k in [1, kc + 1, 2 * kc + 3] for od in [(0, 1, 2), (2, 0, 1)]]
+    rng = np.random.default_rng(29)
+    As = [_rand(rng, (k, x[2], x[1], x[0]), dt) for (x, k, _) in items]      # column-major (x0 x1 x2) x k, leg 0 fastest
+    Bs = [_rand(rng, (k, x[2], x[1], x[0]), dt) for (x, k, _) in items]
+    A = np.concatenate([a.reshape(-1) for a in As]); B = np.concatenate([b.reshape(-1) for b in Bs])
+    rows = [int(np.prod(x)) for (x, _, _) in items]
+    tot = GUARD + sum(r * r + GUARD for r in rows)
+    Cgemm, Cgram = (np.full(tot, np.nan + 1j * np.nan, dtype=dt) for _ in range(2))
+    rc = lib.tnqs_dbg_loop_cgemm(DT[dt], 1, len(items), _p(_ints(rows)), _p(_ints(rows)), _p(_ints([k for (_, k, _) in items])), _p(A), _p(B), _p(Cgemm), GUARD)
+    assert rc == 0, lib.tnqs_last_error()
+    rc = lib.tnqs_dbg_loop_branch_gram(DT[dt], len(items), _p(_ints([x for (x, _, _) in items])), _p(_ints([od for (_, _, od) in items])),
+                                       _p(_ints([k for (_, k, _) in items])), _p(A), _p(B), _p(Cgram), GUARD)
+    assert rc == 0, lib.tnqs_last_error()
+    off = GUARD
+    for (x, k, od), r in zip(items, rows):
+        # the GEMM's C[i + m j]: C-order axes (l2', l1', l0', l2, l1, l0); as G of the test above (l2, l1, l0, l2', l1', l0'), then the same axes as there
+        G = np.transpose(Cgemm[off:off + r * r].reshape(x[2], x[1], x[0], x[2], x[1], x[0]), (3, 4, 5, 0, 1, 2))
+        ket = {0: 2, 1: 1, 2: 0}; bra = {0: 5, 1: 4, 2: 3}
+        axes = [ax for p in (od[2], od[1], od[0]) for ax in (bra[p], ket[p])]
+        want, got = np.ascontiguousarray(np.transpose(G, axes)).reshape(-1), Cgram[off:off + r * r]
+        assert np.all(np.isfinite(got)) and np.all(np.isfinite(want))
+        assert got.tobytes() == want.tobytes(), (x, k, od, int(np.sum(got.view(np.uint8) != want.view(np.uint8))))
+        for Cbuf in (Cgemm, Cgram):
+            assert np.all(np.isnan(Cbuf[off - GUARD:off].real))
+        off += r * r + GUARD
+    assert off == tot and np.all(np.isnan(Cgemm[off - GUARD:].real)) and np.all(np.isnan(Cgram[off - GUARD:].real))
 
 
 # ---- weights on identical inputs ----------------------------------------------------------------------------------------------------------------
