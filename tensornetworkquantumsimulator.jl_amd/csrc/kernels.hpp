@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+#include "gram_item.hpp"
 
 namespace tnqs {
 
@@ -22,14 +23,6 @@ struct FiberItem {        // out[(s',n),(a,b)] = sum_{(s,k)} in[(s,k),(a,b)] * X
     int tile_begin;       // first global tile id of this item (MFMA path: first workgroup id)
     int tpw;              // MFMA path: consecutive tiles walked by one workgroup (generic kernel: 1)
     int want_norm;        // 1: write sum |out|^2 of each tile to norm_partials[global tile id]
-};
-
-struct GramItem {         // partial[c][i + KK*j] = sum_{(a,b) in chunk c} X[i,(a,b)] * conj(Y[j,(a,b)]),  i,j = (s,k)
-    const void* X; const void* Y; void* partial;
-    int D, PA, K, PB;
-    int TA, TB, nta, ntb;
-    int chunk_begin, nchunks, tiles_per_chunk;
-    const void* M;        // fused variant only: 32 x 32 message absorbed on the first row leg of X before the Gram
 };
 
 struct ReduceItem {       // out[i + n*j] = sum_c partial[c][..] (optionally conjugated)

@@ -14,162 +14,10 @@
 
 namespace tnqs {
 
-// ------------------------------------------------------------------------------------------------------------
-// Gram (f32 accumulate), KK = D*K <= 64:  partial[c][i + KK*j] = sum_{rows of chunk c} X[i,row] conj(Y[j,row])
-// Tiles of 64 fibers, LDS layout [kk][row] (rows contiguous = memory order); wave w takes 16 rows of every tile and the whole 64 x 64
-// output (four 32 x 32 accumulator pairs); the next tile's loads are in flight during the MFMA block.  32 flop/B when X != Y.
-// ------------------------------------------------------------------------------------------------------------
+// Gram (f32 accumulate), KK = D*K <= 64, 32 flop/B when X != Y: gram64_body (mfma_common.hpp) on the f32 matrix cores, three-multiplication product
 __global__ __launch_bounds__(256, 2) void mfma_gram64_kernel(const GramItem* __restrict__ items, int nitems) {
-    constexpr int TR = 64, TRP = TR + 4, NU = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* const Xr = reinterpret_cast<float*>(smem);
-    float* const Xi = Xr + 64 * TRP;
-    float* const Yr = Xi + 64 * TRP;
-    float* const Yi = Yr + 64 * TRP;
-    const int tid = threadIdx.x;
-    const int gc = blockIdx.x;
-    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
-    const GramItem it = items[lo];
-    const int lc = gc - it.chunk_begin;
-    const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
-    const long long PA = it.PA;
-    const bool same = (it.X == it.Y);
-    const cf* __restrict__ Xg = reinterpret_cast<const cf*>(it.X);
-    const cf* __restrict__ Yg = reinterpret_cast<const cf*>(it.Y);
-    const int ntiles = it.nta * it.ntb;
-    const int t_begin = lc * it.tiles_per_chunk;
-    const int t_end = min(ntiles, t_begin + it.tiles_per_chunk);
-    const int lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
-    // wave w: output rows block a = w & 1 (i in [32 a, 32 a + 32)) x all 64 columns, tile rows 32 (w >> 1) .. + 32 -- 64 accumulator
-    // registers per wave instead of 128, so that TWO workgroups fit a CU (one's barriers and LDS commits hide behind the other's MFMAs)
-    const int a = w & 1, rh = w >> 1;
-    CAcc32<true> C[2];                                           // three-multiplication product (mfma_common.hpp)
-    C[0].zero(); C[1].zero();
-    for (int e = tid; e < 64 * TRP; e += 256) { Xr[e] = 0.f; Xi[e] = 0.f; Yr[e] = 0.f; Yi[e] = 0.f; }
-    const TileMap m = make_map(tid, D, TA, TB, PA, K);
-    const long long kstride = (long long)D * PA;
-    const bool fast = m.U <= 256 && (K + m.KP - 1) / m.KP <= NU;
-    v4f px[NU], py[NU];
-    auto tile_origin = [&](int t, int& a0, int& b0, int& na, int& nb) {
-        int ta = t % it.nta, tb = t / it.nta;
-        a0 = ta * TA; b0 = tb * TB; na = min(TA, it.PA - a0); nb = min(TB, it.PB - b0);
-    };
-    // full tiles of the usual shape (every thread owns NU two-element units): straight-line loads.  The guarded path below compiles
-    // into one branch per load with an s_waitcnt vmcnt(0) in front of the next one, i.e. the NU loads of a tile are SERIALISED (seen in the
-    // ISA; a 64-row tile then costs NU memory latencies, ~10 us instead of the 3.4 us of its matrix work)
-    const bool straight = fast && m.active && m.vec == 2 && K == m.KP * NU;
-    auto issue_loads = [&](int t) {
-        int a0, b0, na, nb; tile_origin(t, a0, b0, na, nb);
-        const long long org = (long long)D * (a0 + PA * (long long)K * b0);
-        if (straight && na == TA && nb == TB) {
-            const cf* px0 = Xg + org + m.off + kstride * m.kp; const cf* py0 = Yg + org + m.off + kstride * m.kp;
-            const long long st = kstride * m.KP;
-            if (same) {
-#pragma unroll
-                for (int j = 0; j < NU; ++j) { px[j] = ldg4(px0 + st * j); py[j] = px[j]; }
-            } else {
-#pragma unroll
-                for (int j = 0; j < NU; ++j) { px[j] = ldg4(px0 + st * j); py[j] = ldg4(py0 + st * j); }
-            }
-            return;
-        }
-        const bool v0 = m.active && m.al < na && m.bl < nb, v1 = v0 && m.al1 < na;
-#pragma unroll
-        for (int j = 0; j < NU; ++j) {
-            int k = m.kp + m.KP * j;
-            v4f vx, vy; vx[0] = vx[1] = vx[2] = vx[3] = 0.f; vy = vx;
-            if (k < K && v0) {
-                const long long o = org + m.off + kstride * k;
-                if (m.vec == 2 && v1) { vx = ldg4(Xg + o); vy = same ? vx : ldg4(Yg + o); }
-                else { cf x = ldgc(Xg + o); vx[0] = x.re; vx[1] = x.im; if (same) vy = vx; else { cf y = ldgc(Yg + o); vy[0] = y.re; vy[1] = y.im; } }
-            }
-            px[j] = vx; py[j] = vy;
-        }
-    };
-    auto commit_loads = [&]() {                  // invalid cells were loaded as zeros, so edge tiles need no extra clearing
-        if (!m.active) return;
-#pragma unroll
-        for (int j = 0; j < NU; ++j) {
-            int k = m.kp + m.KP * j;
-            if (k < K) {
-                int o0 = (m.c0 + D * k) * TRP + m.row0;
-                Xr[o0] = px[j][0]; Xi[o0] = px[j][1]; Yr[o0] = py[j][0]; Yi[o0] = py[j][1];
-                if (m.vec == 2) { int o1 = (m.c1 + D * k) * TRP + m.row1; Xr[o1] = px[j][2]; Xi[o1] = px[j][3]; Yr[o1] = py[j][2]; Yi[o1] = py[j][3]; }
-            }
-        }
-    };
-    if (fast && t_begin < t_end) issue_loads(t_begin);
-    for (int t = t_begin; t < t_end; ++t) {
-        lds_barrier();
-        if (fast) commit_loads();
-        else {
-            int a0, b0, na, nb; tile_origin(t, a0, b0, na, nb);
-            const int ntile_el = D * TA * K * TB;
-            for (int e = tid; e < ntile_el; e += 256) {
-                int s = e % D; int r1 = e / D; int al = r1 % TA; int r2 = r1 / TA; int k = r2 % K; int bl = r2 / K;
-                cf vx, vy; vx.re = vx.im = vy.re = vy.im = 0.f;
-                if (al < na && bl < nb) {
-                    long long off = s + D * ((long long)(a0 + al) + PA * ((long long)k + (long long)K * (b0 + bl)));
-                    vx = Xg[off]; vy = same ? vx : Yg[off];
-                }
-                int o = (s + D * k) * TRP + (al + TA * bl);
-                Xr[o] = vx.re; Xi[o] = vx.im; Yr[o] = vy.re; Yi[o] = vy.im;
-            }
-        }
-        lds_barrier();
-        if (fast && t + 1 < t_end) issue_loads(t + 1);
-        // rows 32 rh .. 32 rh + 31 in two halves of 16 (lane half h takes 8 of them): bounds the operand registers
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            const int r0 = 32 * rh + 16 * hf + 8 * h;
-            float xr[8], xi[8], yr[2][8], yi[2][8];
-            {
-                const int ro = (32 * a + ln) * TRP + r0;
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    v4f t0 = *reinterpret_cast<const v4f*>(Xr + ro + 4 * q), t1 = *reinterpret_cast<const v4f*>(Xi + ro + 4 * q);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) { xr[4 * q + c] = t0[c]; xi[4 * q + c] = t1[c]; }
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int ro = (32 * b + ln) * TRP + r0;
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    v4f t2 = *reinterpret_cast<const v4f*>(Yr + ro + 4 * q), t3 = *reinterpret_cast<const v4f*>(Yi + ro + 4 * q);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) { yr[b][4 * q + c] = t2[c]; yi[b][4 * q + c] = t3[c]; }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    C[b].mac_conj(xr[q], xi[q], yr[b][q], yi[b][q]);       // out[i][j] += x[i] * conj(y[j])
-                }
-            }
-        }
-    }
-    // one partial per chunk: the two row halves (waves w, w + 2) are summed through the free tile buffers
-    lds_barrier();
-    C[0].finish_conj(); C[1].finish_conj();
-    v2f* const R = reinterpret_cast<v2f*>(smem);                // [rh][j][i], pitch 65: 2 * 64 * 65 * 8 B = 66.5 KB
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int i = 32 * a + (r & 3) + 8 * (r >> 2) + 4 * h, j = 32 * b + ln;
-            v2f v = {C[b].a[r], C[b].b[r]};
-            R[(rh * 64 + j) * 65 + i] = v;
-        }
-    lds_barrier();
-    cf* __restrict__ part = reinterpret_cast<cf*>(it.partial) + (size_t)lc * KK * KK;
-    for (int e = tid; e < KK * KK; e += 256) {
-        const int i = e % KK, j = e / KK;
-        const v2f u = R[j * 65 + i], v = R[(64 + j) * 65 + i];
-        cf o; o.re = u[0] + v[0]; o.im = u[1] + v[1]; part[e] = o;
-    }
+    gram64_body<Gram64F32>(items, nitems, smem);
 }
 bool launch_mfma_gram64(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks, int KKmax) {
     if (KKmax > 64) return false;
@@ -529,7 +377,7 @@ void launch_mfma_rowgemm(hipStream_t s, const FiberItem* d_items, int nitems, in
 
 // ------------------------------------------------------------------------------------------------------------
 // Gram with f64 accumulation on v_mfma_f64_16x16x4_f64 for 64 < KK = D*K <= 128 (gate path at chi = 64: G = psi~^dagger psi~ over the
-// outer legs, 128 x 128).  Same scheme as mfma_gram64_f64_kernel (kernels_mfma.hip): ComplexF32 tiles of 64 fibers, double-buffered in
+// outer legs, 128 x 128).  Same scheme and pieces as mfma_gram64_f64_kernel (kernels_mfma.hip; mfma_common.hpp): ComplexF32 tiles of 64 fibers, double-buffered in
 // LDS as [kk][row], converted on the fly (f32 products are exact in f64); G is Hermitian, so only the 16 x 16 blocks (I <= J) are
 // computed -- 36 for KK = 128, dealt round-robin to the four waves (9 each) -- and mirrored when the partial is written.
 // One partial per chunk.  f64 MFMA layout: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], C[row = (l >> 4) + 4 r][col = l & 15].
@@ -567,11 +415,7 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
     const int nb = (KK + 15) >> 4, nblk = nb * (nb + 1) / 2;
     int bI[NBW], bJ[NBW]; bool bOn[NBW];
 #pragma unroll
-    for (int q = 0; q < NBW; ++q) {
-        int idx = w + 4 * q; bOn[q] = idx < nblk;
-        int I = 0, rem = bOn[q] ? idx : 0; while (rem >= nb - I) { rem -= nb - I; ++I; }
-        bI[q] = I; bJ[q] = I + rem;
-    }
+    for (int q = 0; q < NBW; ++q) { int idx = w + 4 * q; bOn[q] = idx < nblk; gram_block_of(nb, bOn[q] ? idx : 0, bI[q], bJ[q]); }
     if (SHARED) {
         const int rI[9] = {0, 1, 3, 4, 6, 7, 0, 3, 6}, rJ[9] = {7, 7, 7, 7, 7, 7, 6, 6, 6};            // wave 3
 #pragma unroll
@@ -581,7 +425,7 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
             else { bI[q] = rI[q]; bJ[q] = rJ[q]; }
         }
     }
-    v4d Cr[NBW], Ci[NBW], Cc[NBW];                             // sum (ar+ai) br,  sum ai (br-bi),  sum ar (bi+br)  (three multiplications: CAcc32::mac_conj in f64)
+    v4d Cr[NBW], Ci[NBW], Cc[NBW];                             // sum (ar+ai) br,  sum ai (br-bi),  sum ar (bi+br)  (gram_f64_mac3)
 #pragma unroll
     for (int q = 0; q < NBW; ++q)
 #pragma unroll
@@ -595,7 +439,7 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
         int ta = t % it.nta, tb = t / it.nta;
         a0 = ta * TA; b0 = tb * TB; na = min(TA, it.PA - a0); nbb = min(TB, it.PB - b0);
     };
-    const bool straight = fast && m.active && m.vec == 2 && K == m.KP * NU;      // see mfma_gram64_kernel: guarded loads are serialised
+    const bool straight = fast && m.active && m.vec == 2 && K == m.KP * NU;      // see gram64_body (mfma_common.hpp): guarded loads are serialised
     auto issue_loads = [&](int t) {
         int a0, b0, na, nbb; tile_origin(t, a0, b0, na, nbb);
         const long long org = (long long)D * (a0 + PA * (long long)K * b0);
@@ -665,41 +509,12 @@ __global__ __launch_bounds__(256) void mfma_gram128_f64_kernel(const GramItem* _
 #undef TNQS_SET
         } else
 #pragma unroll
-        for (int q = 0; q < NBW; ++q) {
-            if (!bOn[q]) continue;                               // wave-uniform
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int ro = (16 * bI[q] + l15) * TRP + 16 * kq + 8 * half;
-                const int rb = (16 * bJ[q] + l15) * TRP + 16 * kq + 8 * half;
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    const v4f t0 = *reinterpret_cast<const v4f*>(Xr + ro + 4 * qq), t1 = *reinterpret_cast<const v4f*>(Xi + ro + 4 * qq);
-                    const v4f u0 = *reinterpret_cast<const v4f*>(Xr + rb + 4 * qq), u1 = *reinterpret_cast<const v4f*>(Xi + rb + 4 * qq);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const double ar = (double)t0[c], ai = (double)t1[c], br = (double)u0[c], bi = (double)u1[c];
-                        Cr[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar + ai, br, Cr[q], 0, 0, 0);       // out[i][j] += x[i] conj(x[j])
-                        Ci[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br - bi, Ci[q], 0, 0, 0);
-                        Cc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi + br, Cc[q], 0, 0, 0);
-                    }
-                }
-            }
-        }
+        for (int q = 0; q < NBW; ++q) if (bOn[q]) gram_f64_block(Xr, Xi, TRP, l15, kq, bI[q], bJ[q], Cr[q], Ci[q], Cc[q]);      // wave-uniform
         lds_barrier();                                           // tile t consumed by everybody, tile t+1 committed by everybody
     }
     cx<double>* __restrict__ part = reinterpret_cast<cx<double>*>(it.partial) + (size_t)lc * KK * KK;
 #pragma unroll
-    for (int q = 0; q < NBW; ++q) {
-        if (!bOn[q]) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = 16 * bI[q] + kq + 4 * r, j = 16 * bJ[q] + l15;
-            if (i < KK && j < KK) {
-                cx<double> v; v.re = Cr[q][r] - Ci[q][r]; v.im = Cr[q][r] - Cc[q][r]; part[i + (size_t)KK * j] = v;
-                if (bI[q] != bJ[q]) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }
-            }
-        }
-    }
+    for (int q = 0; q < NBW; ++q) if (bOn[q]) gram_f64_store<false>(part, KK, l15, kq, bI[q], bJ[q], Cr[q], Ci[q], Cc[q]);
 }
 bool launch_mfma_gram128_f64(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks, int KKmax, bool all_kk128) {
     if (KKmax > 128) return false;

@@ -23,7 +23,7 @@ namespace tnqs {
 //              v_mfma_f32_32x32x2_f32 with Gauss' three products; A operand 16 consecutive floats per lane (k-step t <-> r = t + 16 h),
 //              B operand = A^T staged once per workgroup; the result is written over the wave's own rows;
 //   Gram       the ten upper 16 x 16 blocks of G on v_mfma_f64_16x16x4_f64 in panel-sharing sets, 3M in f64 (gram_f64_shared), dealt to
-//              the waves exactly as in mfma_gram64_f64_kernel<true> (same partial layout: 2 per chunk, one per tile parity).
+//              the waves by Gram64F64Wave (mfma_common.hpp) as in mfma_gram64_f64_kernel<true> (same partial layout: 2 per chunk, one per tile parity).
 // Pipeline: iteration t commits and transforms tile t + 1 in the other buffer, issues the loads of tile t + 2, then multiplies tile t;
 // ONE workgroup barrier per tile.
 // X3 (round 5, default): the transform on the bf16 matrix cores -- the tile rows split exactly into three bf16 pieces on the fly, the matrix A split once per
@@ -135,17 +135,8 @@ __global__ __launch_bounds__(256, 2) void mfma_gauge_gram64_kernel(const GramIte
             Xr[o] = k1[r] - k3[r]; Xi[o] = k1[r] + k2[r];
         }
     };
-    // Gram accumulators: set A (three blocks, tile parity parA) and set B (two blocks), see mfma_gram64_f64_kernel
-    const int parA = (w < 2) ? 0 : 1;
-    v4d CAr[3], CAi[3], CAc[3], CBr[2], CBi[2], CBc[2];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { CAr[j][r] = 0.0; CAi[j][r] = 0.0; CAc[j][r] = 0.0; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { CBr[j][r] = 0.0; CBi[j][r] = 0.0; CBc[j][r] = 0.0; }
+    Gram64F64Wave G(w);                                          // the panel-sharing sets of KK = 64, accumulators and partial layout: mfma_common.hpp
+    G.zero();
     // the pad columns of the planes are never read (rows 0..63 of a column only); nothing to clear
     lds_barrier();                                                  // A^T staged
     if (t_begin < t_end) { issue_loads(t_begin); commit_loads(0); if (t_begin + 1 < t_end) issue_loads(t_begin + 1); transform(0); }
@@ -158,43 +149,11 @@ __global__ __launch_bounds__(256, 2) void mfma_gauge_gram64_kernel(const GramIte
             transform(cur ^ 1);
         }
         const float* Xr = Xbuf + cur * (2 * PLANE); const float* Xi = Xr + PLANE;
-        if (((t - t_begin) & 1) == parA) {                         // wave-uniform
-            const int q3[3] = {0, 1, 2};
-            if (w & 1) gram_f64_shared<3, false, -1>(Xr, Xi, TRP, l15, kq, 3, q3, CAr, CAi, CAc);
-            else       gram_f64_shared<3, true, 0>(Xr, Xi, TRP, l15, kq, 0, q3, CAr, CAi, CAc);
-        } else if (w & 1) {
-            const int q2[1] = {2}, q3b[1] = {3};
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                v4d r1[1] = {CBr[b]}, i1[1] = {CBi[b]}, c1[1] = {CBc[b]};
-                if (b == 0) gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 2, q2, r1, i1, c1);
-                else        gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 3, q3b, r1, i1, c1);
-                CBr[b] = r1[0]; CBi[b] = i1[0]; CBc[b] = c1[0];
-            }
-        } else {
-            const int q12[2] = {1, 2};
-            gram_f64_shared<2, true, 0>(Xr, Xi, TRP, l15, kq, 1, q12, CBr, CBi, CBc);
-        }
+        G.tile_shared(Xr, Xi, TRP, l15, kq, (t - t_begin) & 1);
         lds_barrier();                                              // tile t consumed by everybody, tile t+1 transformed by everybody
     }
-    int aI[3], aJ[3], bI[2], bJ[2];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { aI[q] = (w & 1) ? q : 0; aJ[q] = (w & 1) ? 3 : q; }
-    bI[0] = (w & 1) ? 2 : 1; bJ[0] = (w & 1) ? 2 : 1; bI[1] = (w & 1) ? 3 : 1; bJ[1] = (w & 1) ? 3 : 2;
-    auto write_block = [&](cx<double>* __restrict__ part, int I, int J, const v4d& cr, const v4d& ci, const v4d& cc) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = 16 * I + kq + 4 * r, j = 16 * J + l15;
-            cx<double> v; v.re = cr[r] - ci[r]; v.im = cr[r] - cc[r]; part[i + (size_t)64 * j] = v;
-            if (I != J) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)64 * i] = c; }     // G[j][i] = conj(G[i][j])
-        }
-    };
-    cx<double>* __restrict__ partA = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + parA) * 4096;
-    cx<double>* __restrict__ partB = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + (parA ^ 1)) * 4096;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) write_block(partA, aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) write_block(partB, bI[q], bJ[q], CBr[q], CBi[q], CBc[q]);
+    G.deal_shared();                                                // the tables serve the store alone (tile_shared does not read them): set here, they are not live across the loop
+    G.store<true>(it.partial, lc, 64, l15, kq);
 }
 
 // the shape the kernel covers: d = 2, a 32-dimensional bond leg b and fastest outer leg r (the lowest leg that is not b), complete

@@ -929,9 +929,8 @@ void launch_recover_v_mfma(hipStream_t s, const RecoverItem* d_items, int nitems
 // ComplexF32 input converted on the fly; the f32 products are exact in f64, so G is the exact Gram of the rounded
 // tensor -- what the eigen factorisation replacing the thin QR needs).  f64 MFMA layout: A[i=l&15][k=l>>4],
 // B[k=l>>4][j=l&15], C[row=(l>>4)+4r][col=l&15].  G is Hermitian: only the 16 x 16 blocks (I, J >= I) are computed (ten for a
-// 64 x 64 G) and mirrored when the partials are written.  The blocks are dealt round-robin to the four waves, forwards on even
-// tiles and backwards on odd tiles, so every wave (= SIMD) does 5 blocks per two tiles instead of 8; the two tile parities
-// accumulate into separate partials (2 per chunk) because a block changes wave with the parity.
+// 64 x 64 G) and mirrored when the partials are written.  The blocks are dealt to the four waves by tile parity, 5 blocks per wave and
+// two tiles instead of 8, two partials per chunk: Gram64F64Wave (mfma_common.hpp), shared with mfma_gauge_gram64_kernel.
 // ------------------------------------------------------------------------------------------------------------
 template <bool SHARED>         // SHARED: every item of the launch has KK = 64 (four panels): blocks dealt in panel-sharing sets
 __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem* __restrict__ items, int nitems) {
@@ -951,36 +950,9 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem*
     const int t_begin = lc * it.tiles_per_chunk;
     const int t_end = min(ntiles, t_begin + it.tiles_per_chunk);
     const int lane = tid & 63, w = tid >> 6, l15 = lane & 15, kq = lane >> 4;
-    // upper-triangle blocks in row-major order, dealt to the waves: slot q of parity p holds block  p ? nblk-1-(w+4q) ... see below
-    const int nb = (KK + 15) >> 4, nblk = nb * (nb + 1) / 2;
-    // waves 0, 1 own three blocks on even tiles and two on odd tiles, waves 2, 3 the other way round: slot sets A (3) and B (2)
-    const int parA = (w < 2) ? 0 : 1;                          // tile parity on which this wave uses set A
-    int aI[3], aJ[3], bI[2], bJ[2]; bool aOn[3], bOn[2];
-    auto block_of = [&](int idx, int& I, int& J) { I = 0; int rem = idx; while (rem >= nb - I) { rem -= nb - I; ++I; } J = I + rem; };
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { const int wv = parA ? 3 - w : w; int idx = wv + 4 * q; aOn[q] = idx < nblk; block_of(aOn[q] ? idx : 0, aI[q], aJ[q]); }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) { const int wv = parA ? w : 3 - w; int idx = wv + 4 * q; bOn[q] = idx < nblk; block_of(bOn[q] ? idx : 0, bI[q], bJ[q]); }
-    // KK = 64 (four panels, ten blocks): sets that share a panel (gram_f64_shared) instead of the round-robin deal --
-    //   even waves: A = {(0,0),(0,1),(0,2)} (rows from panel 0), B = {(1,1),(1,2)} (rows from panel 1)
-    //   odd waves : A = {(0,3),(1,3),(2,3)} (columns from panel 3), B = {(2,2),(3,3)}
-    constexpr bool shared_sets = SHARED;
-    if (shared_sets) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { aOn[q] = true; aI[q] = (w & 1) ? q : 0; aJ[q] = (w & 1) ? 3 : q; }
-        bOn[0] = bOn[1] = true;
-        bI[0] = (w & 1) ? 2 : 1; bJ[0] = (w & 1) ? 2 : 1; bI[1] = (w & 1) ? 3 : 1; bJ[1] = (w & 1) ? 3 : 2;
-    }
-    // Gauss' three-multiplication product in f64 (mfma_common.hpp, CAcc32::mac_conj): per block  sum (ar+ai) br,  sum ai (br-bi),  sum ar (bi+br)
-    v4d CAr[3], CAi[3], CBr[2], CBi[2], CAc[3], CBc[2];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { CAr[j][r] = 0.0; CAi[j][r] = 0.0; CAc[j][r] = 0.0; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { CBr[j][r] = 0.0; CBi[j][r] = 0.0; CBc[j][r] = 0.0; }
+    Gram64F64Wave G(w);                                          // block sets, accumulators and partial layout: mfma_common.hpp
+    if (SHARED) G.deal_shared(); else G.deal(KK);
+    G.zero();
     for (int e = tid; e < 4 * 64 * TRP; e += 256) Xbuf[e] = 0.f;
     const TileMap m = make_map(tid, D, TA, TB, PA, K);
     const long long kstride = (long long)D * PA;
@@ -990,8 +962,7 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem*
         int ta = t % it.nta, tb = t / it.nta;
         a0 = ta * TA; b0 = tb * TB; na = min(TA, it.PA - a0); nb = min(TB, it.PB - b0);
     };
-    // full tiles with NU two-element units per thread: straight-line loads (the guarded loop compiles into one branch per load with an
-    // s_waitcnt vmcnt(0) before the next, which serialises the NU loads of a tile -- kernels_chi64.hip, mfma_gram64_kernel)
+    // full tiles with NU two-element units per thread: straight-line loads (see gram64_body, mfma_common.hpp: guarded loads are serialised)
     const bool straight = fast && m.active && m.vec == 2 && K == m.KP * NU;
     auto issue_loads = [&](int t) {
         int a0, b0, na, nb; tile_origin(t, a0, b0, na, nb);
@@ -1050,73 +1021,11 @@ __global__ __launch_bounds__(256, 2) void mfma_gram64_f64_kernel(const GramItem*
             if (fast) { commit_loads(cur ^ 1); if (t + 2 < t_end) issue_loads(t + 2); } else fill_slow(t + 1, cur ^ 1);
         }
         const float* Xr = Xbuf + cur * (2 * 64 * TRP); const float* Xi = Xr + 64 * TRP;
-        // rows of the tile: lane quarter kq takes rows 16*kq + tt, tt = 0..15, in two halves of 8 to bound registers
-        auto block_pass = [&](int I, int J, v4d& cr, v4d& ci, v4d& cc) {
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int ro = (16 * I + l15) * TRP + 16 * kq + 8 * half;
-                const int rb = (16 * J + l15) * TRP + 16 * kq + 8 * half;
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const v4f t0 = *reinterpret_cast<const v4f*>(Xr + ro + 4 * q), t1 = *reinterpret_cast<const v4f*>(Xi + ro + 4 * q);
-                    const v4f u0 = *reinterpret_cast<const v4f*>(Xr + rb + 4 * q), u1 = *reinterpret_cast<const v4f*>(Xi + rb + 4 * q);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const double ar = (double)t0[c], ai = (double)t1[c], br = (double)u0[c], bi = (double)u1[c];
-                        // out[i][j] += x[i] * conj(x[j])
-                        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(ar + ai, br, cr, 0, 0, 0);
-                        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br - bi, ci, 0, 0, 0);
-                        cc = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi + br, cc, 0, 0, 0);
-                    }
-                }
-            }
-        };
-        if (shared_sets) {
-            if (((t - t_begin) & 1) == parA) {                    // wave-uniform
-                const int q3[3] = {0, 1, 2};
-                if (w & 1) gram_f64_shared<3, false, -1>(Xr, Xi, TRP, l15, kq, 3, q3, CAr, CAi, CAc);
-                else       gram_f64_shared<3, true, 0>(Xr, Xi, TRP, l15, kq, 0, q3, CAr, CAi, CAc);
-            } else if (w & 1) {
-                const int q2[1] = {2}, q3b[1] = {3};
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {                      // two diagonal blocks, each on its own panel (register copies, no address taken)
-                    v4d r1[1] = {CBr[b]}, i1[1] = {CBi[b]}, c1[1] = {CBc[b]};
-                    if (b == 0) gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 2, q2, r1, i1, c1);
-                    else        gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 3, q3b, r1, i1, c1);
-                    CBr[b] = r1[0]; CBi[b] = i1[0]; CBc[b] = c1[0];
-                }
-            } else {
-                const int q12[2] = {1, 2};
-                gram_f64_shared<2, true, 0>(Xr, Xi, TRP, l15, kq, 1, q12, CBr, CBi, CBc);
-            }
-        } else {
-            if (((t - t_begin) & 1) == parA) {                    // wave-uniform
-#pragma unroll
-                for (int q = 0; q < 3; ++q) if (aOn[q]) block_pass(aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) if (bOn[q]) block_pass(bI[q], bJ[q], CBr[q], CBi[q], CBc[q]);
-            }
-        }
+        if (SHARED) G.tile_shared(Xr, Xi, TRP, l15, kq, (t - t_begin) & 1);
+        else G.tile_blocks(Xr, Xi, TRP, l15, kq, (t - t_begin) & 1);
         lds_barrier();                                           // tile t consumed by everybody, tile t+1 committed by everybody
     }
-    auto write_block = [&](cx<double>* __restrict__ part, int I, int J, const v4d& cr, const v4d& ci, const v4d& cc) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int i = 16 * I + kq + 4 * r, j = 16 * J + l15;
-            if (i < KK && j < KK) {
-                cx<double> v; v.re = cr[r] - ci[r]; v.im = cr[r] - cc[r]; part[i + (size_t)KK * j] = v;
-                if (I != J) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }     // G[j][i] = conj(G[i][j])
-            }
-        }
-    };
-    // partial 2*lc + p collects the blocks accumulated on tiles of parity p (each block exactly once per parity)
-    cx<double>* __restrict__ partA = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + parA) * KK * KK;
-    cx<double>* __restrict__ partB = reinterpret_cast<cx<double>*>(it.partial) + (size_t)(2 * lc + (parA ^ 1)) * KK * KK;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) if (aOn[q]) write_block(partA, aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) if (bOn[q]) write_block(partB, bI[q], bJ[q], CBr[q], CBi[q], CBc[q]);
+    G.store<false>(it.partial, lc, KK, l15, kq);
 }
 bool launch_mfma_gram64_f64(hipStream_t s, const GramItem* d_items, int nitems, int total_chunks, int KKmax, bool all_kk64) {
     if (KKmax > 64) return false;

@@ -2,6 +2,7 @@
 // on top of the vocabulary of device_common.hpp.
 #pragma once
 #include "device_common.hpp"
+#include "gram_item.hpp"
 
 namespace tnqs {
 
@@ -185,5 +186,288 @@ __device__ __forceinline__ TileMap make_map(int tid, int D, int TA, int TB, long
     m.off = s + (long long)D * (m.al + PA * (long long)K * m.bl);
     return m;
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Gram (f32 accumulate), KK = D*K <= 64:  partial[c][i + KK*j] = sum_{rows of chunk c} X[i,row] conj(Y[j,row])
+// Tiles of 64 fibers, LDS layout [kk][row] (rows contiguous = memory order); the next tile's loads are in flight during the matrix block.
+// Wave w: output rows block a = w & 1 (i in [32 a, 32 a + 32)) x all 64 columns, tile rows 32 (w >> 1) .. + 32 -- 64 accumulator
+// registers per wave instead of 128, so that TWO workgroups fit a CU (one's barriers and LDS commits hide behind the other's MFMAs).
+// Product: the two 32 x 32 complex accumulator blocks b = 0, 1 (columns 32 b ..) of a wave and how they are multiplied --
+//   zero();  mac_half(xr, xi, yr, yi): block b += x conj(y[b]) over the sixteen tile rows of a half (this lane's eight);
+//   finish();  then re(b, r) / im(b, r) of accumulator register r.        Gram64F32 below, Gram64X3 (x3_common.hpp).
+// ------------------------------------------------------------------------------------------------------------
+struct Gram64F32 {               // v_mfma_f32_32x32x2_f32, three-multiplication product
+    CAcc32<true> C[2];
+    __device__ __forceinline__ void zero() { C[0].zero(); C[1].zero(); }
+    __device__ __forceinline__ void mac_half(const float (&xr)[8], const float (&xi)[8], const float (&yr)[2][8], const float (&yi)[2][8]) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) C[b].mac_conj(xr[q], xi[q], yr[b][q], yi[b][q]);       // out[i][j] += x[i] * conj(y[j])
+        }
+    }
+    __device__ __forceinline__ void finish() { C[0].finish_conj(); C[1].finish_conj(); }
+    __device__ __forceinline__ float re(int b, int r) const { return C[b].a[r]; }
+    __device__ __forceinline__ float im(int b, int r) const { return C[b].b[r]; }
+};
+template <class Product>
+__device__ __forceinline__ void gram64_body(const GramItem* __restrict__ items, int nitems, char* smem) {
+    constexpr int TR = 64, TRP = TR + 4, NU = 8;
+    float* const Xr = reinterpret_cast<float*>(smem);
+    float* const Xi = Xr + 64 * TRP;
+    float* const Yr = Xi + 64 * TRP;
+    float* const Yi = Yr + 64 * TRP;
+    const int tid = threadIdx.x;
+    const int gc = blockIdx.x;
+    const int lo = find_item(items, nitems, &GramItem::chunk_begin, gc);
+    const GramItem it = items[lo];
+    const int lc = gc - it.chunk_begin;
+    const int D = it.D, K = it.K, TA = it.TA, TB = it.TB, KK = D * K;
+    const long long PA = it.PA;
+    const bool same = (it.X == it.Y);
+    const cf* __restrict__ Xg = reinterpret_cast<const cf*>(it.X);
+    const cf* __restrict__ Yg = reinterpret_cast<const cf*>(it.Y);
+    const int ntiles = it.nta * it.ntb;
+    const int t_begin = lc * it.tiles_per_chunk;
+    const int t_end = min(ntiles, t_begin + it.tiles_per_chunk);
+    const int lane = tid & 63, w = tid >> 6, ln = lane & 31, h = lane >> 5;
+    const int a = w & 1, rh = w >> 1;
+    Product C; C.zero();
+    for (int e = tid; e < 64 * TRP; e += 256) { Xr[e] = 0.f; Xi[e] = 0.f; Yr[e] = 0.f; Yi[e] = 0.f; }
+    const TileMap m = make_map(tid, D, TA, TB, PA, K);
+    const long long kstride = (long long)D * PA;
+    const bool fast = m.U <= 256 && (K + m.KP - 1) / m.KP <= NU;
+    v4f px[NU], py[NU];
+    auto tile_origin = [&](int t, int& a0, int& b0, int& na, int& nb) {
+        int ta = t % it.nta, tb = t / it.nta;
+        a0 = ta * TA; b0 = tb * TB; na = min(TA, it.PA - a0); nb = min(TB, it.PB - b0);
+    };
+    // full tiles of the usual shape (every thread owns NU two-element units): straight-line loads.  The guarded path below compiles
+    // into one branch per load with an s_waitcnt vmcnt(0) in front of the next one, i.e. the NU loads of a tile are SERIALISED (seen in the
+    // ISA; a 64-row tile then costs NU memory latencies, ~10 us instead of the 3.4 us of its matrix work)
+    const bool straight = fast && m.active && m.vec == 2 && K == m.KP * NU;
+    auto issue_loads = [&](int t) {
+        int a0, b0, na, nb; tile_origin(t, a0, b0, na, nb);
+        const long long org = (long long)D * (a0 + PA * (long long)K * b0);
+        if (straight && na == TA && nb == TB) {
+            const cf* px0 = Xg + org + m.off + kstride * m.kp; const cf* py0 = Yg + org + m.off + kstride * m.kp;
+            const long long st = kstride * m.KP;
+            if (same) {
+#pragma unroll
+                for (int j = 0; j < NU; ++j) { px[j] = ldg4(px0 + st * j); py[j] = px[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NU; ++j) { px[j] = ldg4(px0 + st * j); py[j] = ldg4(py0 + st * j); }
+            }
+            return;
+        }
+        const bool v0 = m.active && m.al < na && m.bl < nb, v1 = v0 && m.al1 < na;
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+            int k = m.kp + m.KP * j;
+            v4f vx, vy; vx[0] = vx[1] = vx[2] = vx[3] = 0.f; vy = vx;
+            if (k < K && v0) {
+                const long long o = org + m.off + kstride * k;
+                if (m.vec == 2 && v1) { vx = ldg4(Xg + o); vy = same ? vx : ldg4(Yg + o); }
+                else { cf x = ldgc(Xg + o); vx[0] = x.re; vx[1] = x.im; if (same) vy = vx; else { cf y = ldgc(Yg + o); vy[0] = y.re; vy[1] = y.im; } }
+            }
+            px[j] = vx; py[j] = vy;
+        }
+    };
+    auto commit_loads = [&]() {                  // invalid cells were loaded as zeros, so edge tiles need no extra clearing
+        if (!m.active) return;
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+            int k = m.kp + m.KP * j;
+            if (k < K) {
+                int o0 = (m.c0 + D * k) * TRP + m.row0;
+                Xr[o0] = px[j][0]; Xi[o0] = px[j][1]; Yr[o0] = py[j][0]; Yi[o0] = py[j][1];
+                if (m.vec == 2) { int o1 = (m.c1 + D * k) * TRP + m.row1; Xr[o1] = px[j][2]; Xi[o1] = px[j][3]; Yr[o1] = py[j][2]; Yi[o1] = py[j][3]; }
+            }
+        }
+    };
+    if (fast && t_begin < t_end) issue_loads(t_begin);
+    for (int t = t_begin; t < t_end; ++t) {
+        lds_barrier();
+        if (fast) commit_loads();
+        else {
+            int a0, b0, na, nb; tile_origin(t, a0, b0, na, nb);
+            const int ntile_el = D * TA * K * TB;
+            for (int e = tid; e < ntile_el; e += 256) {
+                int s = e % D; int r1 = e / D; int al = r1 % TA; int r2 = r1 / TA; int k = r2 % K; int bl = r2 / K;
+                cf vx, vy; vx.re = vx.im = vy.re = vy.im = 0.f;
+                if (al < na && bl < nb) {
+                    long long off = s + D * ((long long)(a0 + al) + PA * ((long long)k + (long long)K * (b0 + bl)));
+                    vx = Xg[off]; vy = same ? vx : Yg[off];
+                }
+                int o = (s + D * k) * TRP + (al + TA * bl);
+                Xr[o] = vx.re; Xi[o] = vx.im; Yr[o] = vy.re; Yi[o] = vy.im;
+            }
+        }
+        lds_barrier();
+        if (fast && t + 1 < t_end) issue_loads(t + 1);
+        // rows 32 rh .. 32 rh + 31 in two halves of 16 (lane half h takes 8 of them): bounds the operand registers
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            const int r0 = 32 * rh + 16 * hf + 8 * h;
+            float xr[8], xi[8], yr[2][8], yi[2][8];
+            {
+                const int ro = (32 * a + ln) * TRP + r0;
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    v4f t0 = *reinterpret_cast<const v4f*>(Xr + ro + 4 * q), t1 = *reinterpret_cast<const v4f*>(Xi + ro + 4 * q);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) { xr[4 * q + c] = t0[c]; xi[4 * q + c] = t1[c]; }
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int ro = (32 * b + ln) * TRP + r0;
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    v4f t2 = *reinterpret_cast<const v4f*>(Yr + ro + 4 * q), t3 = *reinterpret_cast<const v4f*>(Yi + ro + 4 * q);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) { yr[b][4 * q + c] = t2[c]; yi[b][4 * q + c] = t3[c]; }
+                }
+            }
+            C.mac_half(xr, xi, yr, yi);
+        }
+    }
+    // one partial per chunk: the two row halves (waves w, w + 2) are summed through the free tile buffers
+    lds_barrier();
+    C.finish();
+    v2f* const R = reinterpret_cast<v2f*>(smem);                // [rh][j][i], pitch 65: 2 * 64 * 65 * 8 B = 66.5 KB
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = 32 * a + (r & 3) + 8 * (r >> 2) + 4 * h, j = 32 * b + ln;
+            v2f v = {C.re(b, r), C.im(b, r)};
+            R[(rh * 64 + j) * 65 + i] = v;
+        }
+    lds_barrier();
+    cf* __restrict__ part = reinterpret_cast<cf*>(it.partial) + (size_t)lc * KK * KK;
+    for (int e = tid; e < KK * KK; e += 256) {
+        const int i = e % KK, j = e / KK;
+        const v2f u = R[j * 65 + i], v = R[(64 + j) * 65 + i];
+        cf o; o.re = u[0] + v[0]; o.im = u[1] + v[1]; part[e] = o;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// pieces of the f64 Gram kernels (mfma_gram64_f64_kernel, mfma_gram128_f64_kernel, mfma_gauge_gram64_kernel; tile layout and the three
+// accumulators (cr, ci, cc) per 16 x 16 block as for gram_f64_shared above).  G is Hermitian: only the blocks (I, J >= I) are computed.
+// ------------------------------------------------------------------------------------------------------------
+// one k-step of  out[i][j] += a[i] conj(b[j])  in three multiplications
+__device__ __forceinline__ void gram_f64_mac3(double ar, double ai, double br, double bi, v4d& cr, v4d& ci, v4d& cc) {
+    cr = __builtin_amdgcn_mfma_f64_16x16x4f64(ar + ai, br, cr, 0, 0, 0);
+    ci = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br - bi, ci, 0, 0, 0);
+    cc = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi + br, cc, 0, 0, 0);
+}
+// block (I, J) on its own over the 64 rows of a tile: lane quarter kq takes rows 16 kq .. + 15, in two halves of 8 to bound registers
+__device__ __forceinline__ void gram_f64_block(const float* __restrict__ Xr, const float* __restrict__ Xi, int TRP, int l15, int kq, int I, int J,
+                                               v4d& cr, v4d& ci, v4d& cc) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int ro = (16 * I + l15) * TRP + 16 * kq + 8 * half;
+        const int rb = (16 * J + l15) * TRP + 16 * kq + 8 * half;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const v4f t0 = *reinterpret_cast<const v4f*>(Xr + ro + 4 * q), t1 = *reinterpret_cast<const v4f*>(Xi + ro + 4 * q);
+            const v4f u0 = *reinterpret_cast<const v4f*>(Xr + rb + 4 * q), u1 = *reinterpret_cast<const v4f*>(Xi + rb + 4 * q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) gram_f64_mac3((double)t0[c], (double)t1[c], (double)u0[c], (double)u1[c], cr, ci, cc);
+        }
+    }
+}
+// block (I, J) of a KK x KK partial and its mirror; FULL: KK is a multiple of 16, nothing to guard
+template <bool FULL>
+__device__ __forceinline__ void gram_f64_store(cx<double>* __restrict__ part, int KK, int l15, int kq, int I, int J, const v4d& cr, const v4d& ci, const v4d& cc) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = 16 * I + kq + 4 * r, j = 16 * J + l15;
+        if (FULL || (i < KK && j < KK)) {
+            cx<double> v; v.re = cr[r] - ci[r]; v.im = cr[r] - cc[r]; part[i + (size_t)KK * j] = v;
+            if (I != J) { cx<double> c; c.re = v.re; c.im = -v.im; part[j + (size_t)KK * i] = c; }     // G[j][i] = conj(G[i][j])
+        }
+    }
+}
+// the upper-triangle blocks of nb panels in row-major order: block idx -> (I, J)
+__device__ __forceinline__ void gram_block_of(int nb, int idx, int& I, int& J) { I = 0; int rem = idx; while (rem >= nb - I) { rem -= nb - I; ++I; } J = I + rem; }
+
+// A wave of the 64 x 64 f64 Gram: waves 0, 1 own three blocks on even tiles (set A) and two on odd tiles (set B), waves 2, 3 the other way
+// round, so every wave (= SIMD) does 5 blocks per two tiles; the two tile parities accumulate into separate partials (2 per chunk) because
+// a block changes wave with the parity.  deal(): blocks round-robin, forwards on one parity and backwards on the other.  deal_shared(),
+// KK = 64 (four panels, ten blocks): sets that share a panel (gram_f64_shared) --
+//   even waves: A = {(0,0),(0,1),(0,2)} (rows from panel 0), B = {(1,1),(1,2)} (rows from panel 1)
+//   odd waves : A = {(0,3),(1,3),(2,3)} (columns from panel 3), B = {(2,2),(3,3)}
+struct Gram64F64Wave {
+    int w, parA;                                               // parA: tile parity on which this wave uses set A
+    int aI[3], aJ[3], bI[2], bJ[2]; bool aOn[3], bOn[2];
+    v4d CAr[3], CAi[3], CAc[3], CBr[2], CBi[2], CBc[2];
+    __device__ __forceinline__ explicit Gram64F64Wave(int w_) : w(w_), parA((w_ < 2) ? 0 : 1) {}
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { CAr[j][r] = 0.0; CAi[j][r] = 0.0; CAc[j][r] = 0.0; }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { CBr[j][r] = 0.0; CBi[j][r] = 0.0; CBc[j][r] = 0.0; }
+    }
+    __device__ __forceinline__ void deal(int KK) {
+        const int nb = (KK + 15) >> 4, nblk = nb * (nb + 1) / 2;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { const int wv = parA ? 3 - w : w; int idx = wv + 4 * q; aOn[q] = idx < nblk; gram_block_of(nb, aOn[q] ? idx : 0, aI[q], aJ[q]); }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) { const int wv = parA ? w : 3 - w; int idx = wv + 4 * q; bOn[q] = idx < nblk; gram_block_of(nb, bOn[q] ? idx : 0, bI[q], bJ[q]); }
+    }
+    __device__ __forceinline__ void deal_shared() {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { aOn[q] = true; aI[q] = (w & 1) ? q : 0; aJ[q] = (w & 1) ? 3 : q; }
+        bOn[0] = bOn[1] = true;
+        bI[0] = (w & 1) ? 2 : 1; bJ[0] = (w & 1) ? 2 : 1; bI[1] = (w & 1) ? 3 : 1; bJ[1] = (w & 1) ? 3 : 2;
+    }
+    // one tile (parity = its index in the chunk & 1) of the sets of deal_shared()
+    __device__ __forceinline__ void tile_shared(const float* __restrict__ Xr, const float* __restrict__ Xi, int TRP, int l15, int kq, int parity) {
+        if (parity == parA) {                                  // wave-uniform
+            const int q3[3] = {0, 1, 2};
+            if (w & 1) gram_f64_shared<3, false, -1>(Xr, Xi, TRP, l15, kq, 3, q3, CAr, CAi, CAc);
+            else       gram_f64_shared<3, true, 0>(Xr, Xi, TRP, l15, kq, 0, q3, CAr, CAi, CAc);
+        } else if (w & 1) {
+            const int q2[1] = {2}, q3b[1] = {3};
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {                      // two diagonal blocks, each on its own panel (register copies, no address taken)
+                v4d r1[1] = {CBr[b]}, i1[1] = {CBi[b]}, c1[1] = {CBc[b]};
+                if (b == 0) gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 2, q2, r1, i1, c1);
+                else        gram_f64_shared<1, true, 0>(Xr, Xi, TRP, l15, kq, 3, q3b, r1, i1, c1);
+                CBr[b] = r1[0]; CBi[b] = i1[0]; CBc[b] = c1[0];
+            }
+        } else {
+            const int q12[2] = {1, 2};
+            gram_f64_shared<2, true, 0>(Xr, Xi, TRP, l15, kq, 1, q12, CBr, CBi, CBc);
+        }
+    }
+    // one tile of the blocks of deal()
+    __device__ __forceinline__ void tile_blocks(const float* __restrict__ Xr, const float* __restrict__ Xi, int TRP, int l15, int kq, int parity) {
+        if (parity == parA) {                                  // wave-uniform
+#pragma unroll
+            for (int q = 0; q < 3; ++q) if (aOn[q]) gram_f64_block(Xr, Xi, TRP, l15, kq, aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) if (bOn[q]) gram_f64_block(Xr, Xi, TRP, l15, kq, bI[q], bJ[q], CBr[q], CBi[q], CBc[q]);
+        }
+    }
+    // partial 2 lc + p of the item collects the blocks accumulated on tiles of parity p (each block exactly once per parity)
+    template <bool FULL> __device__ __forceinline__ void store(void* partial, int lc, int KK, int l15, int kq) const {
+        cx<double>* __restrict__ partA = reinterpret_cast<cx<double>*>(partial) + (size_t)(2 * lc + parA) * KK * KK;
+        cx<double>* __restrict__ partB = reinterpret_cast<cx<double>*>(partial) + (size_t)(2 * lc + (parA ^ 1)) * KK * KK;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) if (aOn[q]) gram_f64_store<FULL>(partA, KK, l15, kq, aI[q], aJ[q], CAr[q], CAi[q], CAc[q]);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) if (bOn[q]) gram_f64_store<FULL>(partB, KK, l15, kq, bI[q], bJ[q], CBr[q], CBi[q], CBc[q]);
+    }
+};
 
 }  // namespace tnqs

@@ -43,4 +43,26 @@ __device__ __forceinline__ void mac6x2(v16f& p, const P3& a, const P3& b, v16f& 
     p = TNQS_BF(a.h, b.h, p);             q = TNQS_BF(c.h, d.h, q);
 }
 
+// product of gram64_body (mfma_common.hpp) on the bf16 matrix cores: out = X conj(Y):  re = Xr Yr + Xi Yi,  im = Xi Yr + Xr (-Yi); one matrix
+// instruction covers the sixteen rows of a half (lane half h: eight of them), operands split on the fly
+struct Gram64X3 {
+    v16f Cr[2], Ci[2];
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { Cr[0][r] = 0.f; Cr[1][r] = 0.f; Ci[0][r] = 0.f; Ci[1][r] = 0.f; }
+    }
+    __device__ __forceinline__ void mac_half(const float (&xr)[8], const float (&xi)[8], const float (&yr)[2][8], const float (&yi)[2][8]) {
+        const P3 pxr = split8(xr), pxi = split8(xi);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const P3 pyr = split8(yr[b]), pyi = split8(yi[b]);
+            mac6x2<false>(Cr[b], pxr, pyr, Ci[b], pxi, pyr);
+            mac6x2<false>(Cr[b], pxi, pyi, Ci[b], pxr, neg(pyi));
+        }
+    }
+    __device__ __forceinline__ void finish() {}
+    __device__ __forceinline__ float re(int b, int r) const { return Cr[b][r]; }
+    __device__ __forceinline__ float im(int b, int r) const { return Ci[b][r]; }
+};
+
 }  // namespace tnqs

@@ -112,7 +112,15 @@ def test_fiber_gemm(dtype, mfma, D, PA, K, PB, Do, No):
 @pytest.mark.parametrize("dtype,acc64,mfma", [(0, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (0, 1, 1), (1, 1, 1)])       # (1, 1, 1): ComplexF64 operands with the matrix cores on (D K > 64 or < 4: the vector kernel; asserted below)
 @pytest.mark.parametrize("D,PA,K,PB,same", [(2, 64, 64, 16, 1), (2, 2, 64, 300, 1), (1, 64, 64, 32, 0), (2, 1024, 32, 32, 1), (2, 32, 32, 1000, 1), (2, 1, 32, 1024, 1), (2, 77, 19, 11, 1), (1, 64, 32, 1024, 0), (1, 2048, 32, 32, 0), (1, 2, 32, 700, 1), (1, 70, 17, 9, 0),
                                            (1, 2, 3, 5, 0), (1, 100, 10, 7, 0), (1, 1, 7, 130, 1), (2, 9, 5, 40, 1), (2, 30, 1, 1, 0),
-                                           (1, 64, 32, 33, 0), (2, 16, 16, 16, 1), (2, 512, 32, 8, 1), (3, 5, 5, 6, 0)])
+                                           (1, 64, 32, 33, 0), (2, 16, 16, 16, 1), (2, 512, 32, 8, 1), (3, 5, 5, 6, 0),
+                                           # the element-wise tile fill of the matrix-core kernels (more k-slices per thread than the register prefetch holds;
+                                           # tiles are TA = min(PA, 64), TB = min(PB, max(1, 64 / TA))):
+                                           # KK = 30, D = 3: one-element units, TA = 5, TB = 12, U = 180 units, KP = 1 and K = 10 > 8 -- mfma_gram32_kernel with Y != X
+                                           # (mfma = 1, f32 accumulation), a full tile and an edge tile of one b (PB = 13; with PB < 12 the tile is smaller and KP = 2)
+                                           (3, 5, 10, 13, 0),
+                                           # KK = 40, PA odd: one-element units, TA = 3, TB = 21, U = 63, KP = 4 and K / KP = 10 > 8 -- mfma_gram64_f64_kernel<false>
+                                           # (mfma = 1, acc64 = 1), two full tiles and an edge tile
+                                           (1, 3, 40, 50, 1)])
 def test_gram(dtype, acc64, mfma, D, PA, K, PB, same):
     if mfma and not acc64 and D * K > 32:
         pytest.skip('f32 MFMA Gram covers D*K <= 32')
