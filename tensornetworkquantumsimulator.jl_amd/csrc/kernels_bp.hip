@@ -4,6 +4,7 @@
 //   msg_finalize: abstract...:182-187 (m / sum(m)) + message_diff beliefpropagationcache.jl:17-21
 #include "kernels.hpp"
 #include "device_common.hpp"
+#include "jacobi_common.hpp"
 #include "launch_util.hpp"
 
 namespace tnqs {
@@ -435,9 +436,7 @@ template <class T> __global__ __launch_bounds__(256) void symg_finish_kernel(con
     }
     __syncthreads();
     for (int u = threadIdx.x; u < n; u += 256) {                  // descending order, stable
-        int rk = 0; double su = sig[u];
-        for (int v = 0; v < n; ++v) rk += (sig[v] > su) || (sig[v] == su && v < u);
-        perm[rk] = u;
+        perm[rank_desc(sig, n, u)] = u;
     }
     __syncthreads();
     for (int u = threadIdx.x; u < n; u += 256) it.S[u] = (double)(T)sig[perm[u]];

@@ -1,6 +1,7 @@
 // kernels_chol.hip -- Cholesky factor (and inverse) of a Gram matrix, and the environment square roots' prepare / finish pair.
 #include "kernels.hpp"
 #include "device_common.hpp"
+#include "jacobi_common.hpp"
 #include "launch_util.hpp"
 
 namespace tnqs {
@@ -38,25 +39,15 @@ __global__ __launch_bounds__(NT) void chol_kernel(const CholItem* __restrict__ i
         A[i + np * j] = v;
     }
     __syncthreads();
-    if (tid < 64) {                                                // largest diagonal entry (one wave)
-        double m = 0; for (int i = tid; i < n; i += 64) m = fmax(m, A[i + np * i].re);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-        if (tid == 0) s_dmax = m;
-    }
-    __syncthreads();
-    const double tiny = it.tau * s_dmax;
+    const double tiny = it.tau * max_diag(n, [&](int i) { return A[i + np * i].re; }, &s_dmax);
     // the pivot rule: a pivot at or below tiny (or not a number) flags the item and is replaced, so that the factorisation completes
     auto pivot_of = [&](int k, bool& bad) { double d = A[k + np * k].re; bad = !(d > tiny); return bad ? (tiny > 0 ? tiny : 1.0) : d; };
     // this thread's elements of the trailing triangle: number e = r (r + 1) / 2 + c, 0 <= c <= r  (n <= 96: at most 4560 / 1024 -> 5)
     unsigned char tr[UT], tc[UT];
 #pragma unroll
     for (int u = 0; u < UT; ++u) {
-        const int e = tid + NT * u;
-        int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-        while (r * (r + 1) / 2 > e) --r;
-        while ((r + 1) * (r + 2) / 2 <= e) ++r;
-        tr[u] = (unsigned char)r; tc[u] = (unsigned char)(e - r * (r + 1) / 2);
+        int r, c; tri_decode(tid + NT * u, r, c);
+        tr[u] = (unsigned char)r; tc[u] = (unsigned char)c;
     }
     const bool wantW = it.Winv != nullptr;
     for (int k = 0; k < n; ++k) {
@@ -150,15 +141,9 @@ __global__ __launch_bounds__(1024) void chol_packed_kernel(const CholItem* __res
         A[at(i, j)] = cmake<double>(0.5 * (a.re + b.re), 0.5 * (a.im - b.im));
     }
     __syncthreads();
-    if (tid < 64) {
-        double m = 0; for (int i = tid; i < n; i += 64) m = fmax(m, A[at(i, i)].re);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-        if (tid == 0) s_dmax = m;
-    }
-    __syncthreads();
-    if (it.shift > 0) { for (int i = tid; i < n; i += NT) A[at(i, i)].re += it.shift * s_dmax; __syncthreads(); }
-    const double tiny = it.tau * s_dmax;
+    const double dmax = max_diag(n, [&](int i) { return A[at(i, i)].re; }, &s_dmax);
+    if (it.shift > 0) { for (int i = tid; i < n; i += NT) A[at(i, i)].re += it.shift * dmax; __syncthreads(); }
+    const double tiny = it.tau * dmax;
     // right-looking with ONE barrier per column, as chol_kernel: trailing updates from the unscaled column, pivots by the same rule in every
     // thread, all columns scaled at the end
     auto pivot_of = [&](int k, bool& bad) { double d = A[at(k, k)].re; bad = !(d > tiny); return bad ? (tiny > 0 ? tiny : 1.0) : d; };

@@ -7,6 +7,7 @@
 //   bond_spectrum_finish_kernel   stage D: signed Rayleigh quotients of W (from its Jacobi factorisation, stage C) / tr W, sorted descending
 // One workgroup of 256 threads per bond, any 1 <= n <= 256.  Arithmetic: complex128 with plain f64 FMAs, every sum in a fixed order.
 #include "device_common.hpp"
+#include "jacobi_common.hpp"
 #include "kernels.hpp"
 
 namespace tnqs {
@@ -128,10 +129,8 @@ __global__ __launch_bounds__(256) void bond_spectrum_finish_kernel(const BondSpe
     }
     __syncthreads();
     for (int u = tid; u < n; u += 256) {
-        const double lu = lam[u], ku = lu == lu ? lu : -DBL_MAX;            // a NaN ranks last, so the ranks stay a permutation
-        int rk = 0;
-        for (int v = 0; v < n; ++v) { const double lv = lam[v], kv = lv == lv ? lv : -DBL_MAX; rk += (kv > ku) || (kv == ku && v < u); }
-        it.out[rk] = lu;
+        // a NaN ranks last, so the ranks stay a permutation
+        it.out[rank_desc(n, u, [&](int v) { const double lv = lam[v]; return lv == lv ? lv : -DBL_MAX; })] = lam[u];
     }
 }
 void launch_bond_spectrum_finish(hipStream_t s, const BondSpecItem* d_items, int nitems) {

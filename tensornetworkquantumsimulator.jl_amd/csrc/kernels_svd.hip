@@ -1,9 +1,13 @@
 // kernels_svd.hip -- one-sided Jacobi SVD / eigen factorisations: the global-memory and the LDS-resident kernel, the preconditioned theta SVD,
-// recovery of V, and the prepare / finish pair of the small sites.
+// recovery of V, and the prepare / finish pair of the small sites.  What the sweeps of the three Jacobi kernels share is in jacobi_common.hpp: the pair
+// schedule (jacobi_pair), the rotation (jacobi_rotation, jacobi_rotate), the scaling exponent (pow2_exponent) and the ranking (rank_desc); so are the triangular
+// numbering (tri_decode) and the largest pivot (max_diag) that theta_svd_pre_kernel shares with kernels_chol.hip.  The sweep loop itself is written out in each
+// of the three sweep functions: a shared driver taking the round as a callable cost registers.
 // Reference call sites replaced (paths relative to the reference repo):
 //   jacobi      : `eigen` (src/utils.jl:29-35,94-108) and `factorize_svd` (simple_update.jl:53-59)
 #include "kernels.hpp"
 #include "device_common.hpp"
+#include "jacobi_common.hpp"
 #include "launch_util.hpp"
 
 namespace tnqs {
@@ -12,28 +16,6 @@ namespace tnqs {
 // one-sided (Hestenes) Jacobi: A <- A J_1 J_2 ..., V <- V J_1 J_2 ...  until the columns of A are orthogonal.
 // One workgroup per matrix, one wave per column pair, round-robin pair ordering.  m <= 64 R (R = 4 or 8: up to 512 rows), any n.
 // ------------------------------------------------------------------------------------------------------------
-// Rotation parameters.  f32: the hardware reciprocal (square root).  f64: the compiler's IEEE sqrt and division are ~55 dependent
-// instructions each, and a Jacobi round has three of each on its critical path (most of the 1.2 us per round of the f64 kernels); the
-// hardware seeds (v_rsq_f64 / v_rcp_f64, ~2^-23 relative) with two Newton steps are ~8 instructions and good to a few ulp, which is all
-// a plane rotation needs (c^2 + s^2 = 1 to 1e-15).  Arguments are normal, positive numbers here (see the guards on g2).
-template <class T> __device__ __forceinline__ T fast_rsqrt(T x);
-template <> __device__ __forceinline__ float fast_rsqrt<float>(float x) { return __frsqrt_rn(x); }
-template <> __device__ __forceinline__ double fast_rsqrt<double>(double x) {
-    double y = __builtin_amdgcn_rsq(x);
-    double h = x * y; y = y * (1.5 - 0.5 * h * y);
-    h = x * y; y = y * (1.5 - 0.5 * h * y);
-    return y;
-}
-template <class T> __device__ __forceinline__ T fast_rcp(T x);
-template <> __device__ __forceinline__ float fast_rcp<float>(float x) { return __frcp_rn(x); }
-template <> __device__ __forceinline__ double fast_rcp<double>(double x) {
-    double y = __builtin_amdgcn_rcp(x);
-    y = y * (2.0 - x * y); y = y * (2.0 - x * y);
-    return y;
-}
-template <class T> __device__ __forceinline__ T fast_sqrt(T x);          // x >= 1 at the call sites
-template <> __device__ __forceinline__ float fast_sqrt<float>(float x) { return sqrtf(x); }
-template <> __device__ __forceinline__ double fast_sqrt<double>(double x) { return x * fast_rsqrt<double>(x); }
 template <class T, int R>          // R rows per lane: m <= 64 R
 __global__ __launch_bounds__(1024) void jacobi_kernel(const JacobiItem* __restrict__ items, int max_sweeps) {
     __shared__ int s_rot;
@@ -54,8 +36,7 @@ __global__ __launch_bounds__(1024) void jacobi_kernel(const JacobiItem* __restri
     double frog = 0;
     for (int e = threadIdx.x; e < m * n; e += blockDim.x) { cx<T> v = A[e]; frog += (double)v.re * v.re + (double)v.im * v.im; }
     frog = block_sum(frog, s_redg);
-    int kexp = 0;
-    if (frog > 0 && frog < 1e300) { kexp = -(ilogb(frog) / 2); kexp = kexp > 120 ? 120 : (kexp < -120 ? -120 : kexp); }
+    const int kexp = pow2_exponent(frog);
     const T sc_in = (T)ldexp(1.0, kexp), sc_out = (T)ldexp(1.0, -kexp);
     if (kexp != 0) { for (int e = threadIdx.x; e < m * n; e += blockDim.x) { cx<T> v = A[e]; A[e] = cmake<T>(v.re * sc_in, v.im * sc_in); } }
     __syncthreads();
@@ -65,10 +46,7 @@ __global__ __launch_bounds__(1024) void jacobi_kernel(const JacobiItem* __restri
         __syncthreads();
         for (int round = 0; round < ne - 1; ++round) {
             for (int pi = w; pi < ne / 2; pi += nw) {
-                int p, q;
-                if (pi == 0) { p = ne - 1; q = round; }
-                else { p = (round + pi) % (ne - 1); q = (round - pi + (ne - 1)) % (ne - 1); }
-                if (p > q) { int t = p; p = q; q = t; }
+                int p, q; jacobi_pair(ne, round, pi, p, q);
                 if (q >= n) continue;
                 cx<T> ap[R], aq[R];
                 T alpha = 0, beta = 0, gre = 0, gim = 0;
@@ -86,31 +64,17 @@ __global__ __launch_bounds__(1024) void jacobi_kernel(const JacobiItem* __restri
                 alpha = wave_sum(alpha); beta = wave_sum(beta); gre = wave_sum(gre); gim = wave_sum(gim);
                 const T g2 = gre * gre + gim * gim;
                 if (g2 > (sizeof(T) == 4 ? (T)1e-36 : (T)1e-290) && g2 > tol * tol * alpha * beta) {      // (g2 normal: see fast_rsqrt)
-                    const T iga = fast_rsqrt<T>(g2);
-                    const T pre = gre * iga, pim = -gim * iga;         // e^{-i phi}
-                    const T zeta = (beta - alpha) * (T)0.5 * iga;
-                    const T az = fabs(zeta);
-                    const T t = (zeta >= 0 ? (T)1 : (T)-1) * fast_rcp<T>(az + fast_sqrt<T>(1 + az * az));
-                    const T c = fast_rsqrt<T>(1 + t * t), sn = c * t;
+                    const JacobiRot<T> rot = jacobi_rotation(alpha, beta, gre, gim, g2);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         int i = lane + 64 * r;
-                        if (i < m) {
-                            T qre = aq[r].re * pre - aq[r].im * pim, qim = aq[r].re * pim + aq[r].im * pre;
-                            A[i + (size_t)m * p] = cmake<T>(c * ap[r].re - sn * qre, c * ap[r].im - sn * qim);
-                            A[i + (size_t)m * q] = cmake<T>(sn * ap[r].re + c * qre, sn * ap[r].im + c * qim);
-                        }
+                        if (i < m) jacobi_rotate(rot, ap[r], aq[r], A[i + (size_t)m * p], A[i + (size_t)m * q]);
                     }
                     if (V)
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         int i = lane + 64 * r;
-                        if (i < n) {
-                            cx<T> vp = V[i + (size_t)n * p], vq = V[i + (size_t)n * q];
-                            T qre = vq.re * pre - vq.im * pim, qim = vq.re * pim + vq.im * pre;
-                            V[i + (size_t)n * p] = cmake<T>(c * vp.re - sn * qre, c * vp.im - sn * qim);
-                            V[i + (size_t)n * q] = cmake<T>(sn * vp.re + c * qre, sn * vp.im + c * qim);
-                        }
+                        if (i < n) { cx<T>& vp = V[i + (size_t)n * p]; cx<T>& vq = V[i + (size_t)n * q]; jacobi_rotate(rot, vp, vq, vp, vq); }
                     }
                     if (lane == 0) s_rot = 1;
                 }
@@ -175,12 +139,7 @@ __device__ __forceinline__ int jacobi_lds_sweeps(cx<T>* A, cx<T>* V, bool hasV, 
                 // wave-uniform trip count (the row reductions need all four quarter-waves); idle quarters are predicated off
                 const int pi = base + grp;
                 int p = 0, q = 0; bool act = FULL || pi < ne / 2;
-                if (act) {
-                    if (pi == 0) { p = ne - 1; q = round; }
-                    else { p = round + pi; if (p >= ne - 1) p -= ne - 1; q = round - pi; if (q < 0) q += ne - 1; }
-                    if (p > q) { int t = p; p = q; q = t; }
-                    if (!FULL) act = q < n;
-                }
+                if (act) { jacobi_pair(ne, round, pi, p, q); if (!FULL) act = q < n; }
                 cx<T> ap[RQ], aq[RQ];
                 T alpha = 0, beta = 0, gre = 0, gim = 0;
 #pragma unroll
@@ -197,33 +156,18 @@ __device__ __forceinline__ int jacobi_lds_sweeps(cx<T>* A, cx<T>* V, bool hasV, 
                 alpha = row16_sum(alpha); beta = row16_sum(beta); gre = row16_sum(gre); gim = row16_sum(gim);
                 const T g2 = gre * gre + gim * gim;
                 // f32: g2 must be a NORMAL number -- the fast reciprocal square root returns inf for (flushed) denormals
-                const bool rot = act && g2 > (sizeof(T) == 4 ? (T)1e-36 : (T)1e-290) && g2 > tol * tol * alpha * beta && !(alpha < tiny && beta < tiny);
-                if (rot) {
-                    const T iga = fast_rsqrt<T>(g2);
-                    const T pre = gre * iga, pim = -gim * iga;
-                    const T zeta = (beta - alpha) * (T)0.5 * iga;
-                    const T az = fabs(zeta);
-                    const T t = (zeta >= 0 ? (T)1 : (T)-1) * fast_rcp<T>(az + fast_sqrt<T>(1 + az * az));
-                    const T c = fast_rsqrt<T>(1 + t * t), sn = c * t;
+                if (act && g2 > (sizeof(T) == 4 ? (T)1e-36 : (T)1e-290) && g2 > tol * tol * alpha * beta && !(alpha < tiny && beta < tiny)) {
+                    const JacobiRot<T> rot = jacobi_rotation(alpha, beta, gre, gim, g2);
 #pragma unroll
                     for (int r = 0; r < RQ; ++r) {
                         int i = l16 + 16 * r;
-                        if (FULL || (r < rq && i < m)) {
-                            T qre = aq[r].re * pre - aq[r].im * pim, qim = aq[r].re * pim + aq[r].im * pre;
-                            A[i + mp * p] = cmake<T>(c * ap[r].re - sn * qre, c * ap[r].im - sn * qim);
-                            A[i + mp * q] = cmake<T>(sn * ap[r].re + c * qre, sn * ap[r].im + c * qim);
-                        }
+                        if (FULL || (r < rq && i < m)) jacobi_rotate(rot, ap[r], aq[r], A[i + mp * p], A[i + mp * q]);
                     }
                     if (hasV) {
 #pragma unroll
                         for (int r = 0; r < RQ; ++r) {
                             int i = l16 + 16 * r;
-                            if (r < rqv && i < n) {
-                                cx<T> vp = V[i + np_ * p], vq = V[i + np_ * q];
-                                T qre = vq.re * pre - vq.im * pim, qim = vq.re * pim + vq.im * pre;
-                                V[i + np_ * p] = cmake<T>(c * vp.re - sn * qre, c * vp.im - sn * qim);
-                                V[i + np_ * q] = cmake<T>(sn * vp.re + c * qre, sn * vp.im + c * qim);
-                            }
+                            if (r < rqv && i < n) { cx<T>& vp = V[i + np_ * p]; cx<T>& vq = V[i + np_ * q]; jacobi_rotate(rot, vp, vq, vp, vq); }
                         }
                     }
                     if (l16 == 0) *s_rot = 1;
@@ -253,11 +197,7 @@ __device__ __forceinline__ int jacobi_lds_sweeps_f32_full(cx<float>* A, int m, i
         __syncthreads();
         for (int round = 0; round < ne - 1; ++round) {
             for (int base = 4 * w; base < ne / 2; base += nslots) {
-                const int pi = base + grp;
-                int p, q;
-                if (pi == 0) { p = ne - 1; q = round; }
-                else { p = round + pi; if (p >= ne - 1) p -= ne - 1; q = round - pi; if (q < 0) q += ne - 1; }
-                if (p > q) { int t = p; p = q; q = t; }
+                int p, q; jacobi_pair(ne, round, base + grp, p, q);
                 v2f* cp = Av + l16 + mp * p; v2f* cq = Av + l16 + mp * q;
                 v2f ap[RQ], aq[RQ];
                 v2f sa = {0.f, 0.f}, sb = {0.f, 0.f}, g1 = {0.f, 0.f}, g2v = {0.f, 0.f};
@@ -270,15 +210,9 @@ __device__ __forceinline__ int jacobi_lds_sweeps_f32_full(cx<float>* A, int m, i
                 }
                 float alpha = row16_sum(sa.x + sa.y), beta = row16_sum(sb.x + sb.y), gre = row16_sum(g1.x + g1.y), gim = row16_sum(g2v.x - g2v.y);
                 const float g2 = gre * gre + gim * gim;
-                const bool rot = g2 > 1e-36f && g2 > tol * tol * alpha * beta && !(alpha < tiny && beta < tiny);
-                if (rot) {
-                    const float iga = fast_rsqrt<float>(g2);
-                    const float pre = gre * iga, pim = -gim * iga;
-                    const float zeta = (beta - alpha) * 0.5f * iga;
-                    const float az = fabsf(zeta);
-                    const float t = (zeta >= 0 ? 1.f : -1.f) * fast_rcp<float>(az + sqrtf(1 + az * az));
-                    const float c = fast_rsqrt<float>(1 + t * t), sn = c * t;
-                    const v2f e1 = {pre, pim}, e2 = {-pim, pre}, cc = {c, c}, ss = {sn, sn};
+                if (g2 > 1e-36f && g2 > tol * tol * alpha * beta && !(alpha < tiny && beta < tiny)) {
+                    const JacobiRot<float> rot = jacobi_rotation(alpha, beta, gre, gim, g2);
+                    const v2f e1 = {rot.pre, rot.pim}, e2 = {-rot.pim, rot.pre}, cc = {rot.c, rot.c}, ss = {rot.sn, rot.sn};
 #pragma unroll
                     for (int r = 0; r < RQ; ++r) {
                         const v2f qv = __builtin_shufflevector(aq[r], aq[r], 0, 0) * e1 + __builtin_shufflevector(aq[r], aq[r], 1, 1) * e2;
@@ -324,11 +258,7 @@ __global__ __launch_bounds__(1024) void jacobi_lds_kernel(const JacobiItem* __re
             if (lane == 0) s_cn[j] = s2 == s2 ? s2 : 0.f;
         }
         __syncthreads();
-        for (int j = threadIdx.x; j < n; j += blockDim.x) {
-            int rk = 0; const float cj = s_cn[j];
-            for (int v = 0; v < n; ++v) rk += (s_cn[v] > cj) || (s_cn[v] == cj && v < j);
-            s_pos[j] = (unsigned char)rk;
-        }
+        for (int j = threadIdx.x; j < n; j += blockDim.x) s_pos[j] = (unsigned char)rank_desc(s_cn, n, j);
         __syncthreads();
         for (int e = threadIdx.x; e < m * n; e += blockDim.x) A[(e % m) + mp * (int)s_pos[e / m]] = Ag[e];
     } else
@@ -346,8 +276,7 @@ __global__ __launch_bounds__(1024) void jacobi_lds_kernel(const JacobiItem* __re
     // tensors carry a small norm: singular values 1e-5 already put the products of the smaller columns into the denormal range, the
     // rotation phases lose their unit modulus and the "rotations" stop being unitary).  The matrix is therefore scaled by an exact power
     // of two to ||A||_F = O(1) for the sweeps and scaled back when it is written out; V does not change.
-    int kexp = 0;
-    if (fro > 0 && fro < 1e300) { kexp = -(ilogb(fro) / 2); kexp = kexp > 120 ? 120 : (kexp < -120 ? -120 : kexp); }
+    const int kexp = pow2_exponent(fro);
     const T sc_in = (T)ldexp(1.0, kexp), sc_out = (T)ldexp(1.0, -kexp);
     if (kexp != 0) {
         for (int e = threadIdx.x; e < m * n; e += blockDim.x) { cx<T>& v = A[(e % m) + mp * (e / m)]; v.re *= sc_in; v.im *= sc_in; }
@@ -418,11 +347,7 @@ __global__ __launch_bounds__(NT) void theta_svd_pre_kernel(const JacobiItem* __r
         if (lane == 0) { s_cn[j] = s2 == s2 ? s2 : 0.0; if (!(s2 == s2) || s2 > 1e300) s_bad = 1; }
     }
     __syncthreads();
-    for (int j = tid; j < n; j += NT) {
-        int rk = 0; const double cj = s_cn[j];
-        for (int v = 0; v < n; ++v) rk += (s_cn[v] > cj) || (s_cn[v] == cj && v < j);
-        s_pos[j] = (unsigned char)rk; s_perm[rk] = (unsigned char)j;
-    }
+    for (int j = tid; j < n; j += NT) { const int rk = rank_desc(s_cn, n, j); s_pos[j] = (unsigned char)rk; s_perm[rk] = (unsigned char)j; }
     double fro = 0; for (int j = tid; j < n; j += NT) fro += s_cn[j];
     fro = block_sum(fro, s_red);                                                         // (also orders s_pos before the load below)
     // Degenerate input (round-5 advisor finding).  theta identically ZERO: its SVD is U Sigma = 0 -- A stays as it is, V = 0; before this guard the largest
@@ -440,8 +365,7 @@ __global__ __launch_bounds__(NT) void theta_svd_pre_kernel(const JacobiItem* __r
         if (tid == 0 && it.sweeps_out) *it.sweeps_out = 0;
         return;
     }
-    int kexp = 0;
-    if (fro > 0 && fro < 1e300) { kexp = -(ilogb(fro) / 2); kexp = kexp > 120 ? 120 : (kexp < -120 ? -120 : kexp); }
+    const int kexp = pow2_exponent(fro);
     const double sc2 = ldexp(1.0, 2 * kexp), sc_out = ldexp(1.0, -kexp);                 // G is formed at ||A||_F = O(1): L, the sweeps and s_sig live at that scale
     fro = ldexp(fro, 2 * kexp);
     for (int e = tid; e < m * n; e += NT) Mf[(e % m) + mp * (int)s_pos[e / m]] = Ag[e];
@@ -453,10 +377,7 @@ __global__ __launch_bounds__(NT) void theta_svd_pre_kernel(const JacobiItem* __r
     {
         const int nt = (n + 15) >> 4, ntile = nt * (nt + 1) / 2;
         for (int t = w; t < ntile; t += nw) {
-            int ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-            while (ti * (ti + 1) / 2 > t) --ti;
-            while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-            const int tj = t - ti * (ti + 1) / 2;                                       // ti >= tj
+            int ti, tj; tri_decode(t, ti, tj);                                          // ti >= tj
             const int ia = 16 * ti + l15, ja = 16 * tj + l15;
             const cx<float>* ci_ = Mf + mp * (ia < n ? ia : 0); const cx<float>* cj_ = Mf + mp * (ja < n ? ja : 0);
             v4d cr = {0, 0, 0, 0}, ci = {0, 0, 0, 0};
@@ -474,25 +395,15 @@ __global__ __launch_bounds__(NT) void theta_svd_pre_kernel(const JacobiItem* __r
     __syncthreads();
     PRE_STAMP(2);
     // ---- 3. Cholesky, right-looking from the unscaled column, one barrier per column (see chol_kernel) -------------------------------------
-    if (tid < 64) {
-        double mx = 0; for (int i = tid; i < n; i += 64) mx = fmax(mx, Gd[i + gp * i].re);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-        if (tid == 0) s_dmax = mx;
-    }
-    __syncthreads();
-    const double ptiny = 1e-13 * s_dmax;
+    const double ptiny = 1e-13 * max_diag(n, [&](int i) { return Gd[i + gp * i].re; }, &s_dmax);
     auto pivot_of = [&](int k) { const double d = Gd[k + gp * k].re; return (d > ptiny) ? d : (ptiny > 0 ? ptiny : 1.0); };
     {
         constexpr int UT = (64 * 63 / 2 + NT - 1) / NT;           // trailing-triangle elements a thread owns at most (nested triangular numbering)
         unsigned char tr[UT], tc[UT];
 #pragma unroll
         for (int u = 0; u < UT; ++u) {
-            const int e = tid + NT * u;
-            int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-            while (r * (r + 1) / 2 > e) --r;
-            while ((r + 1) * (r + 2) / 2 <= e) ++r;
-            tr[u] = (unsigned char)r; tc[u] = (unsigned char)(e - r * (r + 1) / 2);
+            int r, c; tri_decode(tid + NT * u, r, c);
+            tr[u] = (unsigned char)r; tc[u] = (unsigned char)c;
         }
         for (int k = 0; k < n - 1; ++k) {
             // a collapsed pivot (A rank deficient: the Schur complement left is rounding noise) ends the column: no trailing update from it, its entries below
@@ -558,11 +469,7 @@ __global__ __launch_bounds__(NT) void theta_svd_pre_kernel(const JacobiItem* __r
     __syncthreads();
     const int cap = (it.cap > 0 && it.cap < n) ? it.cap : n;
     __shared__ unsigned char s_rank[64];
-    for (int j = tid; j < n; j += NT) {
-        int rk = 0; const double sj_ = s_sig[j];
-        for (int v = 0; v < n; ++v) rk += (s_sig[v] > sj_) || (s_sig[v] == sj_ && v < j);
-        s_keep[rk] = (unsigned char)j; s_rank[j] = (unsigned char)rk;                // columns by decreasing singular value
-    }
+    for (int j = tid; j < n; j += NT) { const int rk = rank_desc(s_sig, n, j); s_keep[rk] = (unsigned char)j; s_rank[j] = (unsigned char)rk; }      // columns by decreasing singular value
     __syncthreads();
     // the consumer (gate_finish) ranks the columns again, by their f32 norms: everything within 1e-4 of the cap-th singular value is formed as well, so that a tie
     // at the cap -- the equal pseudo-values of collapsed pivots, or a degenerate pair -- can never make it pick a column that was not formed

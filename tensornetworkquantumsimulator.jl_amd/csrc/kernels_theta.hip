@@ -4,6 +4,7 @@
 //   gate_theta / gate_finish : simple_update.jl:51-59 + NDTensors truncate! rule, apply_gates.jl:126-135
 #include "kernels.hpp"
 #include "device_common.hpp"
+#include "jacobi_common.hpp"
 
 namespace tnqs {
 
@@ -447,9 +448,7 @@ __global__ __launch_bounds__(1024) void gate_finish_kernel(const GateItem* __res
     }
     __syncthreads();
     for (int u = threadIdx.x; u < ncol; u += blockDim.x) {    // rank by counting (descending, stable)
-        int rk = 0; double su = sig[u];
-        for (int v = 0; v < ncol; ++v) rk += (sig[v] > su) || (sig[v] == su && v < u);
-        perm[rk] = u;
+        perm[rank_desc(sig, ncol, u)] = u;
     }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -30,7 +30,8 @@ def jacobi(a, dtype):
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
-@pytest.mark.parametrize("shape", [(3, 3), (6, 6), (12, 12), (12, 6), (17, 9), (40, 40), (64, 64), (128, 128), (130, 70), (1, 1), (5, 2), (256, 256)])
+@pytest.mark.parametrize("shape", [(3, 3), (6, 6), (12, 12), (12, 6), (17, 9), (40, 40), (64, 64), (128, 128), (130, 70), (1, 1), (5, 2), (256, 256),
+                                   (96, 96), (80, 48)])         # six rows per lane: full tiles (f64: V recovered) and the guarded path with V in LDS
 def test_jacobi_svd(dtype, shape):
     rng = np.random.default_rng(sum(shape) + dtype)
     a = rnd(rng, shape, np.complex128)
